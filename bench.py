@@ -16,10 +16,21 @@ no data-path collective on the inference path) -> weak scaling.
     --workload config1|config2|hires  = BASELINE configs[0] shapes (B=1) | configs[1] (default, the metric's
                                         workload; also the per-GPU shape of configs[2]) | configs[4] per-GPU shapes
 
-Prints ONE JSON line (rank 0).  Extra objects: `roofline` (dominant kernel =
-the MFMA convs), `roofline_l1` (the HBM-bound lift-splat kernel), `levels`
-(L1 = lift-splat only, L2 = full hot path), `cpu_baseline` (the CPU oracle
-timed on this host), `train` (fwd+bwd+Adam step with RCCL gradient all-reduce).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the K
+steps and prints the headline (`value`, `ms_per_step`, ...).  `--full` adds the
+extra legs and their objects: `roofline` (dominant kernel = the MFMA convs),
+`roofline_l1` (the HBM-bound lift-splat kernel), `levels` (L1 = lift-splat
+only, L2 = full hot path, cold start, two batches in flight), `cpu_baseline`
+(the CPU oracle timed on this host), `train` (fwd+bwd+Adam step with RCCL
+gradient all-reduce).
+
+    python bench.py --gpus 1 --steps 50 --warmup 10 --full
+    python bench.py --gpus 1 --steps 50 --warmup 10 --dump-outputs DIR
+
+`--dump-outputs DIR` writes the BEV output of the last timed step as DIR/bev.npy
+(float32; DIR/bev_rank<r>.npy per rank when N > 1).  Inputs and weights are
+seeded, so two builds run with the same arguments can be compared output for
+output.
 """
 import argparse
 import json
@@ -135,15 +146,22 @@ def main():
                          "configs[1] (default, the metric's workload, = the per-GPU shape of configs[2]); hires = "
                          "configs[4] per-GPU shapes (6 x 704x256, D=60, 400x400 BEV, batch 2/GPU)")
     ap.add_argument("--dry-launch", action="store_true", help="launcher / rendezvous check on the CPU (gloo), no GPU work")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the extra legs around the timed steps: cold start, roofline and dominant-kernel passes, "
+                         "L1 (lift-splat only), training step, two batches in flight, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the BEV output of the last timed step as DIR/bev.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline leg")
+    ap.add_argument("--no-train", action="store_true", help="with --full: skip the training leg")
     ap.add_argument("--two-streams", action=argparse.BooleanOptionalAction, default=True,
-                    help="extra informational leg (levels.two_batches_in_flight_fps): the same steps with two batches in "
-                         "flight on two HIP streams; `value` stays the single-stream loop")
+                    help="with --full: extra informational leg (levels.two_batches_in_flight_fps): the same steps with two "
+                         "batches in flight on two HIP streams; `value` stays the single-stream loop")
     ap.add_argument("--train-steps", type=int, default=16)
     ap.add_argument("--spinup-ms", type=float, default=300.0,
                     help="keep the GPU under load this long before the warm-up steps (DVFS ramp; 0 = off)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)  # does not return
@@ -215,16 +233,18 @@ def main():
         # milliseconds under load to reach the clock it then sustains; measured on MI355X, the same kernels run 4 %
         # slower in a 20-step (10 ms) run that starts from an idle device than in a 400-step one (conv group 458 vs
         # 435 us).  The W warm-up steps and the K timed steps below are untouched.
-        # The driver's nominal protocol first, from a device that has only seen the W warm-up steps: reported as
-        # levels.cold_start_fps (both numbers in the line).
+        # With --full, the driver's nominal protocol first, from a device that has only seen the W warm-up steps:
+        # reported as levels.cold_start_fps (both numbers in the line).
         for _ in range(args.warmup):
             step()
         barrier()
-        tc = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        barrier()
-        dt_cold = time.perf_counter() - tc
+        dt_cold = dt_l1 = 0.0
+        if args.full:
+            tc = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            barrier()
+            dt_cold = time.perf_counter() - tc
         t_spin = time.perf_counter() + args.spinup_ms * 1e-3
         while time.perf_counter() < t_spin:
             step()
@@ -236,39 +256,45 @@ def main():
         ops.set_timer(None)
         barrier()
         t0 = time.perf_counter()
-        for _ in range(args.steps):
+        for _ in range(args.steps - 1):
             step()
+        y = step()   # only the last result is kept: no step allocates its output while the previous one is alive
         barrier()
         dt = time.perf_counter() - t0
-        # ---- roofline pass: the same K steps with ONE HIP-event bracket around the lift-splat level and one around
-        # the BevEncode launch group (outside the timed region) -------------------------------------------------
-        timer = ops.KernelTimer()
-        ops.set_timer(timer)
-        for _ in range(args.steps):
-            step()
-        barrier()
-        ops.set_timer(None)
-        spans = timer.totals_ms()
-        # ---- the dominant kernel on its own (its own pass: a bracket costs ~10 us of idle) ----
-        # Same steps again with BevEncode's recorded launch list replayed in two calls, so that its LAST launch - up2:
-        # x2 upsample + 3x3 conv 256 -> 128 + BN + ReLU + fused 1x1 head, 38 % of the step's FLOPs - gets a HIP-event
-        # bracket of its own; profiles/r02_bench_kernel_summary.txt holds the same kernel's rocprofv3 average.
-        timer_k = ops.KernelTimer(last_conv=True)
-        ops.set_timer(timer_k)
-        for _ in range(args.steps):
-            step()
-        barrier()
-        ops.set_timer(None)
-        n_dom, ms_dom = timer_k.totals_ms().get("conv_plan_last", (0, 0.0))
-        # ---- L1 only (lift-splat level), same protocol ---------------------------------
-        for _ in range(3):
-            step_l1()
-        barrier()
-        t1 = time.perf_counter()
-        for _ in range(args.steps):
-            step_l1()
-        barrier()
-        dt_l1 = time.perf_counter() - t1
+        if args.dump_outputs:  # the last timed step's result, copied before any later pass can reuse its buffers
+            dump_outputs(args.dump_outputs, {"bev" if world == 1 else "bev_rank%d" % rank: y}, DUMP_BYTES // world)
+        del y
+        if args.full:
+            # ---- roofline pass: the same K steps with ONE HIP-event bracket around the lift-splat level and one
+            # around the BevEncode launch group (outside the timed region) ---------------------------------------
+            timer = ops.KernelTimer()
+            ops.set_timer(timer)
+            for _ in range(args.steps):
+                step()
+            barrier()
+            ops.set_timer(None)
+            spans = timer.totals_ms()
+            # ---- the dominant kernel on its own (its own pass: a bracket costs ~10 us of idle) ----
+            # Same steps again with BevEncode's recorded launch list replayed in two calls, so that its LAST launch -
+            # up2: x2 upsample + 3x3 conv 256 -> 128 + BN + ReLU + fused 1x1 head, 38 % of the step's FLOPs - gets a
+            # HIP-event bracket of its own; profiles/r02_bench_kernel_summary.txt holds the same kernel's rocprofv3
+            # average.
+            timer_k = ops.KernelTimer(last_conv=True)
+            ops.set_timer(timer_k)
+            for _ in range(args.steps):
+                step()
+            barrier()
+            ops.set_timer(None)
+            n_dom, ms_dom = timer_k.totals_ms().get("conv_plan_last", (0, 0.0))
+            # ---- L1 only (lift-splat level), same protocol ---------------------------------
+            for _ in range(3):
+                step_l1()
+            barrier()
+            t1 = time.perf_counter()
+            for _ in range(args.steps):
+                step_l1()
+            barrier()
+            dt_l1 = time.perf_counter() - t1
 
     guards = {"inference": read_guards()}
     tmax = torch.tensor([dt, dt_l1, dt_cold], dtype=torch.float64, device=dev)
@@ -289,34 +315,6 @@ def main():
     frames = args.steps * B * world
     fps = frames / dt
 
-    # ---- roofline of the dominant kernel(s), from the HIP-event brackets -----------------
-    n_conv, ms_conv = spans.get("bevencode", (0, 0.0))   # one bracket per step around the 16 conv launches
-    n_spl, ms_spl = spans.get("lift_splat_level", (0, 0.0))   # one bracket around K2 || K3, region_fill, region_splat
-    conv_flops_step = bevencode_flops(X, Y) * B
-    peak_tf = MFMA_BF16_TFLOPS if args.precision == "bf16" else MFMA_F32_TFLOPS
-    conv_tf = conv_flops_step * args.steps / (ms_conv * 1e-3) / 1e12 if ms_conv else 0.0
-    out_bytes = 2 if args.precision == "bf16" else 4
-    # algorithmic bytes of the lift-splat level: trunk features in, BEV grid out
-    l1_bytes_step = B * l1_bytes_per_frame(6, fH, fW, C, X, Y, Z, D, out_bytes)
-    splat_bytes_step = l1_bytes_step
-    spl_gbs = splat_bytes_step * args.steps / (ms_spl * 1e-3) / 1e9 if ms_spl else 0.0
-
-    conv_traffic, splat_traffic = pmc_traffic("conv_"), pmc_traffic("region_splat_kernel")
-    l1_launches = 3 if os.environ.get("LSS_SPLAT_DIRECT") == "0" else 2   # (splat.hip: the direct form is the default)
-    # the dominant kernel by itself: algorithmic FLOPs of ONE launch / its own average duration
-    dom_flops = 2.0 * B * X * Y * 128 * (256 * 9 + 4)   # 3x3 256 -> 128 on the upsampled grid + the 1x1 head (4 classes)
-    dom_us = ms_dom * 1e3 / n_dom if n_dom else 0.0
-    dom_tf = dom_flops / (dom_us * 1e-6) / 1e12 if dom_us else 0.0
-    ring = os.environ.get("LSS_CONV_RING") != "0" and args.precision == "bf16"
-    dom_name = "conv_ring_kernel<1, true" if ring else "conv_lds_kernel<2, 128, 1, 3, 3, 1, 32, 1, true"
-    dom_traffic = pmc_traffic(dom_name)
-    dominant = {"kernel": ("conv_ring_kernel<MODE 1, HEAD> (loader / consumer ring kernel, csrc/conv_ring.hip)" if ring else
-                           "conv_lds_kernel<2,128,1,3,3,1,32,1,HEAD>") + " = BevEncode.up2: x2 bilinear upsample (fused gather) + 3x3 "
-                          "conv 256->128 + BN + ReLU + 1x1 head, one launch; own HIP-event bracket in a separate pass of the "
-                          "same K steps (outside the timed region)",
-                "bound": "mfma", "flops_per_launch": dom_flops, "avg_us": dom_us, "launches": n_dom, "achieved": dom_tf,
-                "peak": peak_tf, "unit": "TFLOP/s", "frac": dom_tf / peak_tf if peak_tf else 0.0,
-                "traffic": dom_traffic[0], "traffic_unit": "HBM bytes per launch (PMC)", "traffic_source": dom_traffic[1]}
     out = {
         "metric": "BEV frames/sec (6-cam 352x128 -> 200x200x64), full hot path: CamEncode lift + splat + BevEncode",
         "value": fps, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -334,37 +332,69 @@ def main():
                                          "-> BevEncode -> 400x400x4" % B}[args.workload],
                    "batch_per_gpu": B, "global_batch": B * world, "parallelism": "dp%d (sample-sharded, no collective)" % world,
                    "precision": args.precision, "spinup_ms": args.spinup_ms, "calibration": "CPU tensors per step; 3x3 inverses on host (exact-index contract), 576 floats passed in the kernel arguments (no H2D copy)"},
-        "roofline": {"kernel": "conv_lds_kernel / conv_ks_kernel / conv_ring_kernel: the 16 BevEncode launches of a step (stride-2 convs carry their 1x1 downsample, "
-                               "up2 its head; the ten 3x3 / stride-1 convs of layer1-3 run on the K-split one-pass kernel, the three big 3x3 layers on the ring kernel), one HIP-event "
-                               "bracket around the group (per-launch brackets cost ~10 us of idle each)",
-                     "bound": "mfma", "achieved": conv_tf, "peak": peak_tf, "unit": "TFLOP/s",
-                     "frac": conv_tf / peak_tf, "traffic": conv_traffic[0], "traffic_unit": "HBM bytes per launch (PMC)",
-                     "traffic_source": conv_traffic[1], "launches": n_conv * 16,
-                     "avg_us": ms_conv * 1e3 / max(n_conv * 16, 1), "flops_per_step": conv_flops_step,
-                     "dominant_kernel": dominant},
-        "roofline_l1": {"kernel": ("lift-splat level = depthnet_rows_and_voxels (K2 || K3, writes the region entries itself) + "
-                                   "region_splat (direct form: 2 launches, one HIP-event bracket); `traffic` is region_splat_kernel's own"
-                                   if l1_launches == 2 else
-                                   "lift-splat level = depthnet_rows_and_voxels (K2 || K3) + region_fill + region_splat "
-                                   "(3 launches, one HIP-event bracket); `traffic` is region_splat_kernel's own"),
-                        "bound": "hbm", "achieved": spl_gbs, "peak": HBM_PEAK_GBS,
-                        "unit": "GB/s", "frac": spl_gbs / HBM_PEAK_GBS, "traffic": splat_traffic[0],
-                        "traffic_unit": "HBM bytes per launch (PMC)", "traffic_source": splat_traffic[1],
-                        "launches": n_spl * l1_launches,
-                        "avg_us": ms_spl * 1e3 / max(n_spl * l1_launches, 1), "level_us": ms_spl * 1e3 / max(n_spl, 1),
-                        "bytes_per_step": splat_bytes_step},
         "per_rank_fps": per_rank, "comm": comm,
-        "levels": {"L2_hot_path_fps": fps,
-                   "cold_start_fps": frames / dt_cold,
-                   "cold_start_note": "the same K steps timed right after the first W warm-up steps, before the "
-                                      "config.spinup_ms spin-up (device still ramping its clock)",
-                   "L1_lift_splat_fps": frames / dt_l1, "L1_ms_per_step": dt_l1 / args.steps * 1e3,
-                   "L1_algorithmic_GBs": l1_bytes_step * args.steps * world / dt_l1 / 1e9,
-                   "L1_frac_of_hbm_peak": l1_bytes_step * args.steps / dt_l1 / 1e9 / HBM_PEAK_GBS},
     }
 
+    if args.full:
+        # ---- roofline of the dominant kernel(s), from the HIP-event brackets -----------------
+        n_conv, ms_conv = spans.get("bevencode", (0, 0.0))   # one bracket per step around the 16 conv launches
+        n_spl, ms_spl = spans.get("lift_splat_level", (0, 0.0))   # one bracket around K2 || K3, region_fill, region_splat
+        conv_flops_step = bevencode_flops(X, Y) * B
+        peak_tf = MFMA_BF16_TFLOPS if args.precision == "bf16" else MFMA_F32_TFLOPS
+        conv_tf = conv_flops_step * args.steps / (ms_conv * 1e-3) / 1e12 if ms_conv else 0.0
+        out_bytes = 2 if args.precision == "bf16" else 4
+        # algorithmic bytes of the lift-splat level: trunk features in, BEV grid out
+        l1_bytes_step = B * l1_bytes_per_frame(6, fH, fW, C, X, Y, Z, D, out_bytes)
+        splat_bytes_step = l1_bytes_step
+        spl_gbs = splat_bytes_step * args.steps / (ms_spl * 1e-3) / 1e9 if ms_spl else 0.0
+
+        conv_traffic, splat_traffic = pmc_traffic("conv_"), pmc_traffic("region_splat_kernel")
+        l1_launches = 3 if os.environ.get("LSS_SPLAT_DIRECT") == "0" else 2   # (splat.hip: the direct form is the default)
+        # the dominant kernel by itself: algorithmic FLOPs of ONE launch / its own average duration
+        dom_flops = 2.0 * B * X * Y * 128 * (256 * 9 + 4)   # 3x3 256 -> 128 on the upsampled grid + the 1x1 head (4 classes)
+        dom_us = ms_dom * 1e3 / n_dom if n_dom else 0.0
+        dom_tf = dom_flops / (dom_us * 1e-6) / 1e12 if dom_us else 0.0
+        ring = os.environ.get("LSS_CONV_RING") != "0" and args.precision == "bf16"
+        dom_name = "conv_ring_kernel<1, true" if ring else "conv_lds_kernel<2, 128, 1, 3, 3, 1, 32, 1, true"
+        dom_traffic = pmc_traffic(dom_name)
+        dominant = {"kernel": ("conv_ring_kernel<MODE 1, HEAD> (loader / consumer ring kernel, csrc/conv_ring.hip)" if ring else
+                               "conv_lds_kernel<2,128,1,3,3,1,32,1,HEAD>") + " = BevEncode.up2: x2 bilinear upsample (fused gather) + 3x3 "
+                              "conv 256->128 + BN + ReLU + 1x1 head, one launch; own HIP-event bracket in a separate pass of the "
+                              "same K steps (outside the timed region)",
+                    "bound": "mfma", "flops_per_launch": dom_flops, "avg_us": dom_us, "launches": n_dom, "achieved": dom_tf,
+                    "peak": peak_tf, "unit": "TFLOP/s", "frac": dom_tf / peak_tf if peak_tf else 0.0,
+                    "traffic": dom_traffic[0], "traffic_unit": "HBM bytes per launch (PMC)", "traffic_source": dom_traffic[1]}
+        out.update({
+            "roofline": {"kernel": "conv_lds_kernel / conv_ks_kernel / conv_ring_kernel: the 16 BevEncode launches of a step (stride-2 convs carry their 1x1 downsample, "
+                                   "up2 its head; the ten 3x3 / stride-1 convs of layer1-3 run on the K-split one-pass kernel, the three big 3x3 layers on the ring kernel), one HIP-event "
+                                   "bracket around the group (per-launch brackets cost ~10 us of idle each)",
+                         "bound": "mfma", "achieved": conv_tf, "peak": peak_tf, "unit": "TFLOP/s",
+                         "frac": conv_tf / peak_tf, "traffic": conv_traffic[0], "traffic_unit": "HBM bytes per launch (PMC)",
+                         "traffic_source": conv_traffic[1], "launches": n_conv * 16,
+                         "avg_us": ms_conv * 1e3 / max(n_conv * 16, 1), "flops_per_step": conv_flops_step,
+                         "dominant_kernel": dominant},
+            "roofline_l1": {"kernel": ("lift-splat level = depthnet_rows_and_voxels (K2 || K3, writes the region entries itself) + "
+                                       "region_splat (direct form: 2 launches, one HIP-event bracket); `traffic` is region_splat_kernel's own"
+                                       if l1_launches == 2 else
+                                       "lift-splat level = depthnet_rows_and_voxels (K2 || K3) + region_fill + region_splat "
+                                       "(3 launches, one HIP-event bracket); `traffic` is region_splat_kernel's own"),
+                            "bound": "hbm", "achieved": spl_gbs, "peak": HBM_PEAK_GBS,
+                            "unit": "GB/s", "frac": spl_gbs / HBM_PEAK_GBS, "traffic": splat_traffic[0],
+                            "traffic_unit": "HBM bytes per launch (PMC)", "traffic_source": splat_traffic[1],
+                            "launches": n_spl * l1_launches,
+                            "avg_us": ms_spl * 1e3 / max(n_spl * l1_launches, 1), "level_us": ms_spl * 1e3 / max(n_spl, 1),
+                            "bytes_per_step": splat_bytes_step},
+            "levels": {"L2_hot_path_fps": fps,
+                       "cold_start_fps": frames / dt_cold,
+                       "cold_start_note": "the same K steps timed right after the first W warm-up steps, before the "
+                                          "config.spinup_ms spin-up (device still ramping its clock)",
+                       "L1_lift_splat_fps": frames / dt_l1, "L1_ms_per_step": dt_l1 / args.steps * 1e3,
+                       "L1_algorithmic_GBs": l1_bytes_step * args.steps * world / dt_l1 / 1e9,
+                       "L1_frac_of_hbm_peak": l1_bytes_step * args.steps / dt_l1 / 1e9 / HBM_PEAK_GBS},
+        })
+
     # ---- training step (fwd + bwd + Adam, RCCL all-reduce of one flat gradient bucket) ----
-    if not args.no_train and args.workload == "config2":
+    if args.full and not args.no_train and args.workload == "config2":
         # An extra, informational leg: a failure in it (every rank sees the same exception class) must not cost the
         # main metric's line, so it is reported instead of raised.
         # ... a HANG in it (a collective some rank never joins) is different: every rank arms a watchdog that prints
@@ -383,7 +413,7 @@ def main():
     # latency (the launch-bound BevEncode layers and the lift-splat level leave CUs idle that a
     # second, independent batch can use) - what a serving loop that double-buffers batches gets.
     dt_2s = 0.0
-    if args.two_streams:
+    if args.full and args.two_streams:
         with torch.no_grad():
             model_b = L.compile_model_lss(B, grid, aug, 4, precision=args.precision).to(dev).eval()
             model_b.load_state_dict(model.state_dict())
@@ -410,7 +440,7 @@ def main():
                                                        "(informational; `value` is the single-stream loop)")
 
     # ---- CPU baseline: the oracle (op-for-op torch port of the reference) on this host ----
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload in ("config2", "config1"):
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload in ("config2", "config1"):
         out["cpu_baseline"] = cpu_baseline(model, feats, calib, B)
 
     # ---- hang guards: every leg's counters in the line; any non-zero one makes the run fail (rc GUARD_RC) ----
@@ -432,6 +462,23 @@ def main():
     if rc:
         sys.stderr.write("bench.py: loader / consumer flag waits hit their bound: %s\n" % json.dumps(guards))
         raise SystemExit(rc)
+
+
+DUMP_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+
+
+def dump_outputs(dirname, arrays, limit):
+    """--dump-outputs: every tensor of `arrays` as DIR/<name>.npy in float32.  One larger than `limit` bytes is replaced
+    by a fixed sample of its flattened elements (seeded: the same indices on every run with the same shapes)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    limit //= max(len(arrays), 1)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > limit:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, limit // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
 
 
 WATCHDOG_RC = 3

@@ -88,6 +88,29 @@ def test_benched_step_b4_bf16_vs_oracle(report, bn):
     assert emax < 2 * BF16_TOL, emax
 
 
+def test_plain_bench_run_dumps_its_last_timed_step(tmp_path):
+    """A plain `bench.py` run (no --full legs) prints the headline line, and --dump-outputs writes the BEV output of
+    its last timed step: the bits the benched model gives on the same seeded inputs here."""
+    import json
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, bench.__file__, "--gpus", "1", "--steps", "3", "--warmup", "1", "--spinup-ms", "0",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0 and line["guards"]["ok"]
+    assert not {"roofline", "roofline_l1", "levels", "train", "cpu_baseline"} & set(line)
+    got = np.load(tmp_path / "bev.npy")
+    assert got.dtype == np.float32 and got.shape == (4, 4, 200, 200)
+    torch.manual_seed(0)
+    m = L.compile_model_lss(4, bench.GRID, bench.AUG, 4, precision="bf16").cuda().eval()
+    feats, calib = _bench_inputs(4)
+    with torch.no_grad():
+        m(feats.cuda(), *calib)
+        out = m(feats.cuda(), *calib).cpu().numpy()   # plan replay, as in the timed steps
+    assert np.array_equal(got, out), float(np.abs(got - out).max())
+
+
 def test_region_pipeline_b4_vs_reference_rows(golden):
     """The region pipeline (what the benched step runs) against the REFERENCE's own voxel_pooling rows of the
     batch-4 fixture - until now only the voxel-list K5 saw `g4_full_b4_train`."""

@@ -55,3 +55,27 @@ def test_fired_watchdog_exits_non_zero_and_names_the_leg():
     code1 = code.replace("0, 'train'", "1, 'train'")
     p1 = subprocess.run([sys.executable, "-c", code1], capture_output=True, text=True, timeout=120)
     assert p1.returncode == 3 and p1.stdout.strip() == ""
+
+
+def test_steps_below_one_is_an_error():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--dry-launch"],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 2 and "--steps" in r.stderr
+
+
+def test_dump_outputs_are_float32_and_a_seeded_sample_beyond_the_budget(tmp_path):
+    """--dump-outputs: DIR/<name>.npy in float32; an array over the byte budget becomes a fixed sample of its elements."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    small = torch.arange(12.0).reshape(3, 4).to(torch.bfloat16)
+    bench.dump_outputs(str(tmp_path / "a"), {"bev": small}, bench.DUMP_BYTES)
+    got = np.load(tmp_path / "a" / "bev.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.float().numpy())
+    big = torch.randn(1000, generator=torch.Generator().manual_seed(0))
+    bench.dump_outputs(str(tmp_path / "b"), {"bev": big}, 400)
+    bench.dump_outputs(str(tmp_path / "c"), {"bev": big}, 400)
+    s1, s2 = np.load(tmp_path / "b" / "bev.npy"), np.load(tmp_path / "c" / "bev.npy")
+    assert s1.dtype == np.float32 and s1.nbytes == 400 and np.array_equal(s1, s2)
+    assert np.isin(s1, big.numpy()).all() and len(np.unique(s1)) == 100

@@ -76,7 +76,7 @@ def main():
     sq, sqkt = find(os.path.join(src, "sq"), "*counter_collection.csv"), find(os.path.join(src, "sq"), "*kernel_trace.csv")
     if sq and sqkt:
         head = ("# rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS "
-                "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES -- python bench.py --steps 10 --warmup 3 "
+                "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES -- python bench.py --full --steps 10 --warmup 3 "
                 "--no-cpu-baseline --no-train\n# mean per dispatch (tools/pmc_sq_summary.py); MFMA_util = "
                 "SQ_VALU_MFMA_BUSY_CYCLES / (duration x 2.4 GHz x 1024 SIMDs)\n")
         w("conv_pmc_sq.txt", head + run_tool("pmc_sq_summary.py", sq, sqkt))

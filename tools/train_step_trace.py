@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""One replayed training step out of a rocprofv3 --kernel-trace CSV of `bench.py ... --train-steps N`: kernels per step,
+"""One replayed training step out of a rocprofv3 --kernel-trace CSV of `bench.py --full ... --train-steps N`: kernels per step,
 span, busy time, and the kernels grouped by name.   python tools/train_step_trace.py <kernel_trace.csv> [top]"""
 import collections
 import csv
