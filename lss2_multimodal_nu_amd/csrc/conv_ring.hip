@@ -22,14 +22,14 @@
 //   wave  8    weight loader: streams the weight slabs by LDS-DMA
 //   waves 9-11 patch loaders: plain DMA of the input patch, or source-window DMA + four-corner blend (fused upsample)
 // K loop: chunk = 32 input channels, step = (chunk, tap): 20 MFMAs per consumer against one 8-KiB weight slab.
-// LDS (140-154 KiB):
+// LDS (120-154 KiB):
 //   ring   NSL (7-8) slots x 8 KiB: the weight slab of one step in FRAGMENT ORDER (piece (cg, t, lane) at
 //          ((cg*4+t)*64+lane)*16: a consumer reads its A fragment lane-linearly = conflict-free); the packed weights
 //          in global memory have exactly this image, so a slab is 8 fully coalesced 1-KiB DMA pieces
 //   patch  2 buffers x 4 strips x (6 rows x 24 positions x 64 B): position-major, the four 16-B channel pieces of a
 //          position XOR-swizzled by (row & 1) << 1 - conflict-free ds_read_b128 for every tap shift (checked by
-//          enumeration over the hardware's b128 lane groups)
-//   src    (fused upsample) the low-res source window of a chunk, 4 strips x 5 x 14 positions
+//          enumeration over the hardware's b128 lane groups); shared 2 x 2 tile (T22): 2 buffers x 10 x 42 positions
+//   src    (fused upsample) the low-res source window of a chunk, 4 strips x 5 x 14 positions (T22: one 7 x 23)
 //   headx  (fused head) the partial class sums of the second channel half
 //   flags  FULL_W[slot] = fill count (weight loader), FREE_W[slot] = releases (consumers, LDS atomic add),
 //          FULL_P / FREE_P the same for the two patch buffers, FULL_S / FREE_S for the source window
@@ -50,6 +50,17 @@ constexpr int RK_STRIP_PATCH = RK_PH * RK_PW * RK_POSB;   // 9216 B = 9 DMA piec
 constexpr int RK_SLAB = 128 * RK_KC * 2;      // 8192 B = 8 DMA pieces
 constexpr int RK_SRC_H = 5, RK_SRC_W = 14;    // low-res source window of a strip patch (scale factors >= 2)
 constexpr int RK_SRC_STRIP = RK_SRC_H * RK_SRC_W * RK_POSB;  // 4480 B
+// Shared-tile layout (T22, fused upsample only, output a multiple of 8 x 40): the four strips of a workgroup form a
+// 2 x 2 tile of 8 x 40 pixels that shares ONE 10 x 42 patch (420 blended positions instead of 4 x 132) and one low-res
+// source window (7 x 23 instead of 4 x 5 x 14).  A row pitch of 42 positions keeps every consumer read conflict-free
+// with the same (row & 1) << 1 swizzle (enumerated over the b128 lane groups for all nine taps and the four strip
+// offsets); the strip offsets (4 rows, 20 columns) are multiples of 256 B and keep the row parity.
+constexpr int RK_TH = 2 * RK_SH, RK_TW = 2 * RK_SW;       // tile: 8 x 40 output pixels
+constexpr int RK_TPW = RK_TW + 2, RK_TPH = RK_TH + 2;     // patch of a tile: 10 x 42 positions, row pitch 42
+constexpr int RK_TPIECE = (RK_TPH * RK_TPW * 4 + 63) / 64;  // 27 1-KiB pieces (the last one a quarter used)
+constexpr int RK_TSRC_H = 7, RK_TSRC_W = 23;               // low-res source window of a tile patch
+constexpr int RK_TSRC = RK_TSRC_H * RK_TSRC_W * RK_POSB;    // 10304 B
+constexpr int RK_TSRC_PIECE = (RK_TSRC_H * RK_TSRC_W * 4 + 63) / 64;  // 11
 
 struct RingArgs {
   const unsigned short* x;    // (B, H, W, Cx) bf16 NHWC; the low-res source when up > 1
@@ -73,12 +84,13 @@ struct RingArgs {
 __device__ __attribute__((aligned(128))) unsigned char lss_ring_zero_page[128];  // source of out-of-image patch pieces
 __device__ int lss_ring_timeouts;  // flag waits that hit their bound (must stay 0; read by lss_conv2d_ring_timeouts)
 
-template <int MODE, bool HEAD, int NSL>
+template <int MODE, bool HEAD, int NSL, bool T22>
 struct RingLds {
   static constexpr int RING = 0;
   static constexpr int PATCH = NSL * RK_SLAB;
-  static constexpr int SRC = PATCH + 2 * 4 * RK_STRIP_PATCH;           // two buffers x four strips
-  static constexpr int HEADX = SRC + (MODE == 1 ? 4 * RK_SRC_STRIP : 0);
+  static constexpr int PBUF = T22 ? RK_TPIECE * 1024 : 4 * RK_STRIP_PATCH;  // one patch buffer (all strips)
+  static constexpr int SRC = PATCH + 2 * PBUF;                        // two buffers
+  static constexpr int HEADX = SRC + (MODE == 1 ? (T22 ? RK_TSRC : 4 * RK_SRC_STRIP) : 0);
   static constexpr int FLAGS = HEADX + (HEAD ? 4 * 80 * 4 * 4 : 0);
   static constexpr int TOTAL = FLAGS + 256;
 };
@@ -144,7 +156,6 @@ constexpr int RK_NS = 4;              // strips per workgroup
 constexpr int RK_NCONS = 2 * RK_NS;   // consumer waves: (strip, 64-channel half)
 constexpr int RK_NPATCH = 3;          // patch-loader waves
 constexpr int RK_NWAVES = RK_NCONS + 1 + RK_NPATCH;  // 12 = three per SIMD: ONE workgroup per CU
-constexpr int RK_NPIECE = RK_NS * 9;  // 1-KiB pieces of one patch buffer (all strips)
 
 struct RingTile {
   int nb;            // 128-channel block
@@ -159,9 +170,13 @@ struct RingTile {
 // showed half of the workgroups STARTING when the other half had finished.  Six waves land on the four SIMDs as
 // 2, 2, 1, 1 and a second workgroup only fits next to that when its own 2, 2, 1, 1 happens to fall the other way
 // round.)  A weight slab now feeds four strips instead of two: half the weight bytes streamed into LDS per MFMA.
-template <int MODE, bool HEAD, int NSL>
+//
+// T22 (MODE 1 only): the shared 2 x 2 tile layout above; strip s is tile row s >> 1, tile column s & 1.
+template <int MODE, bool HEAD, int NSL, bool T22>
 __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a) {
-  using L = RingLds<MODE, HEAD, NSL>;
+  static_assert(!T22 || MODE == 1, "shared tile: fused upsample only");
+  using L = RingLds<MODE, HEAD, NSL, T22>;
+  constexpr int PW = T22 ? RK_TPW : RK_PW;  // patch row pitch (positions)
   constexpr int LA = NSL - 2;  // weight slabs in flight at most: one slot is being consumed, one is published and waiting
   static_assert(NSL >= 3 && NSL <= 8, "ring depth");
   static_assert(L::TOTAL <= 160 * 1024, "LDS of one CU");
@@ -196,17 +211,29 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
     const int t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
     T.nb = t % a.nblk;
     const int quad = t / a.nblk;
+    if (T22) {  // quad = tile (the launcher takes this layout only when the tiles cover the output exactly)
+      const int tx = a.SX >> 1, per = tx * (a.SY >> 1);
+      const int b = quad / per, rem = quad - b * per, ty = rem / tx;
 #pragma unroll
-    for (int s = 0; s < RK_NS; ++s) {
-      int sid = RK_NS * quad + s;
-      T.ok[s] = sid < a.nstrips;
-      sid = min(sid, a.nstrips - 1);
-      const int per = a.SX * a.SY;
-      T.b[s] = sid / per;
-      const int rem = sid - T.b[s] * per;
-      const int sy = rem / a.SX;
-      T.oy0[s] = sy * RK_SH;
-      T.ox0[s] = (rem - sy * a.SX) * RK_SW;
+      for (int s = 0; s < RK_NS; ++s) {
+        T.ok[s] = true;
+        T.b[s] = b;
+        T.oy0[s] = ty * RK_TH + (s >> 1) * RK_SH;
+        T.ox0[s] = (rem - ty * tx) * RK_TW + (s & 1) * RK_SW;
+      }
+    } else {
+#pragma unroll
+      for (int s = 0; s < RK_NS; ++s) {
+        int sid = RK_NS * quad + s;
+        T.ok[s] = sid < a.nstrips;
+        sid = min(sid, a.nstrips - 1);
+        const int per = a.SX * a.SY;
+        T.b[s] = sid / per;
+        const int rem = sid - T.b[s] * per;
+        const int sy = rem / a.SX;
+        T.oy0[s] = sy * RK_SH;
+        T.ox0[s] = (rem - sy * a.SX) * RK_SW;
+      }
     }
   }
   const int nsteps = a.nch * 9;
@@ -269,55 +296,72 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
 
   if (wave > RK_NCONS) {
     // =============================== patch loaders ===============================
-    // Patch loader p takes the 1-KiB pieces it = p, p + 3, ... of a patch buffer (12 of 36).  Piece it = (strip it / 9,
-    // block it % 9): lane -> patch position 16 * (it % 9) + (lane >> 2), 16-B slot lane & 3, which holds channel piece
-    // slot ^ ((row & 1) << 1).  FULL_P / FREE_S etc. are counters: every patch loader adds its share.
+    // Patch loader p takes the 1-KiB pieces it = p, p + 3, ... of a patch buffer (12 of 36; T22: 9 of 27).  Piece it =
+    // (strip it / 9, block it % 9): lane -> patch position 16 * (it % 9) + (lane >> 2), 16-B slot lane & 3, which holds
+    // channel piece slot ^ ((row & 1) << 1); T22: position 16 * it + (lane >> 2) of the tile's one patch.  FULL_P /
+    // FREE_S etc. are counters: every patch loader adds its share.
     __builtin_amdgcn_s_setprio(RK_PRIO_P);
     const int pw = wave - RK_NCONS - 1;
-    constexpr int NIT = RK_NPIECE / RK_NPATCH;  // 12
+    constexpr int NIT = (T22 ? RK_TPIECE : RK_NS * 9) / RK_NPATCH;  // 12; T22: 9
+    static_assert(NIT * RK_NPATCH == (T22 ? RK_TPIECE : RK_NS * 9), "pieces split evenly over the patch loaders");
     const int nskip = MODE == 1 ? a.C2 / RK_KC : a.nch;  // chunks copied straight from a full-resolution tensor
     const unsigned short* xfull = MODE == 1 ? a.x2 : a.x;
     const int cfull = MODE == 1 ? a.C2 : a.Cx;
     int poff[NIT];  // element offset of the piece's pixel in the full-resolution tensor (+ channel piece), or -1
     int g_off[MODE == 1 ? NIT : 1];
-    unsigned int g_w[MODE == 1 ? NIT : 1];
-    constexpr int NSRC = MODE == 1 ? (RK_NS * 5 + RK_NPATCH - 1) / RK_NPATCH : 1;  // source-window pieces of this wave (7)
+    // blend weights of the piece's position as 16-bit fixed-point fractions (wy << 16 | wx).  T22 decodes them once
+    // here into fp32 lx / ly (same expressions, so every operand bit of rk_blend is unchanged) instead of at every
+    // chunk; the per-strip layout keeps the packed word (12 pieces: 12 more registers there spill)
+    constexpr int NWD = MODE == 1 && T22 ? NIT : 1, NWP = MODE == 1 && !T22 ? NIT : 1;
+    float g_lx[NWD], g_ly[NWD];
+    unsigned int g_wp[NWP];
+    constexpr int SRCW = T22 ? RK_TSRC_W : RK_SRC_W;  // source window row length (positions)
+    constexpr int NSRCP = T22 ? RK_TSRC_PIECE : RK_NS * 5;  // 1-KiB pieces of the source window(s)
+    constexpr int NSRC = MODE == 1 ? (NSRCP + RK_NPATCH - 1) / RK_NPATCH : 1;  // source-window pieces of this wave (7; T22: 4)
     int src_o[NSRC];
 #pragma unroll
     for (int k = 0; k < NIT; ++k) {
       const int it = pw + k * RK_NPATCH;
-      const int s = it / 9, pos = (it % 9) * 16 + (lane >> 2);
-      const int prow = pos / RK_PW, pcol = pos - prow * RK_PW;
+      const int s = T22 ? 0 : it / 9, pos = T22 ? it * 16 + (lane >> 2) : (it % 9) * 16 + (lane >> 2);
+      const int prow = pos / PW, pcol = pos - prow * PW;
       const int piece = (lane & 3) ^ ((prow & 1) << 1);
       const int sb = s == 0 ? T.b[0] : s == 1 ? T.b[1] : s == 2 ? T.b[2] : T.b[3];
       const int soy = s == 0 ? T.oy0[0] : s == 1 ? T.oy0[1] : s == 2 ? T.oy0[2] : T.oy0[3];
       const int sox = s == 0 ? T.ox0[0] : s == 1 ? T.ox0[1] : s == 2 ? T.ox0[2] : T.ox0[3];
       const bool sok = s == 0 ? T.ok[0] : s == 1 ? T.ok[1] : s == 2 ? T.ok[2] : T.ok[3];
       const int iy = soy - 1 + prow, ix = sox - 1 + pcol;
-      const bool in = sok && pcol < RK_SW + 2 && iy >= 0 && iy < a.Hin && ix >= 0 && ix < a.Win;
+      const bool used = T22 ? pos < RK_TPH * RK_TPW : pcol < RK_SW + 2;
+      const bool in = sok && used && iy >= 0 && iy < a.Hin && ix >= 0 && ix < a.Win;
       poff[k] = (in && cfull > 0) ? ((sb * a.Hin + iy) * a.Win + ix) * cfull + piece * 8 : -1;
       if (MODE == 1) {
         g_off[k] = 0;
-        g_w[k] = 0;
+        unsigned int g_w = 0;
         if (in) {
           const int wy0 = (int)(a.ry * (float)max(soy - 1, 0)), wx0 = (int)(a.rx * (float)max(sox - 1, 0));
           const float sy = a.ry * (float)iy, sx = a.rx * (float)ix;
           const int y0 = (int)sy, x0 = (int)sx;
           const unsigned int wy = (unsigned int)((sy - (float)y0) * 65536.f + 0.5f);
           const unsigned int wx = (unsigned int)((sx - (float)x0) * 65536.f + 0.5f);
-          g_w[k] = min(wx, 65535u) | (min(wy, 65535u) << 16);
+          g_w = min(wx, 65535u) | (min(wy, 65535u) << 16);
           const int fl = (x0 < a.W - 1 ? 1 : 0) | (y0 < a.H - 1 ? 2 : 0) | 4;
-          g_off[k] = ((((y0 - wy0) * RK_SRC_W + (x0 - wx0)) * 4 + piece) * 16) | fl;
+          g_off[k] = ((((y0 - wy0) * SRCW + (x0 - wx0)) * 4 + piece) * 16) | fl;
+        }
+        if constexpr (T22) {
+          g_lx[k] = (float)(g_w & 0xffff) * (1.f / 65536.f);
+          g_ly[k] = (float)(g_w >> 16) * (1.f / 65536.f);
+        } else {
+          g_wp[k] = g_w;
         }
       }
     }
     if (MODE == 1) {
 #pragma unroll
       for (int k = 0; k < NSRC; ++k) {
-        const int it = pw + k * RK_NPATCH;  // source piece it = (strip it / 5, block it % 5); it >= 20: none
-        const int s = min(it / 5, RK_NS - 1), q = (it % 5) * 64 + lane;
-        const int pos = min(q >> 2, RK_SRC_H * RK_SRC_W - 1), part = q & 3;
-        const int sr = pos / RK_SRC_W, sc = pos - sr * RK_SRC_W;
+        // source piece it = (strip it / 5, block it % 5); it >= 20: none.  T22: piece it of the tile's window
+        const int it = pw + k * RK_NPATCH;
+        const int s = T22 ? 0 : min(it / 5, RK_NS - 1), q = (T22 ? it : it % 5) * 64 + lane;
+        const int pos = min(q >> 2, (T22 ? RK_TSRC_H : RK_SRC_H) * SRCW - 1), part = q & 3;
+        const int sr = pos / SRCW, sc = pos - sr * SRCW;
         const int sb = s == 0 ? T.b[0] : s == 1 ? T.b[1] : s == 2 ? T.b[2] : T.b[3];
         const int soy = s == 0 ? T.oy0[0] : s == 1 ? T.oy0[1] : s == 2 ? T.oy0[2] : T.oy0[3];
         const int sox = s == 0 ? T.ox0[0] : s == 1 ? T.ox0[1] : s == 2 ? T.ox0[2] : T.ox0[3];
@@ -327,7 +371,7 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
     }
     // this wave's pieces of full-resolution chunk c -> patch buffer `buf` by DMA
     auto issue_full = [&](int c, int buf) {
-      unsigned char* dst = smem + L::PATCH + buf * (RK_NS * RK_STRIP_PATCH);
+      unsigned char* dst = smem + L::PATCH + buf * L::PBUF;
 #pragma unroll
       for (int k = 0; k < NIT; ++k) {
         const void* src = poff[k] >= 0 ? (const void*)(xfull + poff[k] + c * RK_KC) : (const void*)lss_ring_zero_page;
@@ -364,8 +408,12 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
 #pragma unroll
         for (int k = 0; k < NSRC; ++k) {
           const int it = pw + k * RK_NPATCH;
-          if (it < RK_NS * 5 && (it % 5) * 64 + lane < RK_SRC_H * RK_SRC_W * 4)
+          if (T22) {
+            if (it < RK_TSRC_PIECE && it * 64 + lane < RK_TSRC_H * RK_TSRC_W * 4)
+              rk_glds16(a.x + src_o[k] + cx, smem + L::SRC + it * 1024);
+          } else if (it < RK_NS * 5 && (it % 5) * 64 + lane < RK_SRC_H * RK_SRC_W * 4) {
             rk_glds16(a.x + src_o[k] + cx, smem + L::SRC + (it / 5) * RK_SRC_STRIP + (it % 5) * 1024);
+          }
         }
       };
       // start the DMA chunk c needs.  Full-resolution chunk: straight into patch buffer c & 1 once the consumers have
@@ -387,15 +435,15 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
           rk_add1(flags + F_FULL_S, lane);
           st1 += rk_wait_ge(flags + F_FULL_S, RK_NPATCH * (c - nskip + 1));
           st0 += rk_wait_ge<RK_PSLEEP>(flags + F_FREE_P + (c & 1), RK_NCONS * (c >> 1));
-          unsigned char* dst = smem + L::PATCH + (c & 1) * (RK_NS * RK_STRIP_PATCH);
+          unsigned char* dst = smem + L::PATCH + (c & 1) * L::PBUF;
           // fully unrolled (static register indices for g_off / g_w), no branches (a piece outside the image blends
           // whatever sits at offset 0 of the window and is replaced by zeros afterwards), and the four corner reads of
           // piece k + 1 are requested before piece k is blended
           uint4 qa[4], qb[4];
           auto corners = [&](int k, uint4* q) {
             const int it = pw + k * RK_NPATCH;
-            const unsigned char* p00 = smem + L::SRC + (it / 9) * RK_SRC_STRIP + (g_off[k] & 0xfff0);
-            const int dx = (g_off[k] & 1) ? 4 * 16 : 0, dy = (g_off[k] & 2) ? RK_SRC_W * 4 * 16 : 0;
+            const unsigned char* p00 = smem + L::SRC + (T22 ? 0 : (it / 9) * RK_SRC_STRIP) + (g_off[k] & 0xfff0);
+            const int dx = (g_off[k] & 1) ? 4 * 16 : 0, dy = (g_off[k] & 2) ? SRCW * 4 * 16 : 0;
             q[0] = *reinterpret_cast<const uint4*>(p00);
 #if defined(RK_DIAG_ONEREAD)  // timing-only: one corner read, the full arithmetic
             q[1] = q[0]; q[2] = q[0]; q[3] = q[0];
@@ -413,8 +461,11 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
             v.x = q[0].x ^ q[1].x ^ q[2].x ^ q[3].x; v.y = q[0].y ^ q[1].y ^ q[2].y ^ q[3].y;
             v.z = q[0].z ^ q[1].z ^ q[2].z ^ q[3].z; v.w = q[0].w ^ q[1].w ^ q[2].w ^ q[3].w;
 #else
-            v = rk_blend(q[0], q[1], q[2], q[3], (float)(g_w[k] & 0xffff) * (1.f / 65536.f),
-                         (float)(g_w[k] >> 16) * (1.f / 65536.f));
+            if constexpr (T22)
+              v = rk_blend(q[0], q[1], q[2], q[3], g_lx[k], g_ly[k]);
+            else
+              v = rk_blend(q[0], q[1], q[2], q[3], (float)(g_wp[k] & 0xffff) * (1.f / 65536.f),
+                           (float)(g_wp[k] >> 16) * (1.f / 65536.f));
 #endif
             const bool in = (g_off[k] & 4) != 0;
             v.x = in ? v.x : 0u; v.y = in ? v.y : 0u; v.z = in ? v.z : 0u; v.w = in ? v.w : 0u;
@@ -424,10 +475,12 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
           corners(0, qa);
 #pragma unroll
           for (int k = 0; k < NIT; k += 2) {
-            corners(k + 1, qb);
+            if (k + 1 < NIT) corners(k + 1, qb);
             finish(k, qa);
-            if (k + 2 < NIT) corners(k + 2, qa);
-            finish(k + 1, qb);
+            if (k + 1 < NIT) {
+              if (k + 2 < NIT) corners(k + 2, qa);
+              finish(k + 1, qb);
+            }
           }
           rk_wait_lgkm0();  // the blended pieces are in LDS, and this wave's reads of the source window are done
           rk_add1(flags + F_FREE_S, lane);
@@ -479,16 +532,18 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
   // keeps the MFMAs behind them (cdna_hip_programming.md section 5.4 rule 18).
   bf16x8 fw[4], fp[5];
 #define RK_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
-  // The two lane-dependent offsets - weight fragment (cg * 4096 + lane * 16 < 8192) and pixel fragment (< 8192) - live
+  // The two lane-dependent offsets - weight fragment (cg * 4096 + lane * 16 < 8192) and pixel fragment (< 8320) - live
   // packed in ONE register; an address is (field | or + wave-uniform part): 1-2 VALU where the first builds spent ~25
   // per step recomputing them from the lane id.  The few VALU / SALU instructions of a step are placed BETWEEN the
   // MFMA pairs of phase A (they issue in the shadow of the matrix pipe) instead of in one block between the phases,
   // where neither this wave nor - when the two consumer waves of a SIMD run in step - its partner issues MFMAs.
   const unsigned int lanepk =
       (unsigned int)(cg * 4096 + lane * 16) |
-      ((unsigned int)((((n >> 2) * RK_PW + (n & 3)) * RK_POSB + (kq << 4)) ^ (((n >> 2) & 1) << 5)) << 16);
+      ((unsigned int)((((n >> 2) * PW + (n & 3)) * RK_POSB + (kq << 4)) ^ (((n >> 2) & 1) << 5)) << 16);
   const unsigned int flag_base = (unsigned int)(__UINTPTR_TYPE__)flags;
-  const int pconst = L::PATCH + sidx * RK_STRIP_PATCH;
+  // the strip's patch; T22: the strip's corner inside the tile's patch (4 rows / 20 columns on: multiples of 256 B,
+  // row parity kept, so the swizzle and the bank pattern of every read are those of a strip's own patch)
+  const int pconst = L::PATCH + (T22 ? ((sidx >> 1) * RK_SH * PW + (sidx & 1) * RK_SW) * RK_POSB : sidx * RK_STRIP_PATCH);
   // FREE counters: lane 0 adds 1 (exec narrowed inside the asm: no branch around it)
   auto add1 = [&](int word) {
     unsigned long long save;
@@ -518,7 +573,7 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
   auto step = [&](auto TAPc, bool last) {
     constexpr int TAP = decltype(TAPc)::value;
     constexpr int NT = (TAP + 1) % 9;
-    constexpr int POFF = (NT / 3) * (RK_PW * RK_POSB) + (NT % 3) * RK_POSB;  // tap offset of the next step's pixel fragments
+    constexpr int POFF = (NT / 3) * (PW * RK_POSB) + (NT % 3) * RK_POSB;  // tap offset of the next step's pixel fragments
     {
       const int wa = (int)(lanepk & 0xffffu) + (L::RING + slot * RK_SLAB);
       RK_DSR(fw[2], wa, 2048);
@@ -543,7 +598,7 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
     acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[0], fp[1], acc[1][0], 0, 0, 0);
     acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[1], fp[1], acc[1][1], 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
-    const int pan = (int)((lanepk >> 16) ^ (NT / 3 == 1 ? 32u : 0u)) + (pconst + nbuf * (RK_NS * RK_STRIP_PATCH));
+    const int pan = (int)((lanepk >> 16) ^ (NT / 3 == 1 ? 32u : 0u)) + (pconst + nbuf * L::PBUF);
     const int n2 = nslot + 1 == NSL ? 0 : nslot + 1;
     const unsigned int fa = flag_base + 4 * (F_FULL_W + n2);
     __builtin_amdgcn_sched_barrier(0);
@@ -837,13 +892,19 @@ int lss_conv_ring_launch(const void* x, const void* x2, const void* w_ring, cons
     a.stats = e ? reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 16)) : nullptr;
   }
   const bool fused = up > 1 || C2 > 0;
+  // the shared 2 x 2 tile where the tiles cover the output exactly and its 10 x 42 patch interpolates from a 7 x 23
+  // source window (up2 at 200^2); every other fused shape keeps one patch per strip
+  const bool t22 = fused && a.Hin % RK_TH == 0 && a.Win % RK_TW == 0 &&
+                   (int)(a.ry * (RK_TPH - 1) + 0.999f) + 2 <= RK_TSRC_H && (int)(a.rx * (RK_TPW - 1) + 0.999f) + 2 <= RK_TSRC_W;
   const dim3 g((a.nstrips + RK_NS - 1) / RK_NS * a.nblk), blk(RK_NWAVES * 64);
   if (head_n > 0) {
-    if (fused) hipLaunchKernelGGL((conv_ring_kernel<1, true, 7>), g, blk, 0, st, a);
-    else hipLaunchKernelGGL((conv_ring_kernel<0, true, 8>), g, blk, 0, st, a);
+    if (t22) hipLaunchKernelGGL((conv_ring_kernel<1, true, 7, true>), g, blk, 0, st, a);
+    else if (fused) hipLaunchKernelGGL((conv_ring_kernel<1, true, 7, false>), g, blk, 0, st, a);
+    else hipLaunchKernelGGL((conv_ring_kernel<0, true, 8, false>), g, blk, 0, st, a);
   } else {
-    if (fused) hipLaunchKernelGGL((conv_ring_kernel<1, false, 7>), g, blk, 0, st, a);
-    else hipLaunchKernelGGL((conv_ring_kernel<0, false, 8>), g, blk, 0, st, a);
+    if (t22) hipLaunchKernelGGL((conv_ring_kernel<1, false, 7, true>), g, blk, 0, st, a);
+    else if (fused) hipLaunchKernelGGL((conv_ring_kernel<1, false, 7, false>), g, blk, 0, st, a);
+    else hipLaunchKernelGGL((conv_ring_kernel<0, false, 8, false>), g, blk, 0, st, a);
   }
   return lss_launch_status();
 }
