@@ -249,6 +249,39 @@ int lss_deform_attn_fwd(const void* value, int value_layout, const float* offset
                         const float* token_bias, const float* ref_x, const float* ref_y, int B, int H,
                         int W, int n_heads, int n_points, int C, int dt, void* out, void* stream);
 
+/* Deformable attention core with PER-TOKEN reference points (the training path's node).
+ *  replaces: src/transformer_modules.py:117-156, as lss_deform_attn_fwd, for any reference_points (:113)
+ *   value          value_proj(value) fp32 (B, H*W, C) (NHWC)
+ *   offsets_logits (B*H*W, 192) fp32 as above (no token_bias)
+ *   ref_pts        (B, H*W, 2) fp32 (x, y) in [0, 1], 8-B aligned; sample b starts at ref_pts + b * ref_bstride
+ *                  floats (ref_bstride even and >= 0; 0 = one set shared by every sample, torch's expand())
+ *   out            (B, H*W, C) fp32
+ * On the regular grid (ref_pts[t] = (ref_x[t % W], ref_y[t / W])) the result has the bits of lss_deform_attn_fwd. */
+int lss_deform_attn_pts_fwd(const float* value, const float* offsets_logits, const float* ref_pts,
+                            long long ref_bstride, int B, int H, int W, int n_heads, int n_points, int C,
+                            float* out, void* stream);
+
+/* Backward of lss_deform_attn_pts_fwd.  replaces: the autograd backward of src/transformer_modules.py:117-156
+ *  (grid_sampler_2d_backward, the softmax / clamp / mul / sum backwards)
+ *   value, offsets_logits, ref_pts, ref_bstride  as in the forward
+ *   d_out            (B, H*W, C) fp32: gradient of the forward's out
+ *   workspace        >= lss_deform_attn_bwd_workspace_bytes(B, H, W) bytes, 16-B aligned; contents need not be zero
+ *   d_value          (B, H*W, C) fp32, every element written
+ *   d_offsets_logits (B*H*W, 192) fp32, every element written
+ * No gradient flows to ref_pts.  d_value is summed in int64 fixed point (scale per sample from its largest finite
+ * |d_out|): the result is bit-reproducible and independent of the rest of the batch, with no float atomics.  A
+ * non-finite d_out element makes the d_value elements it reaches NaN, and its (token, head) row of d_offsets_logits
+ * non-finite; every other element keeps its bits.  Argument checks: LSS_E_NULL, LSS_E_SHAPE (sizes, n_heads or
+ * n_points != 8, C != 256, negative ref_bstride), LSS_E_ALIGN (16 B; 8 B for ref_pts, even ref_bstride),
+ * LSS_E_WORKSPACE. */
+int lss_deform_attn_bwd(const float* value, const float* offsets_logits, const float* ref_pts,
+                        long long ref_bstride, const float* d_out, int B, int H, int W, int n_heads,
+                        int n_points, int C, void* workspace, size_t workspace_bytes, float* d_value,
+                        float* d_offsets_logits, void* stream);
+/* H*W*(256*8 + 8*4) + 4*B: one sample's int64 sums and non-finite flag words, then B per-sample maxima
+ * (samples are reduced one after another); 0 if a size is <= 0 */
+size_t lss_deform_attn_bwd_workspace_bytes(int B, int H, int W);
+
 /* nn.LayerNorm(C) over rows.  replaces: src/transformer_modules.py:204,208 (norm1, norm2)
  *   x (rows, C) in x_dt; y (rows, C) in y_dt; gamma, beta (C) fp32 */
 int lss_layernorm_fwd(const void* x, int x_dt, const float* gamma, const float* beta,

@@ -32,6 +32,9 @@ SIGNATURES = {
     "lss_depth_fuse_softmax_fwd": (_i, [_vp] * 5 + [_i] * 6 + [_vp, _vp]),
     "lss_add_pos_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "lss_deform_attn_fwd": (_i, [_vp, _i] + [_vp] * 4 + [_i] * 7 + [_vp, _vp]),
+    "lss_deform_attn_pts_fwd": (_i, [_vp] * 3 + [ctypes.c_longlong] + [_i] * 6 + [_vp, _vp]),
+    "lss_deform_attn_bwd": (_i, [_vp] * 3 + [ctypes.c_longlong, _vp] + [_i] * 6 + [_vp, _sz, _vp, _vp, _vp]),
+    "lss_deform_attn_bwd_workspace_bytes": (_sz, [_i] * 3),
     "lss_layernorm_fwd": (_i, [_vp, _i, _vp, _vp, ctypes.c_longlong, _i, ctypes.c_float, _vp, _i, _vp]),
     "lss_depthnet_voxels_fwd": (_i, [_vp] * 10 + [_i] * 10 + [_vp] * 5),
     "lss_linear_res_ln_fwd": (_i, [_vp] * 4 + [ctypes.c_longlong, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),

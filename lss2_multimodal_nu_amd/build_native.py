@@ -27,6 +27,7 @@ SOURCES = {
     "conv_ks.hip": [],
     "layout.hip": [],
     "bev_transformer.hip": [],
+    "deform_grad.hip": [],
     "linear_mfma.hip": [],
     "ffn_fused.hip": [],
     "conv_grad.hip": [],

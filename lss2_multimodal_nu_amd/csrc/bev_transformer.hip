@@ -127,11 +127,13 @@ __device__ __forceinline__ void store8(float* p, const f32x2 (&a)[4]) {
   *reinterpret_cast<f32x4*>(p + 4) = (f32x4){a[2][0], a[2][1], a[3][0], a[3][1]};
 }
 
-template <typename T>
+// PTS: per-token reference points - ref_x is then ref_pts (B, H*W, 2) with sample stride ref_bstr floats (0 = one
+// set shared by all samples) and ref_y is unused; the arithmetic after the two loads is the same.
+template <typename T, bool PTS = false>
 __global__ __launch_bounds__(256) void deform_attn_kernel(
     const T* __restrict__ value, const float* __restrict__ ol, const float* __restrict__ tok_bias,
     const float* __restrict__ ref_x, const float* __restrict__ ref_y, int B, int H, int W,
-    long long pstr, long long hstr, long long bstr, T* __restrict__ out) {
+    long long pstr, long long hstr, long long bstr, T* __restrict__ out, long long ref_bstr = 0) {
   const int lane = threadIdx.x & 63, tok = lane >> 5, head = (lane >> 2) & 7, sub = lane & 3;
   const long long rows = (long long)B * H * W;
   const long long want = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 2 + tok;
@@ -159,7 +161,15 @@ __global__ __launch_bounds__(256) void deform_attn_kernel(
   float sum = e0 + e1;
   sum += __shfl_xor(sum, 1, 64);
   sum += __shfl_xor(sum, 2, 64);
-  const float rx = ref_x[t % W], ry = ref_y[t / W];
+  float rx, ry;
+  if constexpr (PTS) {
+    const float2 rp = *reinterpret_cast<const float2*>(ref_x + (size_t)b * ref_bstr + 2 * (size_t)t);
+    rx = rp.x;
+    ry = rp.y;
+  } else {
+    rx = ref_x[t % W];
+    ry = ref_y[t / W];
+  }
   const TapSet ta = make_taps(off[0], off[1], e0 / sum, rx, ry, H, W);
   const TapSet tb = make_taps(off[2], off[3], e1 / sum, rx, ry, H, W);
 
@@ -271,6 +281,24 @@ extern "C" int lss_deform_attn_fwd(const void* value, int value_layout, const fl
                        B, H, W, pstr, hstr, bstr, static_cast<unsigned short*>(out));
   else
     return LSS_E_LAYOUT;
+  return lss_launch_status();
+}
+
+extern "C" int lss_deform_attn_pts_fwd(const float* value, const float* offsets_logits, const float* ref_pts,
+                                       long long ref_bstride, int B, int H, int W, int n_heads, int n_points, int C,
+                                       float* out, void* stream) {
+  LSS_CHECK_PTR(value); LSS_CHECK_PTR(offsets_logits); LSS_CHECK_PTR(ref_pts); LSS_CHECK_PTR(out);
+  LSS_CHECK_POS(B); LSS_CHECK_POS(H); LSS_CHECK_POS(W);
+  if (n_heads != 8 || n_points != 8 || C != TC) return LSS_E_SHAPE;
+  if (ref_bstride < 0) return LSS_E_SHAPE;
+  if (!aligned16(value) || !aligned16(offsets_logits) || !aligned16(out)) return LSS_E_ALIGN;
+  if ((reinterpret_cast<uintptr_t>(ref_pts) & 7) != 0 || (ref_bstride & 1) != 0) return LSS_E_ALIGN;
+  const long long rows = (long long)B * H * W;
+  if (rows >= (1LL << 31)) return LSS_E_SHAPE;
+  const long long HW = (long long)H * W;
+  hipLaunchKernelGGL((deform_attn_kernel<float, true>), dim3(lss_cdiv(rows, 8)), dim3(256), 0, lss_stream(stream),
+                     value, offsets_logits, nullptr, ref_pts, nullptr, B, H, W, (long long)TC, 32LL, HW * TC, out,
+                     ref_bstride);
   return lss_launch_status();
 }
 

@@ -618,6 +618,52 @@ def deform_attn(value, offsets_logits, ref_x, ref_y, n_heads=8, n_points=8, toke
     return out
 
 
+def _ref_pts_arg(ref_pts, B, T):
+    """(B, T, 2) fp32 GPU reference points -> (tensor whose storage is read, sample stride in floats).  A batch
+    stride of 0 (torch's expand()) is passed through as is; other layouts are made contiguous."""
+    if ref_pts.dtype != torch.float32 or not ref_pts.is_cuda or ref_pts.dim() != 3 \
+            or tuple(ref_pts.shape[1:]) != (T, 2) or ref_pts.shape[0] not in (1, B):
+        raise ValueError("ref_pts must be fp32 GPU (B, %d, 2), got %s %s %s"
+                         % (T, ref_pts.dtype, ref_pts.device, tuple(ref_pts.shape)))
+    if ref_pts.stride(2) != 1 or ref_pts.stride(1) != 2 or ref_pts.storage_offset() % 2:
+        ref_pts = ref_pts.contiguous()
+    return ref_pts, (0 if ref_pts.shape[0] == 1 else ref_pts.stride(0))
+
+
+def deform_attn_pts(value, offsets_logits, ref_pts, H, W):
+    """Deformable-attention core with per-token reference points (lss_deform_attn_pts_fwd).
+    value (B, H*W, 256) fp32; offsets_logits (B, H*W, 192) fp32; ref_pts (B, H*W, 2) fp32 (batch stride 0 allowed)
+    -> (B, H*W, 256) fp32."""
+    B = value.shape[0]
+    _f32c(value, "value", (B, H * W, 256))
+    _f32c(offsets_logits, "offsets_logits", (B, H * W, 192))
+    ref_pts, rstride = _ref_pts_arg(ref_pts, B, H * W)
+    out = torch.empty(B, H * W, 256, dtype=torch.float32, device=value.device)
+    with _timed("deform_attn"):
+        N.check(N.lib().lss_deform_attn_pts_fwd(N.ptr(value), N.ptr(offsets_logits), N.ptr(ref_pts), rstride, B, H, W,
+                                                8, 8, 256, N.ptr(out), N.stream()), "lss_deform_attn_pts_fwd")
+    return out
+
+
+def deform_attn_bwd(value, offsets_logits, ref_pts, d_out, H, W):
+    """Backward of `deform_attn_pts` (lss_deform_attn_bwd) -> d_value (B, H*W, 256), d_offsets_logits
+    (B, H*W, 192), both fp32.  d_value is reduced in int64 fixed point: bit-reproducible, no float atomics."""
+    B = value.shape[0]
+    _f32c(value, "value", (B, H * W, 256))
+    _f32c(offsets_logits, "offsets_logits", (B, H * W, 192))
+    _f32c(d_out, "d_out", (B, H * W, 256))
+    ref_pts, rstride = _ref_pts_arg(ref_pts, B, H * W)
+    nbytes = N.lib().lss_deform_attn_bwd_workspace_bytes(B, H, W)
+    ws = torch.empty((nbytes + 15) // 16, 2, dtype=torch.int64, device=value.device)
+    d_value = torch.empty_like(value)
+    d_ol = torch.empty_like(offsets_logits)
+    with _timed("deform_attn_bwd"):
+        N.check(N.lib().lss_deform_attn_bwd(N.ptr(value), N.ptr(offsets_logits), N.ptr(ref_pts), rstride, N.ptr(d_out),
+                                            B, H, W, 8, 8, 256, N.ptr(ws), ws.numel() * 8, N.ptr(d_value), N.ptr(d_ol),
+                                            N.stream()), "lss_deform_attn_bwd")
+    return d_value, d_ol
+
+
 def layernorm(x, gamma, beta, eps, out_dtype):
     """nn.LayerNorm over the last (256-wide) dim of contiguous fp32|bf16 rows."""
     if not x.is_contiguous() or x.dtype not in (torch.float32, torch.bfloat16):

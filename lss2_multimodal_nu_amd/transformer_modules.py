@@ -7,7 +7,9 @@ reference.  torch.nn modules are PARAMETER CONTAINERS: in inference the
 arithmetic runs in csrc/ (token-major NHWC activations: the linears are 1x1
 MFMA convs, sampling + softmax + weighting is one gather kernel, residual +
 LayerNorm one row kernel).  Training / autograd runs the same parameters through
-torch ops with all heads sampled in ONE batched `grid_sample`.
+torch ops; on the GPU the deformable-attention sampling core is one native
+autograd node (`_DeformAttnFn`: HIP forward and backward), elsewhere all heads
+are sampled in ONE batched `grid_sample`.
 """
 import math
 import os
@@ -81,6 +83,41 @@ class PositionEmbeddingSine(nn.Module):
         return t.t().reshape(1, -1, H, W).expand(B, -1, -1, -1)
 
 
+class _DeformAttnFn(torch.autograd.Function):
+    """Sampling core of DeformableAttention (ref: src/transformer_modules.py:117-156 - softmax over the points,
+    sampling locations with clamp(0, 1), bilinear zero-padded grid_sample, weighted sum) as one native node.
+    value (B, N, 256), offsets_logits (B, N, 192) = [offsets | logits], ref_pts (B, N, 2) -> (B, N, 256) fp32.
+    Runs in fp32 under autocast, as the torch composition does (grid_sample takes the widest input, fp32 grid;
+    softmax is fp32-listed).  Saves only its three inputs; no gradient for the reference points."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, value, offsets_logits, ref_pts, H, W):
+        ctx.dtypes = (value.dtype, offsets_logits.dtype)
+        value = value.float().contiguous()
+        offsets_logits = offsets_logits.float().contiguous()
+        ref_pts = ref_pts.float()
+        ctx.save_for_backward(value, offsets_logits, ref_pts)
+        ctx.hw = (H, W)
+        return ops.deform_attn_pts(value, offsets_logits, ref_pts, H, W)
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, d_out):
+        value, offsets_logits, ref_pts = ctx.saved_tensors
+        d_value, d_ol = ops.deform_attn_bwd(value, offsets_logits, ref_pts, d_out.float().contiguous(), *ctx.hw)
+        return d_value.to(ctx.dtypes[0]), d_ol.to(ctx.dtypes[1]), None, None, None
+
+
+def _deform_native_ok(attn, query, value, reference_points):
+    """Does this DeformableAttention call take the native node?  (GPU tensors, the reference's 256 / 8 heads /
+    8 points, reference points without grad, LSS_DEFORM_NATIVE not "0".)"""
+    return (query.is_cuda and value.is_cuda and reference_points.is_cuda
+            and attn.d_model == 256 and attn.n_heads == 8 and attn.n_points == 8
+            and not reference_points.requires_grad
+            and os.environ.get("LSS_DEFORM_NATIVE", "1") != "0")
+
+
 class DeformableAttention(nn.Module):
     """Every query token samples `n_points` bilinear taps per head around its own
     grid position and mixes them with softmax weights; offsets and weights are
@@ -117,6 +154,10 @@ class DeformableAttention(nn.Module):
         B, N, C = query.shape
         H = W = int(math.sqrt(N))
         nh, npt, ch = self.n_heads, self.n_points, C // self.n_heads
+        if H * W == N and _deform_native_ok(self, query, value, reference_points):
+            ol = torch.cat([self.sampling_offsets(query), self.attention_weights(query)], -1)
+            out = _DeformAttnFn.apply(self.value_proj(value), ol, reference_points, H, W)
+            return self.output_proj(out)
         off = self.sampling_offsets(query).view(B, N, nh, npt, 2)
         aw = self.attention_weights(query).view(B, N, nh, npt).softmax(-1)
         loc = (reference_points[:, :, None, None, :] + off / H).clamp(0, 1)
