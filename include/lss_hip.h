@@ -342,6 +342,24 @@ int lss_conv2d_pack_weights_ks(const float* w_oihw, int Cout, int Cin, void* w_p
  * Cin % 32 == 0) */
 int lss_conv2d_pack_weights_ks_dgrad(const float* w_oihw, int Cout, int Cin, void* w_packed, void* stream);
 
+/* K8k, stride-2 mode: the entry of a downsampling BasicBlock in ONE launch of the same one-pass form (replaces
+ * torchvision BasicBlock.forward's `relu(bn1(conv1(x)))` and `downsample(x)` of layer2.0 / layer3.0 as called from
+ * src/modules.py:104-106):
+ *   y  = act(scale[co] * conv3x3_s2_p1(x, w1)[.., co] + shift[co])               (B, Ho, Wo, Cout) bf16 NHWC
+ *   y2 =     scale[Cout + co] * conv1x1_s2(x, wd)[.., co] + shift[Cout + co]     (B, Ho, Wo, Cout), no activation
+ * with Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1; x (B, H, W, Cin) bf16 NHWC; scale / shift (2 Cout) fp32 or NULL.
+ * K is exactly 9 Cin + Cin: the input patch goes to LDS with its columns de-interleaved by parity, the 1x1 reuses the
+ * centre tap's fragments.  lss_conv2d_ks_s2_dual_ok: 1 when the shape is a case (Cin in {64, 128}, Cout % 64 == 0,
+ * Wo in 48..63 / 24..31, 64-512 workgroups; honours LSS_CONV_KS=0); lss_conv2d_ks_s2_dual_fwd returns LSS_E_SHAPE for
+ * every other shape.  w_packed: lss_conv2d_pack_weights_ks_s2_dual(w1 (Cout, Cin, 3, 3), wd (Cout, Cin)) fp32 ->
+ * [64-channel output block][32-channel chunk][nine taps + the 1x1][4 channel tiles][lane][8] bf16. */
+int lss_conv2d_ks_s2_dual_ok(int B, int H, int W, int Cin, int Cout);
+size_t lss_conv2d_ks_s2_dual_packed_weight_bytes(int Cout, int Cin);
+int lss_conv2d_pack_weights_ks_s2_dual(const float* w1_oihw, const float* wd_oi, int Cout, int Cin, void* w_packed,
+                                       void* stream);
+int lss_conv2d_ks_s2_dual_fwd(const void* x, const void* w_packed, const float* scale, const float* shift, void* y,
+                              void* y2, int B, int H, int W, int Cin, int Cout, int relu, void* stream);
+
 /* ---------------------------------------------------------------------------
  * K8b  gradients of the convolutions (training; replaces the ConvolutionBackward autograd
  *      nodes behind `loss.backward()`, train.py:61, for the convs of src/modules.py:22-27,
@@ -586,9 +604,10 @@ typedef struct lss_conv_launch {
   const void* x; const void* x2; const void* w; const float* scale; const float* shift;
   const void* residual; void* y; float* stats;
   const float* head_w; const float* head_b; float* head_out;   /* kind 2 only */
-  void* y2;                                                     /* kind 3 only */
+  void* y2;                                                     /* kinds 3, 4 */
   int32_t B, H, W, Cx, C2, up, Cout, KH, KW, stride, pad, relu, dt, head_n;
-  int32_t kind;   /* 0 = lss_conv2d_fwd, 1 = lss_conv2d_s2_fwd, 2 = lss_conv2d_head_fwd, 3 = lss_conv2d_s2_dual_fwd */
+  int32_t kind;   /* 0 = lss_conv2d_fwd, 1 = lss_conv2d_s2_fwd, 2 = lss_conv2d_head_fwd, 3 = lss_conv2d_s2_dual_fwd,
+                     4 = lss_conv2d_ks_s2_dual_fwd (Cout: channels of EACH output) */
   int32_t split;  /* kind 3 only */
 } lss_conv_launch_t;
 /* Enqueue `n` conv launches in order on `stream`; returns the first non-zero code. */

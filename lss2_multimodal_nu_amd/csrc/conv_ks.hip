@@ -366,6 +366,313 @@ int ks_launch(const KsPlan& p, const KsArgs& a, hipStream_t st) {
   return lss_launch_status();
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Stride-2 mode: the entry of a downsampling BasicBlock (layer2.0 / layer3.0) - conv1 3x3 / stride 2 / pad 1 + BN + ReLU
+// AND the 1x1 / stride 2 downsample + BN over the same input - as one launch of the same one-pass form.  K is exactly
+// 9 Cin for the 3x3 and Cin for the 1x1 (the phase-plane form on the tile kernel walks 16 (tap, phase) steps for each).
+//   * patch: 7 input rows (3 output rows: a pixel block of PB <= 2 Wo + 1 flattened output pixels spans at most three)
+//     with the COLUMNS DE-INTERLEAVED BY PARITY while they are filled: a patch row is [E: columns 2 j, j < Wo]
+//     [O: columns 2 j - 1, j <= Wo] (pitch 2 Wo + 1 positions; O[0] and, for odd W, O[Wo] come from the zero page).  The B
+//     fragment of 16 consecutive output pixels at tap (ky, kx) is then 16 consecutive positions again: lane base
+//     2 (oy - r0) pitch + ox, wave-uniform tap offset ky pitch + {Wo, 0, Wo + 1}[kx] - the cell layout and the bank
+//     behaviour of the stride-1 kernel;
+//   * workgroup = 3 NPW pixel tiles x 64 output channels (four channel tiles) of BOTH outputs; wave (kp, ph) owns the
+//     nine taps of 32-channel chunk kp (Cin 64: 2 K parts x 2 pixel halves of 48; Cin 128: 4 K parts x 48 pixels): 36 +
+//     4 A fragments in registers, 12 + 12 accumulators;
+//   * the 1x1 rides on the centre tap: at k-step 4 the wave holds the B fragments it needs and issues 12 more MFMAs
+//     against the downsample's A fragments into the second accumulator set - no LDS read of its own;
+//   * both accumulator sets meet through LDS in the fixed order kp = 0 .. NKW - 1 (96 KiB of partial tiles) and leave
+//     through the same epilogue: scale / shift (channels [0, Cout) of the arrays: y, [Cout, 2 Cout): y2), ReLU on y only.
+struct KsS2Args {
+  const unsigned short* x;        // (B, H, W, Cin) bf16 NHWC
+  const unsigned char* w;         // lss_conv2d_pack_weights_ks_s2_dual
+  const float* scale;             // (2 Cout) folded BatchNorm of conv1 | downsample (or null: 1)
+  const float* shift;             // (or null: 0)
+  unsigned short* y;              // (B, Ho, Wo, Cout) bf16 NHWC: act(conv3x3 / 2)
+  unsigned short* y2;             // (B, Ho, Wo, Cout): conv1x1 / 2, no activation
+  int B, H, W, Cin, Cout, relu;
+  int Ho, Wo, pitch;              // patch row pitch in positions: 2 Wo + 1
+  int PB, npb, nposp, ncb;        // as KsArgs; ncb: 64-channel output blocks
+  unsigned long long* stamps;     // as KsArgs
+};
+
+constexpr int KS2_PXT = 3;        // 16-pixel tiles per wave
+constexpr int KS2_CT = 4;         // channel tiles per workgroup (64 output channels)
+
+template <int NKW>
+__global__ __launch_bounds__(256, 1) void conv_ks_s2_dual_kernel(const KsS2Args a) {
+  static_assert(NKW == 4 || NKW == 2, "one 32-channel chunk of nine taps per K part");
+  constexpr int NPW = 4 / NKW, PXT = KS2_PXT, CT = KS2_CT, NT = PXT * NPW, NCH = NKW;
+  extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int kp = wave % NKW, ph = wave / NKW;
+  const int n = lane & 15, kq = lane >> 4;
+  auto stamp = [&](int k) {
+    if (a.stamps != nullptr && tid == 0) a.stamps[(size_t)blockIdx.x * 8 + k] = __builtin_amdgcn_s_memrealtime();
+  };
+  stamp(0);
+  unsigned long long clk_main = 0;
+
+  int t;
+  {
+    const int nwg = gridDim.x, bid = blockIdx.x;
+    const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
+    t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  }
+  const int cb = t % a.ncb;
+  const int pbg = t / a.ncb;
+  const int b = pbg / a.npb, pb = pbg - b * a.npb;
+  const int HWo = a.Ho * a.Wo, WP = a.pitch;
+  const int p0 = pb * a.PB;                       // first output pixel of the block (flattened, inside image b)
+  const int r0 = p0 / a.Wo;                       // patch row 0 = input row 2 r0 - 1
+
+  // ---- input patch -> LDS, columns de-interleaved: position (pr, pc) <- input (2 r0 - 1 + pr, pc < Wo ? 2 pc : 2 (pc - Wo) - 1)
+  {
+    const int ppc = a.nposp >> 4;
+    const int q64 = 64 / WP, r64 = 64 - q64 * WP;
+    const int h = wave & 1;
+    const int pos0 = 32 * (wave >> 1) + (lane >> 1);
+    int pr = pos0 / WP, pc = pos0 - pr * WP;
+    const unsigned char* zsrc = lss_ks_zero_page + (lane & 7) * 16;
+    const unsigned short* xb = a.x + (size_t)b * a.H * a.W * a.Cin + (2 * h + (lane & 1)) * 8;
+    for (int i = wave; i < ppc; i += 4) {
+      const int iy = 2 * r0 - 1 + pr, ix = pc < a.Wo ? 2 * pc : 2 * (pc - a.Wo) - 1;
+      const bool in = pr < KS_ROWS && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
+      const unsigned short* src = xb + (in ? (iy * a.W + ix) * a.Cin : 0);
+#pragma unroll
+      for (int c = 0; c < NCH; ++c)
+        ks_glds16(in ? (const void*)(src + c * 32) : (const void*)zsrc,
+                  smem + ((size_t)(c * 2 + h) * a.nposp + 32 * (i >> 1)) * 32);
+      pr += q64; pc += r64;
+      if (pc >= WP) { pc -= WP; ++pr; }
+    }
+  }
+
+  // ---- weights: nine 3x3 k-steps (streamed as in the stride-1 kernel) + the 1x1 k-step, four channel tiles each ----
+  constexpr int WPRE = 4;
+  bf16x8 wf[9][CT], wd[CT];
+  const unsigned char* wp = a.w + ((size_t)(cb * NKW + kp) * 10 * CT) * 1024 + lane * 16;
+  auto load_w = [&](int s) {
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) wf[s][ct] = *reinterpret_cast<const bf16x8*>(wp + (s * CT + ct) * 1024);
+  };
+#pragma unroll
+  for (int s = 0; s < WPRE; ++s) load_w(s);
+#pragma unroll
+  for (int ct = 0; ct < CT; ++ct) wd[ct] = *reinterpret_cast<const bf16x8*>(wp + (9 * CT + ct) * 1024);
+
+  const int npx = min(a.PB, HWo - p0);
+  int ab[PXT];
+  {
+    const int x_first = p0 - r0 * a.Wo;
+    const int plast = npx - 1;                                   // pixels past the block's end read its last one
+    const int yl = (x_first + plast) / a.Wo, xl = x_first + plast - yl * a.Wo;
+    int pl = ph * PXT * 16 + n;
+    int y = (x_first + pl) / a.Wo, x = x_first + pl - y * a.Wo;   // relative to r0
+#pragma unroll
+    for (int j = 0; j < PXT; ++j) {
+      const bool live = pl < npx;
+      ab[j] = (2 * (live ? y : yl) * WP + (live ? x : xl)) * 32 + (kq >> 1) * a.nposp * 32 + (kq & 1) * 16;
+      pl += 16; x += 16;
+      if (x >= a.Wo) { x -= a.Wo; ++y; }
+    }
+  }
+  stamp(1);
+  f32x4 acc[PXT][CT], acc2[PXT][CT];
+#pragma unroll
+  for (int j = 0; j < PXT; ++j)
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+      acc[j][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      acc2[j][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  stamp(2);
+
+  // ---- main phase: 9 k-steps x PXT pixel tiles x 4 channel tiles, + the 1x1's 4 PXT MFMAs on the centre tap ----
+  bf16x8 fb[2][PXT];
+  auto load_frags = [&](int buf, int s) {
+    const unsigned char* cbase = smem + (size_t)kp * a.nposp * KS_POSB;
+    const int ky = s / 3, kx = s % 3;
+    const int toff = (ky * WP + (kx == 1 ? 0 : kx == 0 ? a.Wo : a.Wo + 1)) * 32;
+#pragma unroll
+    for (int j = 0; j < PXT; ++j) fb[buf][j] = *reinterpret_cast<const bf16x8*>(cbase + ab[j] + toff);
+  };
+  if (a.stamps != nullptr) clk_main = __builtin_amdgcn_s_memtime();
+  load_frags(0, 0);
+#pragma unroll
+  for (int s = 0; s < 9; ++s) {
+    if (s + WPRE < 9) load_w(s + WPRE);
+    if (s + 1 < 9) load_frags((s + 1) & 1, s + 1);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int j = 0; j < PXT; ++j)
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct)
+        acc[j][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s][ct], fb[s & 1][j], acc[j][ct], 0, 0, 0);
+    if (s == 4) {
+#pragma unroll
+      for (int j = 0; j < PXT; ++j)
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct)
+          acc2[j][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wd[ct], fb[0][j], acc2[j][ct], 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+
+  // ---- the K parts meet: part[output][kp][tile][ct][lane], summed in the fixed order kp = 0 .. NKW - 1 ----
+  if (a.stamps != nullptr) asm volatile("s_nop 0" ::"v"(acc[0][0]), "v"(acc[PXT - 1][CT - 1]));
+  stamp(3);
+  if (a.stamps != nullptr && tid == 0) a.stamps[(size_t)blockIdx.x * 8 + 7] = __builtin_amdgcn_s_memtime() - clk_main;
+  __syncthreads();  // every wave is done reading the patch: its LDS is free
+  f32x4* part = reinterpret_cast<f32x4*>(smem);
+#pragma unroll
+  for (int j = 0; j < PXT; ++j) {
+    const int tile = ph * PXT + j;
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+      part[(((0 * NKW + kp) * NT + tile) * CT + ct) * 64 + lane] = acc[j][ct];
+      part[(((1 * NKW + kp) * NT + tile) * CT + ct) * 64 + lane] = acc2[j][ct];
+    }
+  }
+  // epilogue constants: [output][channel group g of 32][8 consecutive channels cb 64 + 32 g + 8 kq ..]
+  float sc[2][2][8], sh[2][2][8];
+#pragma unroll
+  for (int o = 0; o < 2; ++o)
+#pragma unroll
+    for (int g = 0; g < 2; ++g) {
+      const int ch = o * a.Cout + cb * 64 + g * 32 + kq * 8;
+      f32x4 s0 = {1.f, 1.f, 1.f, 1.f}, s1 = s0, h0 = {0.f, 0.f, 0.f, 0.f}, h1 = h0;
+      if (a.scale) { s0 = *reinterpret_cast<const f32x4*>(a.scale + ch); s1 = *reinterpret_cast<const f32x4*>(a.scale + ch + 4); }
+      if (a.shift) { h0 = *reinterpret_cast<const f32x4*>(a.shift + ch); h1 = *reinterpret_cast<const f32x4*>(a.shift + ch + 4); }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { sc[o][g][i] = s0[i]; sc[o][g][4 + i] = s1[i]; sh[o][g][i] = h0[i]; sh[o][g][4 + i] = h1[i]; }
+    }
+  __syncthreads();
+  stamp(4);
+  // wave (kp, ph) finishes the tiles ph * PXT + j with j % NKW == kp, both outputs
+  constexpr int NOWN = (PXT + NKW - 1) / NKW;
+#pragma unroll
+  for (int k = 0; k < NOWN; ++k) {
+    const int j = kp + k * NKW;
+    if (j >= PXT) break;  // wave-uniform
+    const int tile = ph * PXT + j;
+    const int pl = tile * 16 + n;
+    const bool live = pl < npx;
+    const size_t opix = ((size_t)b * HWo + p0 + (live ? pl : 0)) * a.Cout + cb * 64 + kq * 8;
+#pragma unroll
+    for (int o = 0; o < 2; ++o)
+#pragma unroll
+      for (int g = 0; g < 2; ++g) {
+        float v[8];
+#pragma unroll
+        for (int tt = 0; tt < 2; ++tt) {
+          const int ct = 2 * g + tt;
+          f32x4 sum = part[(((o * NKW + 0) * NT + tile) * CT + ct) * 64 + lane];
+#pragma unroll
+          for (int q = 1; q < NKW; ++q) {
+            const f32x4 pv = part[(((o * NKW + q) * NT + tile) * CT + ct) * 64 + lane];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) sum[i] += pv[i];
+          }
+#pragma unroll
+          for (int i = 0; i < 4; ++i) v[4 * tt + i] = sum[i];
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+          v[i] = v[i] * sc[o][g][i] + sh[o][g][i];
+          if (o == 0 && a.relu) v[i] = fmaxf(v[i], 0.f);
+        }
+        if (live) {
+          typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+          const u32x4 ov = {lss_pack_bf2(v[0], v[1]), lss_pack_bf2(v[2], v[3]), lss_pack_bf2(v[4], v[5]), lss_pack_bf2(v[6], v[7])};
+          *reinterpret_cast<u32x4*>((o == 0 ? a.y : a.y2) + opix + g * 32) = ov;
+        }
+      }
+  }
+  if (a.stamps != nullptr) {
+    stamp(5);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    stamp(6);
+  }
+}
+
+// w1 (Cout, Cin, 3, 3) + wd (Cout, Cin) fp32 -> the stride-2 kernel's register image, bf16:
+// [co block of 64][32-channel chunk kp][k-step s: nine taps, then the 1x1][channel tile ct][lane][8]; A-fragment lane
+// (kq, m) of tile ct holds W[co = cb 64 + 32 (ct >> 1) + 8 (m >> 2) + 4 (ct & 1) + (m & 3)][ci = 32 kp + 8 kq .. + 8]
+__global__ void pack_weights_ks_s2_dual_kernel(const float* __restrict__ w1, const float* __restrict__ wd, int Cout,
+                                               int Cin, unsigned short* __restrict__ out) {
+  const size_t ntot = (size_t)Cout * Cin * 10;
+  const int nch = Cin >> 5;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < ntot; e += (size_t)gridDim.x * 256) {
+    const int j = e & 7;
+    size_t r = e >> 3;
+    const int l = r & 63; r >>= 6;
+    const int ct = r & 3; r >>= 2;
+    const int s = r % 10; r /= 10;
+    const int kp = r % nch;
+    const int cb = r / nch;
+    const int m = l & 15, kq = l >> 4;
+    const int co = cb * 64 + 32 * (ct >> 1) + 8 * (m >> 2) + 4 * (ct & 1) + (m & 3);
+    const int ci = kp * 32 + kq * 8 + j;
+    out[e] = lss_f2bf(s < 9 ? w1[((size_t)co * Cin + ci) * 9 + s] : wd[(size_t)co * Cin + ci]);
+  }
+}
+
+struct KsS2Plan {
+  int ok, Ho, Wo, pitch, PB, npb, nposp, ncb, lds, grid, nkw;
+};
+
+KsS2Plan ks_s2_plan(int B, int H, int W, int Cin, int Cout) {
+  KsS2Plan p = {};
+  if (B <= 0 || H < 2 || W < 4 || Cout <= 0 || Cout % 64 != 0) return p;
+  if (Cin == 128) p.nkw = 4;
+  else if (Cin == 64) p.nkw = 2;
+  else return p;
+  p.Ho = (H - 1) / 2 + 1; p.Wo = (W - 1) / 2 + 1;
+  p.pitch = 2 * p.Wo + 1;
+  p.PB = 16 * KS2_PXT * (4 / p.nkw);
+  if (p.PB > 2 * p.Wo + 1) return p;                 // a pixel block spans at most three output rows
+  const long long HWo = (long long)p.Ho * p.Wo;
+  p.npb = (int)((HWo + p.PB - 1) / p.PB);
+  p.ncb = Cout / 64;
+  p.nposp = (KS_ROWS * p.pitch + 31) / 32 * 32;
+  const int patch = (Cin / 32) * p.nposp * KS_POSB;
+  if (patch > 112 * 1024) return p;
+  const int red = 2 * p.nkw * (p.PB / 16) * KS2_CT * 1024;   // the K parts' partial tiles of both outputs
+  p.lds = patch > red ? patch : red;
+  if (p.lds > KS_LDS_MAX) return p;
+  const long long grid = (long long)B * p.npb * p.ncb;
+  if (grid < 64 || grid > 512) return p;
+  if ((long long)B * H * W * Cin >= (1LL << 30) || (long long)B * HWo * Cout >= (1LL << 30)) return p;
+  p.grid = (int)grid;
+  p.ok = 1;
+  return p;
+}
+
+template <int NKW>
+int ks_s2_launch(const KsS2Plan& p, const KsS2Args& a, hipStream_t st) {
+  static bool attr_set[64] = {};
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
+  if (dev < 0 || !attr_set[dev]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_ks_s2_dual_kernel<NKW>),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, KS_LDS_MAX);
+    if (e != hipSuccess) return (int)e;
+    if (dev >= 0) attr_set[dev] = true;
+  }
+  hipLaunchKernelGGL((conv_ks_s2_dual_kernel<NKW>), dim3(p.grid), dim3(256), p.lds, st, a);
+  return lss_launch_status();
+}
+
+// the diagnostic stamp buffer of tools/bench_ks.py --stamps (both kernels of this file), or null
+unsigned long long* ks_stamps_from_env() {
+  const char* e = getenv("LSS_KS_STAMPS");
+  return e ? reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 16)) : nullptr;
+}
+
 }  // namespace
 
 // Is (shape) a case for the K-split one-pass kernel?  3x3 / stride 1 / pad 1, bf16, Cin in {64, 128, 256}, Cout a
@@ -420,11 +727,56 @@ int lss_conv_ks_launch(const void* x, const void* w_ks, const float* scale, cons
   a.y = reinterpret_cast<unsigned short*>(y);
   a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.relu = relu; a.wt = wt;
   a.PB = p.PB; a.npb = p.npb; a.nposp = p.nposp; a.ncb = p.ncb;
-  {
-    const char* e = getenv("LSS_KS_STAMPS");
-    a.stamps = e ? reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 16)) : nullptr;
-  }
+  a.stamps = ks_stamps_from_env();
   if (p.variant == 0) return ks_launch<18, 4, 5>(p, a, st);
   if (p.variant == 1) return ks_launch<9, 4, 10>(p, a, st);
   return ks_launch<9, 2, 10>(p, a, st);
+}
+
+// Stride-2 mode (conv1 3x3 / 2 + the 1x1 / 2 downsample of a BasicBlock in one launch): is (shape) a case?  bf16, Cin in
+// {64, 128}, Cout a multiple of 64, an output 48-63 (Cin 64) / 24-31 (Cin 128) pixels wide - the 7-row patch fits LDS
+// and a pixel block of 96 / 48 spans at most three output rows - and a grid of 64-512 workgroups.
+extern "C" int lss_conv2d_ks_s2_dual_ok(int B, int H, int W, int Cin, int Cout) {
+  if (const char* e = getenv("LSS_CONV_KS"))
+    if (atoi(e) == 0) return 0;
+  return ks_s2_plan(B, H, W, Cin, Cout).ok;
+}
+
+extern "C" size_t lss_conv2d_ks_s2_dual_packed_weight_bytes(int Cout, int Cin) {
+  if (Cout <= 0 || Cout % 64 != 0 || (Cin != 64 && Cin != 128)) return 0;
+  return (size_t)Cout * Cin * 10 * 2;
+}
+
+extern "C" int lss_conv2d_pack_weights_ks_s2_dual(const float* w1_oihw, const float* wd_oi, int Cout, int Cin,
+                                                  void* w_packed, void* stream) {
+  LSS_CHECK_PTR(w1_oihw); LSS_CHECK_PTR(wd_oi); LSS_CHECK_PTR(w_packed);
+  if (lss_conv2d_ks_s2_dual_packed_weight_bytes(Cout, Cin) == 0) return LSS_E_SHAPE;
+  const size_t n = (size_t)Cout * Cin * 10;
+  const int grid = (int)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
+  hipLaunchKernelGGL(pack_weights_ks_s2_dual_kernel, dim3(grid), dim3(256), 0, lss_stream(stream), w1_oihw, wd_oi, Cout,
+                     Cin, reinterpret_cast<unsigned short*>(w_packed));
+  return lss_launch_status();
+}
+
+extern "C" int lss_conv2d_ks_s2_dual_fwd(const void* x, const void* w_packed, const float* scale, const float* shift,
+                                         void* y, void* y2, int B, int H, int W, int Cin, int Cout, int relu,
+                                         void* stream) {
+  LSS_CHECK_PTR(x); LSS_CHECK_PTR(w_packed); LSS_CHECK_PTR(y); LSS_CHECK_PTR(y2);
+  const KsS2Plan p = ks_s2_plan(B, H, W, Cin, Cout);
+  if (!p.ok) return LSS_E_SHAPE;
+  if (relu != 0 && relu != 1) return LSS_E_LAYOUT;
+  if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(y2) |
+        reinterpret_cast<uintptr_t>(w_packed) | reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(shift)) & 15) != 0)
+    return LSS_E_ALIGN;
+  KsS2Args a;
+  a.x = reinterpret_cast<const unsigned short*>(x);
+  a.w = reinterpret_cast<const unsigned char*>(w_packed);
+  a.scale = scale; a.shift = shift;
+  a.y = reinterpret_cast<unsigned short*>(y);
+  a.y2 = reinterpret_cast<unsigned short*>(y2);
+  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.relu = relu;
+  a.Ho = p.Ho; a.Wo = p.Wo; a.pitch = p.pitch;
+  a.PB = p.PB; a.npb = p.npb; a.nposp = p.nposp; a.ncb = p.ncb;
+  a.stamps = ks_stamps_from_env();
+  return p.nkw == 4 ? ks_s2_launch<4>(p, a, lss_stream(stream)) : ks_s2_launch<2>(p, a, lss_stream(stream));
 }

@@ -845,12 +845,27 @@ class BasicBlock(nn.Module):
             self._dual_key = key
         return self._dual_pack
 
+    def _dual_ks(self, dt):
+        """The same two weight sets in the layout of the K-split kernel's stride-2 mode; `_dual(dt)` must have been
+        called for the current key."""
+        if getattr(self, "_dual_ks_key", None) != self._dual_key:
+            with torch.no_grad():
+                self._dual_ks_pack = ops.pack_conv_weight_ks_s2_dual(
+                    self.conv1.weight.detach().float().contiguous(),
+                    self.downsample[0].weight.detach().float().contiguous())
+            self._dual_ks_key = self._dual_key
+        return self._dual_ks_pack
+
     def _nhwc(self, x, dt):
         c1 = self.conv1
         if (self._fd is not None and dt == ops.DT_BF16 and c1.stride == (2, 2) and self._f1._s2d(dt)
                 and self.downsample[0].stride == (2, 2) and c1.out_channels % 128 == 0
                 and os.environ.get("LSS_NO_DUAL") is None):
             w, scale, shift = self._dual(dt)
+            B, H, W, Cx = x.shape
+            if ops.conv_ks_s2_dual_ok(B, H, W, Cx, c1.out_channels):   # one pass, K = 9 Cin + Cin (csrc/conv_ks.hip)
+                t, idt = ops.conv2d_ks_s2_dual_nhwc(x, self._dual_ks(dt), scale, shift, relu=True)
+                return self._f2.run(t, dt, relu=True, residual=idt)
             t, idt = ops.conv2d_s2_dual_nhwc(x, w, scale, shift, c1.out_channels, relu=True)
             return self._f2.run(t, dt, relu=True, residual=idt)
         idt = x if self._fd is None else self._fd.run(x, dt, relu=False)

@@ -1368,6 +1368,52 @@ def conv2d_s2_dual_nhwc(x, w_s2d, scale, shift, split, relu=True, tag="conv2d_fw
     return y, y2
 
 
+def conv_ks_s2_dual_ok(B, H, W, Cin, Cout):
+    """Is this BasicBlock entry (3x3 / stride 2 / pad 1 conv + 1x1 / stride 2 downsample, bf16, Cout channels each) a
+    case for the stride-2 mode of the K-split one-pass kernel (lss_conv2d_ks_s2_dual_ok)?"""
+    return bool(N.lib().lss_conv2d_ks_s2_dual_ok(B, H, W, Cin, Cout))
+
+
+def pack_conv_weight_ks_s2_dual(w1_oihw, wd_oihw):
+    """conv1 (Cout, Cin, 3, 3) + downsample (Cout, Cin, 1, 1) fp32 -> KsWeight in the stride-2 K-split layout."""
+    Cout, Cin, KH, KW = w1_oihw.shape
+    _f32c(w1_oihw, "conv weight")
+    _f32c(wd_oihw, "downsample weight", (Cout, Cin, 1, 1))
+    nbytes = N.lib().lss_conv2d_ks_s2_dual_packed_weight_bytes(Cout, Cin)
+    if (KH, KW) != (3, 3) or nbytes == 0:
+        raise ValueError("KS stride-2 weights: 3x3 + 1x1, Cout %% 64 == 0, Cin in (64, 128) (got %s)"
+                         % (tuple(w1_oihw.shape),))
+    out = torch.empty(nbytes // 2, dtype=torch.bfloat16, device=w1_oihw.device)
+    N.check(N.lib().lss_conv2d_pack_weights_ks_s2_dual(N.ptr(w1_oihw), N.ptr(wd_oihw), Cout, Cin, N.ptr(out),
+                                                       N.stream()), "lss_conv2d_pack_weights_ks_s2_dual")
+    return KsWeight(out, Cout, Cin)
+
+
+def conv2d_ks_s2_dual_nhwc(x, w_ks, scale=None, shift=None, relu=True, tag="conv2d_fwd"):
+    """relu(scale[:C] * conv3x3/2(x, w1) + shift[:C]) and scale[C:] * conv1x1/2(x, wd) + shift[C:] over the same bf16
+    NHWC input in one launch of the K-split one-pass kernel; w_ks from pack_conv_weight_ks_s2_dual, scale / shift
+    (2 Cout) fp32 or None.  Returns (y, y2), both (B, Ho, Wo, Cout)."""
+    B, H, W, Cx = x.shape
+    if x.dtype != torch.bfloat16 or not x.is_contiguous() or not isinstance(w_ks, KsWeight) or w_ks.Cin != Cx \
+            or w_ks.data.numel() != w_ks.Cout * Cx * 10:
+        raise ValueError("conv2d_ks_s2_dual_nhwc operands must be contiguous bf16 with stride-2 KS-packed weights")
+    Cout = w_ks.Cout
+    for name, t in (("scale", scale), ("shift", shift)):
+        if t is not None:
+            _f32c(t, name, (2 * Cout,))
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    y = torch.empty(B, Ho, Wo, Cout, dtype=torch.bfloat16, device=x.device)
+    y2 = torch.empty(B, Ho, Wo, Cout, dtype=torch.bfloat16, device=x.device)
+    if _recorder is not None:
+        _recorder.add(4, (x, w_ks.data, scale, shift, y, y2), x=x, w=w_ks.data, scale=scale, shift=shift, y=y, y2=y2,
+                      B=B, H=H, W=W, Cx=Cx, Cout=Cout, KH=3, KW=3, stride=2, pad=1, relu=1 if relu else 0, dt=DT_BF16)
+    with _timed(tag):
+        N.check(N.lib().lss_conv2d_ks_s2_dual_fwd(N.ptr(x), N.ptr(w_ks.data), N.ptr(scale), N.ptr(shift), N.ptr(y),
+                                                  N.ptr(y2), B, H, W, Cx, Cout, 1 if relu else 0, N.stream()),
+                "lss_conv2d_ks_s2_dual_fwd")
+    return y, y2
+
+
 def conv3x3_head_nchw(x, w_packed, scale, shift, head_w, head_b, x2=None, up=1, relu=True, tag="conv2d_fwd"):
     """3x3/s1/p1 conv (+fused upsample/concat) + scale/shift + ReLU + 1x1 head in one launch.
     x (B,H,W,Cx) bf16 NHWC; head_w (n,Cout) fp32, Cout = 128 (64: plain 3x3 only); returns (B, n, H*up, W*up)

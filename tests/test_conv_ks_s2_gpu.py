@@ -1,0 +1,195 @@
+"""K8k stride-2 mode (csrc/conv_ks.hip: conv_ks_s2_dual_kernel): the entry of a downsampling BasicBlock - conv1 3x3 / 2
++ BN + ReLU and the 1x1 / 2 downsample + BN of resnet18's layer2.0 / layer3.0 inside BevEncode (ref src/modules.py:104-106
++ torchvision BasicBlock) - as one launch of the one-pass K-split kernel.  Both outputs against torch's CPU convs on the
+same bf16-rounded operands and against the phase-plane dual launch it replaces, at the benchmark shapes and at odd /
+ragged ones; the refusal of shapes outside its plan; the module-level fallback; the recorded BevEncode plan."""
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+BF16_OUT_TOL = 6e-3   # tests/test_conv_ks_gpu.py: fp32 accumulation, output rounded once to bf16
+
+
+@pytest.fixture(scope="module")
+def ops():
+    assert torch.cuda.is_available()
+    from lss2_multimodal_nu_amd import ops as _ops
+    return _ops
+
+
+def _q(t):
+    return t.bfloat16().float()
+
+
+SHAPES = [
+    # B, H, W, Cin, Cout, folded BN
+    (4, 100, 100, 64, 128, True),    # layer2.0 at the benched batch: 27 blocks of 96 pixels (the last of 4), 2 K parts
+    (4, 50, 50, 128, 256, True),     # layer3.0: 14 blocks of 48 pixels (the last of 1), 4 K parts
+    (4, 100, 100, 64, 128, False),   # no BatchNorm: scale / shift NULL
+    (4, 53, 51, 128, 256, True),     # odd H and W: 27 x 26 outputs, the last odd-plane column is padding; last block of 30
+    (3, 99, 97, 64, 128, False),     # odd, Cin 64: 50 x 49 outputs, last block of 50
+    (4, 50, 50, 128, 192, True),     # Cout != 2 Cin: three 64-channel blocks
+    (2, 48, 62, 128, 256, True),     # 24 x 31 = 744 outputs: last block of 24; the widest row the Cin-128 patch takes
+    (1, 126, 96, 64, 192, True),     # batch 1, 63 x 48: the narrowest row a 96-pixel block takes (spans three rows)
+]
+
+
+def _run_case(ops, cfg):
+    B, H, W, Cin, Cout, bn = cfg
+    gen = torch.Generator().manual_seed(sum(int(c) for c in cfg))
+    x = _q(torch.randn(B, Cin, H, W, generator=gen))
+    w1 = _q(torch.randn(Cout, Cin, 3, 3, generator=gen) * (Cin * 9) ** -0.5)
+    wd = _q(torch.randn(Cout, Cin, 1, 1, generator=gen) * Cin ** -0.5)
+    scale = (torch.rand(2 * Cout, generator=gen) + 0.5) if bn else None
+    shift = (torch.randn(2 * Cout, generator=gen) * 0.1) if bn else None
+    ref1 = torch.nn.functional.conv2d(x, w1, None, stride=2, padding=1)
+    ref2 = torch.nn.functional.conv2d(x, wd, None, stride=2)
+    if bn:
+        ref1 = ref1 * scale[:Cout].view(1, -1, 1, 1) + shift[:Cout].view(1, -1, 1, 1)
+        ref2 = ref2 * scale[Cout:].view(1, -1, 1, 1) + shift[Cout:].view(1, -1, 1, 1)
+    ref1 = ref1.relu()
+    return x, w1, wd, scale, shift, ref1, ref2
+
+
+@pytest.mark.parametrize("cfg", SHAPES)
+def test_ks_s2_dual_vs_torch_and_phase_plane_kernel(ops, report, cfg):
+    B, H, W, Cin, Cout, bn = cfg
+    assert ops.conv_ks_s2_dual_ok(B, H, W, Cin, Cout), "test shape must be a case for the stride-2 K-split kernel"
+    x, w1, wd, scale, shift, ref1, ref2 = _run_case(ops, cfg)
+    xg = ops.nchw_to_nhwc(x.cuda(), 1)
+    sg, hg = (scale.cuda(), shift.cuda()) if bn else (None, None)
+    wk = ops.pack_conv_weight_ks_s2_dual(w1.cuda(), wd.cuda())
+    y, y2 = ops.conv2d_ks_s2_dual_nhwc(xg, wk, sg, hg, relu=True)
+    yb, y2b = ops.conv2d_ks_s2_dual_nhwc(xg, wk, sg, hg, relu=True)
+    out1, out2 = ops.nhwc_to_nchw(y, 1).cpu(), ops.nhwc_to_nchw(y2, 1).cpu()
+    assert out1.shape == ref1.shape and out2.shape == ref2.shape
+    tag = "x".join(str(int(c)) for c in cfg)
+    for nm, out, ref in (("y", out1, ref1), ("y2", out2, ref2)):
+        e_max = report("k8k_s2_max_rel_%s_%s" % (nm, tag), (out - ref).abs().max() / ref.abs().max())
+        e_l2 = report("k8k_s2_rel_l2_%s_%s" % (nm, tag), (out - ref).norm() / ref.norm())
+        print("%s %s: max-rel %.3e rel-L2 %.3e" % (tag, nm, e_max, e_l2))
+        assert e_max <= BF16_OUT_TOL
+        assert e_l2 <= BF16_OUT_TOL / 3
+    assert float(out2.min()) < 0 and float(out1.min()) >= 0   # ReLU on y only
+    assert torch.equal(y, yb) and torch.equal(y2, y2b)        # fixed summation order: bit-reproducible
+    if Cout % 128 == 0:
+        # the phase-plane dual launch on the same operands: the same fp32 products in another order
+        frame = torch.zeros(Cout, Cin, 3, 3)
+        frame[:, :, 1, 1] = wd[:, :, 0, 0]
+        wcat = torch.cat([ops.pack_conv_weight_s2d(w1.cuda(), 1), ops.pack_conv_weight_s2d(frame.cuda(), 1)], 1).contiguous()
+        so = sg if bn else torch.ones(2 * Cout, device="cuda")
+        ho = hg if bn else torch.zeros(2 * Cout, device="cuda")
+        o, o2 = ops.conv2d_s2_dual_nhwc(xg, wcat, so, ho, Cout, relu=True)
+        for nm, new, old, ref in (("y", y, o, ref1), ("y2", y2, o2, ref2)):
+            e = report("k8k_s2_vs_dual_%s_%s" % (nm, tag),
+                       (new.float() - old.float()).abs().max().cpu() / ref.abs().max())
+            print("%s %s vs phase-plane dual: max-rel %.3e" % (tag, nm, e))
+            assert e <= BF16_OUT_TOL
+
+
+REFUSED = [
+    (4, 200, 200, 64, 128),   # the hires workload: the 7-row patch of a 100-wide output does not fit
+    (4, 100, 100, 64, 96),    # Cout not a multiple of 64
+    (4, 50, 50, 256, 512),    # Cin 256
+    (4, 37, 41, 128, 256),    # 21 outputs per row: a 48-pixel block would span four rows
+    (1, 50, 50, 128, 256),    # 56 workgroups: under the plan's 64
+]
+
+
+@pytest.mark.parametrize("shape", REFUSED)
+def test_ks_s2_dual_refuses_shapes_outside_its_plan(ops, shape):
+    """An argument error from the C entry, not a silent fallback inside it."""
+    from lss2_multimodal_nu_amd import _native as N
+    B, H, W, Cin, Cout = shape
+    assert not ops.conv_ks_s2_dual_ok(B, H, W, Cin, Cout)
+    x = torch.zeros(B, H, W, Cin, device="cuda").bfloat16()
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    y = torch.zeros(B, Ho, Wo, Cout, device="cuda").bfloat16()
+    y2 = torch.zeros_like(y)
+    w = torch.zeros(Cout * Cin * 10, device="cuda").bfloat16()
+    rc = N.lib().lss_conv2d_ks_s2_dual_fwd(N.ptr(x), N.ptr(w), None, None, N.ptr(y), N.ptr(y2), B, H, W, Cin, Cout, 1,
+                                           N.stream())
+    assert rc == -2   # LSS_E_SHAPE
+    torch.cuda.synchronize()
+
+
+def _block(inplanes, planes, seed):
+    import lss2_multimodal_nu_amd as L
+    from lss2_multimodal_nu_amd.modules import BasicBlock
+    torch.manual_seed(seed)
+    blk = BasicBlock(inplanes, planes, 2)
+    with torch.no_grad():
+        for m in blk.modules():
+            if isinstance(m, torch.nn.BatchNorm2d):
+                m.weight.uniform_(0.5, 1.5)
+                m.bias.normal_(0, 0.1)
+                m.running_mean.normal_(0, 0.1)
+                m.running_var.uniform_(0.5, 1.5)
+    return blk.cuda().eval(), L
+
+
+def test_basic_block_takes_the_new_path_and_falls_back(ops, monkeypatch):
+    """A BasicBlock on a benched shape runs the stride-2 K-split launch (recorded kind 4) and agrees with the phase-plane
+    path within the output rounding; on a shape the plan refuses (too wide for the patch) it gives the old path's bits;
+    LSS_NO_DUAL and LSS_CONV_KS=0 switch it off."""
+    blk, L = _block(64, 128, 5)
+
+    def run(x):
+        rec = ops.ConvRecorder()
+        ops.set_recorder(rec)
+        try:
+            with torch.no_grad():
+                y = blk._nhwc(x, ops.DT_BF16)
+        finally:
+            ops.set_recorder(None)
+        return y, [k for k, _ in rec.launches]
+
+    x = torch.randn(4, 100, 100, 64, device="cuda").bfloat16()
+    y_new, kinds = run(x)
+    assert kinds == [4, 0]
+    monkeypatch.setenv("LSS_CONV_KS", "0")
+    y_old, kinds = run(x)
+    assert kinds == [3, 0]
+    monkeypatch.delenv("LSS_CONV_KS")
+    monkeypatch.setenv("LSS_NO_DUAL", "1")
+    _, kinds = run(x)
+    assert 3 not in kinds and 4 not in kinds and len(kinds) == 3
+    monkeypatch.delenv("LSS_NO_DUAL")
+    e = float((y_new.float() - y_old.float()).abs().max() / y_old.float().abs().max())
+    print("BasicBlock 64->128 @100, new vs old path: max-rel %.3e" % e)
+    assert e <= 2 * BF16_OUT_TOL   # two bf16 roundings in a row (conv1's output, then conv2's)
+    # refused shape: 160 wide -> 80 outputs per row, the patch does not fit
+    xw = torch.randn(2, 160, 160, 64, device="cuda").bfloat16()
+    assert not ops.conv_ks_s2_dual_ok(2, 160, 160, 64, 128)
+    y_a, kinds = run(xw)
+    assert kinds[0] == 3
+    w, scale, shift = blk._dual(ops.DT_BF16)
+    with torch.no_grad():
+        t, idt = ops.conv2d_s2_dual_nhwc(xw, w, scale, shift, 128, relu=True)
+        y_b = blk._f2.run(t, ops.DT_BF16, relu=True, residual=idt)
+    assert torch.equal(y_a, y_b)
+
+
+def test_bevencode_plan_replays_the_new_launches(ops):
+    """BevEncode at the benched shape: 16 recorded launches, two of them the stride-2 K-split kind; the replay equals the
+    recording pass; no bounded wait was hit."""
+    import lss2_multimodal_nu_amd as L
+    torch.manual_seed(3)
+    be = L.BevEncode(64, 4, precision="bf16")
+    with torch.no_grad():
+        for m in be.modules():
+            if isinstance(m, torch.nn.BatchNorm2d):
+                m.weight.uniform_(0.5, 1.5)
+                m.running_var.uniform_(0.5, 1.5)
+    be = be.cuda().eval()
+    x = torch.randn(4, 200, 200, 64, device="cuda").bfloat16()
+    with torch.no_grad():
+        a = be.forward_nhwc(x, ops.DT_BF16)
+        b = be.forward_nhwc(x, ops.DT_BF16)
+    torch.cuda.synchronize()
+    (plan, _), = be._plans.values()
+    kinds = [int(plan.arr[i].kind) for i in range(plan.n)]
+    assert plan.n == 16 and kinds.count(4) == 2 and 3 not in kinds
+    assert torch.equal(a, b)
+    assert all(v == 0 for v in ops.timeout_counters().values())

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """The launch-bound 3x3 / stride-1 layers of BevEncode (layer1-3, batch 4) on the tile kernel (conv_mfma.hip) and on the
 K-split one-pass kernel (conv_ks.hip), back to back inside ONE recorded launch list per kernel so that the host is out
-of the picture (HIP-event timing of 40 launches per bracket).   python tools/bench_ks.py [--rounds 5]"""
+of the picture (HIP-event timing of 40 launches per bracket); then the two stride-2 BasicBlock entries (layer2.0,
+layer3.0) on the phase-plane dual launch and on the K-split kernel's stride-2 mode.   python tools/bench_ks.py [--rounds 5]"""
 import argparse
 import os
 import sys
@@ -12,6 +13,82 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from lss2_multimodal_nu_amd import ops  # noqa: E402
 
 LAYERS = [("layer1 64->64 @100", 4, 100, 100, 64), ("layer2 128->128 @50", 4, 50, 50, 128), ("layer3 256->256 @25", 4, 25, 25, 256)]
+
+
+S2_LAYERS = [("layer2.0 64->128 @100/2", 4, 100, 100, 64, 128), ("layer3.0 128->256 @50/2", 4, 50, 50, 128, 256)]
+
+
+def _s2_operands(B, H, W, Cin, Cout):
+    """x + the two weight sets of a stride-2 BasicBlock entry, packed for the phase-plane dual launch and for the K-split
+    stride-2 mode."""
+    x = torch.randn(B, H, W, Cin, device="cuda").bfloat16()
+    w1 = torch.randn(Cout, Cin, 3, 3, device="cuda") * (Cin * 9) ** -0.5
+    wd = torch.randn(Cout, Cin, 1, 1, device="cuda") * Cin ** -0.5
+    sc, sh = torch.rand(2 * Cout, device="cuda") + 0.5, torch.randn(2 * Cout, device="cuda") * 0.1
+    frame = torch.zeros(Cout, Cin, 3, 3, device="cuda")
+    frame[:, :, 1, 1] = wd[:, :, 0, 0]
+    wcat = torch.cat([ops.pack_conv_weight_s2d(w1, 1), ops.pack_conv_weight_s2d(frame, 1)], 1).contiguous()
+    return x, wcat, ops.pack_conv_weight_ks_s2_dual(w1, wd), sc, sh
+
+
+def _print_stamps(name, buf, n_mfma):
+    import numpy as np
+    t = buf.view(-1, 8).cpu().numpy().astype(np.float64) * 0.01
+    t = t[t[:, 0] != 0]
+    t0 = t[:, 0].min()
+    f = lambda v: "%5.2f/%5.2f" % (np.median(v), v.max())  # noqa: E731
+    print("%-22s %4d | %s  %s  %s  %s  %s  %s  %s | %s" % (
+        name, len(t), f(t[:, 0] - t0), f(t[:, 1] - t[:, 0]), f(t[:, 2] - t[:, 1]), f(t[:, 3] - t[:, 2]),
+        f(t[:, 4] - t[:, 3]), f(t[:, 5] - t[:, 4]), f(t[:, 6] - t[:, 5]), f(t[:, 6] - t[:, 0])))
+    clk = t[:, 7] * 100.0  # slot 7: s_memtime ticks over the main phase
+    print("%-22s        main phase: %.0f s_memtime ticks (median) = %.1f per MFMA of a wave; ticks per us of s_memrealtime %.0f"
+          % ("", np.median(clk), np.median(clk) / n_mfma, np.median(clk / np.maximum(t[:, 3] - t[:, 2], 1e-3))))
+
+
+def stamps_s2():
+    for name, B, H, W, Cin, Cout in S2_LAYERS:
+        x, _, wk, sc, sh = _s2_operands(B, H, W, Cin, Cout)
+        for _ in range(5):
+            ops.conv2d_ks_s2_dual_nhwc(x, wk, sc, sh)
+        buf = torch.zeros(1024 * 8, dtype=torch.int64, device="cuda")
+        os.environ["LSS_KS_STAMPS"] = "%x" % buf.data_ptr()
+        torch.cuda.synchronize()
+        ops.conv2d_ks_s2_dual_nhwc(x, wk, sc, sh)
+        torch.cuda.synchronize()
+        del os.environ["LSS_KS_STAMPS"]
+        _print_stamps(name, buf, 120.0)
+
+
+def bench_s2(rounds, chain):
+    """Per-launch time of the stride-2 entries inside one recorded list: `chain` launches over the same input (the
+    output is half the size, so no dependent chain; the launches still serialise on the stream)."""
+    plans, res = [], {}
+    for name, B, H, W, Cin, Cout in S2_LAYERS:
+        x, wcat, wk, sc, sh = _s2_operands(B, H, W, Cin, Cout)
+        for tag in ("dual", "ks"):
+            rec = ops.ConvRecorder()
+            ops.set_recorder(rec)
+            for _ in range(chain):
+                y, _ = ops.conv2d_s2_dual_nhwc(x, wcat, sc, sh, Cout) if tag == "dual" else \
+                    ops.conv2d_ks_s2_dual_nhwc(x, wk, sc, sh)
+            ops.set_recorder(None)
+            plans.append((name, tag, ops.ConvPlan(rec, x, y), x, y))
+    for _ in range(3):
+        for name, tag, plan, x, y in plans:
+            plan.run(x, y)
+    torch.cuda.synchronize()
+    for _ in range(rounds):
+        for name, tag, plan, x, y in plans:
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            plan.run(x, y)
+            e.record()
+            torch.cuda.synchronize()
+            res.setdefault((name, tag), []).append(s.elapsed_time(e) * 1e3 / chain)
+    for name, *_ in S2_LAYERS:
+        t, k = sorted(res[(name, "dual")]), sorted(res[(name, "ks")])
+        print("%-22s dual %5.2f us (min %6.2f)   ks %6.2f us (min %6.2f)   per launch incl. its boundary"
+              % (name, t[len(t) // 2], t[0], k[len(k) // 2], k[0]))
 
 
 def stamps():
@@ -42,6 +119,7 @@ def stamps():
         clk = t[:, 7] * 100.0  # slot 7: s_memtime ticks over the main phase
         print("%-22s        main phase: %.0f s_memtime ticks (median) = %.1f per MFMA of a wave; ticks per us of s_memrealtime %.0f"
               % ("", np.median(clk), np.median(clk) / 180.0, np.median(clk / np.maximum(t[:, 3] - t[:, 2], 1e-3))))
+    stamps_s2()
 
 
 def main():
@@ -84,6 +162,7 @@ def main():
         t, k = sorted(res[(name, "tile")]), sorted(res[(name, "ks")])
         print("%-22s tile %6.2f us (min %6.2f)   ks %6.2f us (min %6.2f)   per launch incl. its boundary"
               % (name, t[len(t) // 2], t[0], k[len(k) // 2], k[0]))
+    bench_s2(a.rounds, a.chain)
 
 
 if __name__ == "__main__":
