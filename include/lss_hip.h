@@ -360,6 +360,22 @@ int lss_conv2d_pack_weights_ks_s2_dual(const float* w1_oihw, const float* wd_oi,
 int lss_conv2d_ks_s2_dual_fwd(const void* x, const void* w_packed, const float* scale, const float* shift, void* y,
                               void* y2, int B, int H, int W, int Cin, int Cout, int relu, void* stream);
 
+/* K8k, stem mode: BevEncode's 7x7 / stride-2 / pad-3 stem (ref src/modules.py:96-98, 120-122: conv1 - bn1 - relu) in ONE
+ * launch of the one-pass form:
+ *   y = act(scale[co] * conv7x7_s2_p3(x, w)[.., co] + shift[co])                 (B, Ho, Wo, Cout) bf16 NHWC
+ * with Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1; x (B, H, W, 64) bf16 NHWC; scale / shift (Cout) fp32 or NULL.
+ * K is exactly 49 x 64: a workgroup owns a 12 x 16 tile of output pixels x 64 channels, its 29 x 37 input patch goes to
+ * LDS once with the columns de-interleaved by parity, the weights stream through registers.
+ * lss_conv2d_ks_stem_ok: 1 when the shape is a case (Cin == 64, Cout % 64 == 0, Ho >= 12, Wo >= 16, 32-256 workgroups
+ * of B x ceil(Ho / 12) x ceil(Wo / 16) x Cout / 64; honours LSS_CONV_KS=0); lss_conv2d_ks_stem_fwd returns LSS_E_SHAPE
+ * for every other shape.  w_packed: lss_conv2d_pack_weights_ks_stem(w (Cout, 64, 7, 7)) fp32 ->
+ * [64-channel output block][tap][32-channel chunk][4 channel tiles][lane][8] bf16. */
+int lss_conv2d_ks_stem_ok(int B, int H, int W, int Cin, int Cout);
+size_t lss_conv2d_ks_stem_packed_weight_bytes(int Cout, int Cin);
+int lss_conv2d_pack_weights_ks_stem(const float* w_oihw, int Cout, int Cin, void* w_packed, void* stream);
+int lss_conv2d_ks_stem_fwd(const void* x, const void* w_packed, const float* scale, const float* shift, void* y,
+                           int B, int H, int W, int Cin, int Cout, int relu, void* stream);
+
 /* ---------------------------------------------------------------------------
  * K8b  gradients of the convolutions (training; replaces the ConvolutionBackward autograd
  *      nodes behind `loss.backward()`, train.py:61, for the convs of src/modules.py:22-27,
@@ -607,7 +623,7 @@ typedef struct lss_conv_launch {
   void* y2;                                                     /* kinds 3, 4 */
   int32_t B, H, W, Cx, C2, up, Cout, KH, KW, stride, pad, relu, dt, head_n;
   int32_t kind;   /* 0 = lss_conv2d_fwd, 1 = lss_conv2d_s2_fwd, 2 = lss_conv2d_head_fwd, 3 = lss_conv2d_s2_dual_fwd,
-                     4 = lss_conv2d_ks_s2_dual_fwd (Cout: channels of EACH output) */
+                     4 = lss_conv2d_ks_s2_dual_fwd (Cout: channels of EACH output), 5 = lss_conv2d_ks_stem_fwd */
   int32_t split;  /* kind 3 only */
 } lss_conv_launch_t;
 /* Enqueue `n` conv launches in order on `stream`; returns the first non-zero code. */

@@ -59,6 +59,10 @@ SIGNATURES = {
     "lss_conv2d_ks_s2_dual_packed_weight_bytes": (_sz, [_i, _i]),
     "lss_conv2d_pack_weights_ks_s2_dual": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "lss_conv2d_ks_s2_dual_fwd": (_i, [_vp] * 6 + [_i] * 6 + [_vp]),
+    "lss_conv2d_ks_stem_ok": (_i, [_i] * 5),
+    "lss_conv2d_ks_stem_packed_weight_bytes": (_sz, [_i, _i]),
+    "lss_conv2d_pack_weights_ks_stem": (_i, [_vp, _i, _i, _vp, _vp]),
+    "lss_conv2d_ks_stem_fwd": (_i, [_vp] * 5 + [_i] * 6 + [_vp]),
     "lss_gather_pack": (_i, [_vp, _i, _vp]),
     "lss_conv_bn_act_train_pack": (_i, [_vp] + [_i] * 8 + [_vp, _vp]),
     "lss_clip_adam_partials": (ctypes.c_longlong, [_vp, _i]),

@@ -667,10 +667,224 @@ int ks_s2_launch(const KsS2Plan& p, const KsS2Args& a, hipStream_t st) {
   return lss_launch_status();
 }
 
-// the diagnostic stamp buffer of tools/bench_ks.py --stamps (both kernels of this file), or null
+// the diagnostic stamp buffer of tools/bench_ks.py --stamps (every kernel of this file), or null
 unsigned long long* ks_stamps_from_env() {
   const char* e = getenv("LSS_KS_STAMPS");
   return e ? reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 16)) : nullptr;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Stem mode: BevEncode.conv1 - 64 -> Cout, 7x7 / stride 2 / pad 3 + folded BN + ReLU - as one pass.  K is exactly
+// 49 taps x 2 chunks of 32 channels = 98 k-steps (the phase-plane form on the tile kernel walks 4 x 16 = 64 (phase, tap)
+// positions per channel, 15 of them zeros).
+//   * workgroup = a TWO-DIMENSIONAL tile of 12 output rows x 16 output columns x 64 output channels (a 7-row halo of
+//     whole image rows does not fit LDS); every MFMA pixel tile is one 16-column row segment;
+//   * patch: 29 input rows x 37 input columns x 64 channels, filled once by LDS-DMA (zero page outside the image), the
+//     COLUMNS DE-INTERLEAVED BY PARITY: a patch row is [E: relative columns 0, 2, .. 36][O: 1, 3, .. 35] (pitch 37), so the B
+//     fragment of an output row segment at tap (ky, kx) is 16 consecutive positions: lane base 2 row pitch + n,
+//     wave-uniform tap offset ky pitch + (kx even ? kx / 2 : 19 + kx / 2).  Rows stay interleaved: a tile never mixes
+//     output rows, so 2 row + ky is an address, not a stride.  Cells as in the other modes ([chunk][16-channel half]
+//     [position][32 B]): the same conflict-free 1-KiB reads for every tap shift.  1 088 positions x 128 B = 136 KiB;
+//   * the weights (392 KiB per 64 output channels) stream: a rolling window of A fragments in registers, k-step s + 8
+//     requested while k-step s computes, straight from a pack that has this image;
+//   * work split 2 x 2, no reduction: wave (g, ph) owns channel tiles 2 g, 2 g + 1 and tile rows 6 ph .. 6 ph + 5 and
+//     walks the whole K: 6 ds_read_b128 and 2 x 1 KiB of weights for 12 MFMAs per k-step (0.5 KiB of LDS reads per MFMA,
+//     the ratio of the other modes; 2 KiB of weights per 12 MFMAs and wave = ~32 B / clk of the CU's 64-B L1 path).
+//     Every output element is one wave's sum in one fixed order: bit-reproducible;
+//   * epilogue straight from the accumulators: scale / shift / ReLU, 16-B stores of 8 consecutive channels.
+constexpr int ST_TH = 12, ST_TW = 16;                    // output tile
+constexpr int ST_PR = 2 * ST_TH + 5, ST_PW = 2 * ST_TW + 5;  // patch rows, row pitch in positions (29, 37)
+constexpr int ST_NE = ST_TW + 3;                         // even-column plane of a patch row (19), then the odd one (18)
+constexpr int ST_NPOSP = (ST_PR * ST_PW + 31) / 32 * 32; // 1 088
+constexpr int ST_LDS = 2 * ST_NPOSP * KS_POSB;           // 139 264 B
+constexpr int ST_KS = 98;                                // k-steps: S = tap * 2 + chunk
+constexpr int ST_WPRE = 8;                               // k-steps of weights in flight
+constexpr int ST_PXT = ST_TH / 2;                        // row segments per wave
+
+struct KsStemArgs {
+  const unsigned short* x;        // (B, H, W, 64) bf16 NHWC
+  const unsigned char* w;         // lss_conv2d_pack_weights_ks_stem
+  const float* scale;             // (Cout) folded BatchNorm (or null: 1)
+  const float* shift;             // (or null: 0)
+  unsigned short* y;              // (B, Ho, Wo, Cout) bf16 NHWC
+  int B, H, W, Cout, relu;
+  int Ho, Wo, nty, ntx, ncb;      // tiles per image (rows, columns), 64-channel output blocks
+  unsigned long long* stamps;     // as KsArgs
+};
+
+__global__ __launch_bounds__(256, 1) void conv_ks_stem_kernel(const KsStemArgs a) {
+  constexpr int PXT = ST_PXT, Cin = 64;
+  extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int g = wave & 1, ph = wave >> 1;       // channel half (32 of the 64), row half of the tile
+  const int n = lane & 15, kq = lane >> 4;
+  auto stamp = [&](int k) {
+    if (a.stamps != nullptr && tid == 0) a.stamps[(size_t)blockIdx.x * 8 + k] = __builtin_amdgcn_s_memrealtime();
+  };
+  stamp(0);
+  unsigned long long clk_main = 0;
+
+  int t;
+  {
+    const int nwg = gridDim.x, bid = blockIdx.x;
+    const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
+    t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  }
+  const int cb = t % a.ncb;
+  const int tg = t / a.ncb;
+  const int npi = a.nty * a.ntx;
+  const int b = tg / npi, ti = tg - b * npi;
+  const int ty = ti / a.ntx, tx = ti - ty * a.ntx;
+  const int oy0 = ty * ST_TH, ox0 = tx * ST_TW;
+  const int iy0 = 2 * oy0 - 3, ix0 = 2 * ox0 - 3;  // input row / column of patch row 0 / relative column 0
+
+  // ---- input patch -> LDS, columns de-interleaved: position (pr, pc) <- input (iy0 + pr, ix0 + (pc < 19 ? 2 pc : 2 (pc - 19) + 1))
+  {
+    constexpr int ppc = ST_NPOSP >> 4;
+    constexpr int q64 = 64 / ST_PW, r64 = 64 - q64 * ST_PW;
+    const int h = wave & 1;
+    const int pos0 = 32 * (wave >> 1) + (lane >> 1);
+    int pr = pos0 / ST_PW, pc = pos0 - pr * ST_PW;
+    const unsigned char* zsrc = lss_ks_zero_page + (lane & 7) * 16;
+    const unsigned short* xb = a.x + (size_t)b * a.H * a.W * Cin + (2 * h + (lane & 1)) * 8;
+    for (int i = wave; i < ppc; i += 4) {
+      const int iy = iy0 + pr, ix = ix0 + (pc < ST_NE ? 2 * pc : 2 * (pc - ST_NE) + 1);
+      const bool in = pr < ST_PR && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
+      const unsigned short* src = xb + (in ? (iy * a.W + ix) * Cin : 0);
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+        ks_glds16(in ? (const void*)(src + c * 32) : (const void*)zsrc,
+                  smem + ((size_t)(c * 2 + h) * ST_NPOSP + 32 * (i >> 1)) * 32);
+      pr += q64; pc += r64;
+      if (pc >= ST_PW) { pc -= ST_PW; ++pr; }
+    }
+  }
+
+  // ---- weights: the first ST_WPRE k-steps of this wave's two channel tiles; the window never closes ----
+  bf16x8 wf[ST_KS][2];
+  const unsigned char* wp = a.w + ((size_t)cb * ST_KS * 4 + 2 * g) * 1024 + lane * 16;
+  auto load_w = [&](int s) {
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) wf[s][ct] = *reinterpret_cast<const bf16x8*>(wp + (s * 4 + ct) * 1024);
+  };
+#pragma unroll
+  for (int s = 0; s < ST_WPRE; ++s) load_w(s);
+
+  // lane base of row segment 0 of this wave; segment j adds 2 j pitch positions, tap (ky, kx) its wave-uniform offset
+  const int ab0 = (2 * (ph * PXT) * ST_PW + n) * 32 + (kq >> 1) * ST_NPOSP * 32 + (kq & 1) * 16;
+  stamp(1);
+  f32x4 acc[PXT][2];
+#pragma unroll
+  for (int j = 0; j < PXT; ++j) {
+    acc[j][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    acc[j][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  }
+  // epilogue constants of this lane's 8 consecutive channels, requested with everything else
+  const int ch = cb * 64 + g * 32 + kq * 8;
+  float sc[8], sh[8];
+  {
+    f32x4 s0 = {1.f, 1.f, 1.f, 1.f}, s1 = s0, h0 = {0.f, 0.f, 0.f, 0.f}, h1 = h0;
+    if (a.scale) { s0 = *reinterpret_cast<const f32x4*>(a.scale + ch); s1 = *reinterpret_cast<const f32x4*>(a.scale + ch + 4); }
+    if (a.shift) { h0 = *reinterpret_cast<const f32x4*>(a.shift + ch); h1 = *reinterpret_cast<const f32x4*>(a.shift + ch + 4); }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { sc[i] = s0[i]; sc[4 + i] = s1[i]; sh[i] = h0[i]; sh[4 + i] = h1[i]; }
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the patch pieces have landed
+  __syncthreads();
+  stamp(2);
+
+  // ---- main phase: 98 k-steps x 6 row segments x 2 channel tiles, LDS reads, weight requests and MFMAs only ----
+  bf16x8 fb[2][PXT];
+  auto load_frags = [&](int buf, int s) {
+    const int tap = s >> 1, ky = tap / 7, kx = tap % 7;
+    const int toff = (ky * ST_PW + ((kx & 1) ? ST_NE + (kx >> 1) : (kx >> 1))) * 32;
+    const unsigned char* cbase = smem + (size_t)(s & 1) * 2 * ST_NPOSP * 32 + ab0 + toff;
+#pragma unroll
+    for (int j = 0; j < PXT; ++j) fb[buf][j] = *reinterpret_cast<const bf16x8*>(cbase + j * (2 * ST_PW * 32));
+  };
+  if (a.stamps != nullptr) clk_main = __builtin_amdgcn_s_memtime();
+  load_frags(0, 0);
+#pragma unroll
+  for (int s = 0; s < ST_KS; ++s) {
+    if (s + ST_WPRE < ST_KS) load_w(s + ST_WPRE);
+    if (s + 1 < ST_KS) load_frags((s + 1) & 1, s + 1);
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int j = 0; j < PXT; ++j) {
+      acc[j][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s][0], fb[s & 1][j], acc[j][0], 0, 0, 0);
+      acc[j][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s][1], fb[s & 1][j], acc[j][1], 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  if (a.stamps != nullptr) asm volatile("s_nop 0" ::"v"(acc[0][0]), "v"(acc[PXT - 1][1]));  // the MFMA chain has retired
+  stamp(3);
+  if (a.stamps != nullptr && tid == 0) a.stamps[(size_t)blockIdx.x * 8 + 7] = __builtin_amdgcn_s_memtime() - clk_main;
+  stamp(4);  // (no K parts to meet)
+
+  // ---- epilogue: lane (kq, n) holds channels ch .. ch + 7 of pixel (oy0 + 6 ph + j, ox0 + n) ----
+  const int ox = ox0 + n;
+#pragma unroll
+  for (int j = 0; j < PXT; ++j) {
+    const int oy = oy0 + ph * PXT + j;
+    float v[8];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { v[i] = acc[j][0][i]; v[4 + i] = acc[j][1][i]; }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      v[i] = v[i] * sc[i] + sh[i];
+      if (a.relu) v[i] = fmaxf(v[i], 0.f);
+    }
+    if (oy < a.Ho && ox < a.Wo) {
+      typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+      const u32x4 ov = {lss_pack_bf2(v[0], v[1]), lss_pack_bf2(v[2], v[3]), lss_pack_bf2(v[4], v[5]), lss_pack_bf2(v[6], v[7])};
+      *reinterpret_cast<u32x4*>(a.y + (((size_t)b * a.Ho + oy) * a.Wo + ox) * a.Cout + ch) = ov;
+    }
+  }
+  if (a.stamps != nullptr) {
+    stamp(5);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    stamp(6);
+  }
+}
+
+// w (Cout, 64, 7, 7) fp32 -> the stem kernel's register image, bf16: [co block of 64][k-step S = tap * 2 + chunk]
+// [channel tile ct][lane][8]; A-fragment lane (kq, m) of tile ct holds
+// W[co = cb 64 + 32 (ct >> 1) + 8 (m >> 2) + 4 (ct & 1) + (m & 3)][ci = 32 chunk + 8 kq .. + 8][tap = ky 7 + kx]
+__global__ void pack_weights_ks_stem_kernel(const float* __restrict__ w, int Cout, unsigned short* __restrict__ out) {
+  const size_t ntot = (size_t)Cout * 64 * 49;
+  for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < ntot; e += (size_t)gridDim.x * 256) {
+    const int j = e & 7;
+    size_t r = e >> 3;
+    const int l = r & 63; r >>= 6;
+    const int ct = r & 3; r >>= 2;
+    const int S = r % ST_KS;
+    const int cb = r / ST_KS;
+    const int m = l & 15, kq = l >> 4;
+    const int co = cb * 64 + 32 * (ct >> 1) + 8 * (m >> 2) + 4 * (ct & 1) + (m & 3);
+    const int ci = (S & 1) * 32 + kq * 8 + j;
+    out[e] = lss_f2bf(w[((size_t)co * 64 + ci) * 49 + (S >> 1)]);
+  }
+}
+
+struct KsStemPlan {
+  int ok, Ho, Wo, nty, ntx, ncb, grid;
+};
+
+KsStemPlan ks_stem_plan(int B, int H, int W, int Cin, int Cout) {
+  KsStemPlan p = {};
+  if (B <= 0 || H <= 0 || W <= 0 || Cin != 64 || Cout <= 0 || Cout % 64 != 0) return p;
+  p.Ho = (H - 1) / 2 + 1; p.Wo = (W - 1) / 2 + 1;
+  if (p.Ho < ST_TH || p.Wo < ST_TW) return p;          // at least one whole tile
+  p.nty = (p.Ho + ST_TH - 1) / ST_TH; p.ntx = (p.Wo + ST_TW - 1) / ST_TW;
+  p.ncb = Cout / 64;
+  const long long grid = (long long)B * p.nty * p.ntx * p.ncb;
+  // one workgroup per CU in ONE round; below 32 workgroups the tile kernel's smaller tiles spread wider
+  if (grid < 32 || grid > 256) return p;
+  if ((long long)B * H * W * Cin >= (1LL << 30) || (long long)B * p.Ho * p.Wo * Cout >= (1LL << 30)) return p;
+  p.grid = (int)grid;
+  p.ok = 1;
+  return p;
 }
 
 }  // namespace
@@ -779,4 +993,57 @@ extern "C" int lss_conv2d_ks_s2_dual_fwd(const void* x, const void* w_packed, co
   a.PB = p.PB; a.npb = p.npb; a.nposp = p.nposp; a.ncb = p.ncb;
   a.stamps = ks_stamps_from_env();
   return p.nkw == 4 ? ks_s2_launch<4>(p, a, lss_stream(stream)) : ks_s2_launch<2>(p, a, lss_stream(stream));
+}
+
+// Stem mode (7x7 / stride 2 / pad 3, Cin 64, one launch): is (shape) a case?  bf16, Cout a multiple of 64, at least one
+// 12 x 16 tile of outputs, and a grid of 32-256 workgroups (one round; the hires workload's 442 stay on the tile kernel).
+extern "C" int lss_conv2d_ks_stem_ok(int B, int H, int W, int Cin, int Cout) {
+  if (const char* e = getenv("LSS_CONV_KS"))
+    if (atoi(e) == 0) return 0;
+  return ks_stem_plan(B, H, W, Cin, Cout).ok;
+}
+
+extern "C" size_t lss_conv2d_ks_stem_packed_weight_bytes(int Cout, int Cin) {
+  if (Cout <= 0 || Cout % 64 != 0 || Cin != 64) return 0;
+  return (size_t)Cout * Cin * 49 * 2;
+}
+
+extern "C" int lss_conv2d_pack_weights_ks_stem(const float* w_oihw, int Cout, int Cin, void* w_packed, void* stream) {
+  LSS_CHECK_PTR(w_oihw); LSS_CHECK_PTR(w_packed);
+  if (lss_conv2d_ks_stem_packed_weight_bytes(Cout, Cin) == 0) return LSS_E_SHAPE;
+  const size_t n = (size_t)Cout * Cin * 49;
+  const int grid = (int)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
+  hipLaunchKernelGGL(pack_weights_ks_stem_kernel, dim3(grid), dim3(256), 0, lss_stream(stream), w_oihw, Cout,
+                     reinterpret_cast<unsigned short*>(w_packed));
+  return lss_launch_status();
+}
+
+extern "C" int lss_conv2d_ks_stem_fwd(const void* x, const void* w_packed, const float* scale, const float* shift,
+                                      void* y, int B, int H, int W, int Cin, int Cout, int relu, void* stream) {
+  LSS_CHECK_PTR(x); LSS_CHECK_PTR(w_packed); LSS_CHECK_PTR(y);
+  const KsStemPlan p = ks_stem_plan(B, H, W, Cin, Cout);
+  if (!p.ok) return LSS_E_SHAPE;
+  if (relu != 0 && relu != 1) return LSS_E_LAYOUT;
+  if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(w_packed) |
+        reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(shift)) & 15) != 0)
+    return LSS_E_ALIGN;
+  KsStemArgs a;
+  a.x = reinterpret_cast<const unsigned short*>(x);
+  a.w = reinterpret_cast<const unsigned char*>(w_packed);
+  a.scale = scale; a.shift = shift;
+  a.y = reinterpret_cast<unsigned short*>(y);
+  a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.relu = relu;
+  a.Ho = p.Ho; a.Wo = p.Wo; a.nty = p.nty; a.ntx = p.ntx; a.ncb = p.ncb;
+  a.stamps = ks_stamps_from_env();
+  static bool attr_set[64] = {};
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
+  if (dev < 0 || !attr_set[dev]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_ks_stem_kernel),
+                                       hipFuncAttributeMaxDynamicSharedMemorySize, KS_LDS_MAX);
+    if (e != hipSuccess) return (int)e;
+    if (dev >= 0) attr_set[dev] = true;
+  }
+  hipLaunchKernelGGL(conv_ks_stem_kernel, dim3(p.grid), dim3(256), ST_LDS, lss_stream(stream), a);
+  return lss_launch_status();
 }

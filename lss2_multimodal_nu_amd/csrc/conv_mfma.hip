@@ -1461,6 +1461,8 @@ extern "C" int lss_conv2d_sequence(const lss_conv_launch_t* L, int n, void* stre
                                   c.pad, c.relu, stream);
     else if (c.kind == 4)
       rc = lss_conv2d_ks_s2_dual_fwd(c.x, c.w, c.scale, c.shift, c.y, c.y2, c.B, c.H, c.W, c.Cx, c.Cout, c.relu, stream);
+    else if (c.kind == 5)
+      rc = lss_conv2d_ks_stem_fwd(c.x, c.w, c.scale, c.shift, c.y, c.B, c.H, c.W, c.Cx, c.Cout, c.relu, stream);
     else
       rc = LSS_E_LAYOUT;
     if (rc != 0) return rc;

@@ -560,6 +560,27 @@ class _FoldedConv:
         self.w = self.scale = self.shift = None
         self.w_ring, self.ring_key = None, None
         self.w_ks, self.ks_key = None, None
+        self.w_stem, self.stem_key = None, None
+
+    def stem(self, dt):
+        """The 7x7 weights in the layout of the K-split kernel's stem mode, cached under the key of the s2d pack (which
+        the fallback keeps); `get(dt)` must have been called for the current key."""
+        if self.stem_key != self.key:
+            with torch.no_grad():
+                self.w_stem = ops.pack_conv_weight_ks_stem(self.conv.weight.detach().float().contiguous())
+            self.stem_key = self.key
+        return self.w_stem
+
+    def stem_case(self, x, dt, residual=None, x2=None, up=1):
+        """Does this call go to the stem mode of the K-split one-pass kernel?  7x7 / stride 2 / pad 3, bf16, nothing fused,
+        and a shape `lss_conv2d_ks_stem_ok` accepts (LSS_CONV_KS=0 refuses all); LSS_NO_STEM_KS switches only this off."""
+        c = self.conv
+        if (dt != ops.DT_BF16 or residual is not None or x2 is not None or up != 1 or c.kernel_size != (7, 7)
+                or c.stride != (2, 2) or c.padding != (3, 3) or not self.pack or self.pad_in is not None
+                or os.environ.get("LSS_NO_STEM_KS") is not None):
+            return False
+        B, H, W, Cx = x.shape
+        return ops.conv_ks_stem_ok(B, H, W, Cx, c.out_channels)
 
     def ks(self, dt):
         """The same weights in the K-split one-pass kernel's layout (csrc/conv_ks.hip), packed on first use and
@@ -654,6 +675,8 @@ class _FoldedConv:
     def run(self, x, dt, relu, residual=None, x2=None, up=1):
         w, scale, shift = self.get(dt)
         c = self.conv
+        if relu in (False, True) and self.stem_case(x, dt, residual, x2, up):   # one pass, K = 49 Cin (csrc/conv_ks.hip)
+            return ops.conv2d_ks_stem_nhwc(x, self.stem(dt), scale, shift, relu=relu)
         if self._s2d(dt) and x2 is None and up == 1:
             return ops.conv2d_s2_nhwc(x, w, c.kernel_size[0], c.padding[0], scale, shift, residual, relu)
         if relu in (False, True) and self.ks_case(x, dt, x2, up):

@@ -1414,6 +1414,48 @@ def conv2d_ks_s2_dual_nhwc(x, w_ks, scale=None, shift=None, relu=True, tag="conv
     return y, y2
 
 
+def conv_ks_stem_ok(B, H, W, Cin, Cout):
+    """Is this 7x7 / stride 2 / pad 3 conv (bf16, Cin 64) a case for the stem mode of the K-split one-pass kernel
+    (lss_conv2d_ks_stem_ok)?"""
+    return bool(N.lib().lss_conv2d_ks_stem_ok(B, H, W, Cin, Cout))
+
+
+def pack_conv_weight_ks_stem(w_oihw):
+    """(Cout, 64, 7, 7) fp32 -> KsWeight in the stem layout of the K-split kernel."""
+    Cout, Cin, KH, KW = w_oihw.shape
+    _f32c(w_oihw, "conv weight")
+    nbytes = N.lib().lss_conv2d_ks_stem_packed_weight_bytes(Cout, Cin)
+    if (KH, KW) != (7, 7) or nbytes == 0:
+        raise ValueError("KS stem weights: 7x7, Cout %% 64 == 0, Cin 64 (got %s)" % (tuple(w_oihw.shape),))
+    out = torch.empty(nbytes // 2, dtype=torch.bfloat16, device=w_oihw.device)
+    N.check(N.lib().lss_conv2d_pack_weights_ks_stem(N.ptr(w_oihw), Cout, Cin, N.ptr(out), N.stream()),
+            "lss_conv2d_pack_weights_ks_stem")
+    return KsWeight(out, Cout, Cin)
+
+
+def conv2d_ks_stem_nhwc(x, w_ks, scale=None, shift=None, relu=True, tag="conv2d_fwd"):
+    """act(scale * conv7x7/2/pad3(x, w) + shift) on the stem mode of the K-split one-pass kernel: x (B, H, W, 64) bf16
+    NHWC, w_ks from pack_conv_weight_ks_stem, scale / shift (Cout) fp32 or None.  Returns (B, Ho, Wo, Cout) bf16."""
+    B, H, W, Cx = x.shape
+    if x.dtype != torch.bfloat16 or not x.is_contiguous() or not isinstance(w_ks, KsWeight) or w_ks.Cin != Cx \
+            or w_ks.data.numel() != w_ks.Cout * Cx * 49:
+        raise ValueError("conv2d_ks_stem_nhwc operands must be contiguous bf16 with stem KS-packed weights")
+    Cout = w_ks.Cout
+    for name, t in (("scale", scale), ("shift", shift)):
+        if t is not None:
+            _f32c(t, name, (Cout,))
+    Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    y = torch.empty(B, Ho, Wo, Cout, dtype=torch.bfloat16, device=x.device)
+    if _recorder is not None:
+        _recorder.add(5, (x, w_ks.data, scale, shift, y), x=x, w=w_ks.data, scale=scale, shift=shift, y=y,
+                      B=B, H=H, W=W, Cx=Cx, Cout=Cout, KH=7, KW=7, stride=2, pad=3, relu=1 if relu else 0, dt=DT_BF16)
+    with _timed(tag):
+        N.check(N.lib().lss_conv2d_ks_stem_fwd(N.ptr(x), N.ptr(w_ks.data), N.ptr(scale), N.ptr(shift), N.ptr(y),
+                                               B, H, W, Cx, Cout, 1 if relu else 0, N.stream()),
+                "lss_conv2d_ks_stem_fwd")
+    return y
+
+
 def conv3x3_head_nchw(x, w_packed, scale, shift, head_w, head_b, x2=None, up=1, relu=True, tag="conv2d_fwd"):
     """3x3/s1/p1 conv (+fused upsample/concat) + scale/shift + ReLU + 1x1 head in one launch.
     x (B,H,W,Cx) bf16 NHWC; head_w (n,Cout) fp32, Cout = 128 (64: plain 3x3 only); returns (B, n, H*up, W*up)

@@ -1,0 +1,210 @@
+"""K8k stem mode (csrc/conv_ks.hip: conv_ks_stem_kernel): BevEncode's 7x7 / stride 2 / pad 3 stem + folded BN + ReLU (ref
+src/modules.py:96-98, 120-122) as one launch of the one-pass K-split kernel.  Against torch's CPU conv on the same
+bf16-rounded operands, with the tile kernel's own error on the same tensors as the bound; against the tile kernel
+directly; bit-reproducibility; zero padding; refusals; the module-level switches; the recorded BevEncode plan.
+
+Error bound: K is 49 x 64 = 3 136 deep.  Both kernels accumulate in fp32 and round once to bf16 (2^-9 relative), which
+dominates both errors; only the fp32 summation order differs.  So the new kernel's max-abs and rel-L2 error against the
+CPU reference must be <= 1.05 x the tile kernel's (`ops.conv2d_s2_nhwc`), measured here on the same tensors."""
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def ops():
+    assert torch.cuda.is_available()
+    from lss2_multimodal_nu_amd import ops as _ops
+    return _ops
+
+
+def _q(t):
+    return t.bfloat16().float()
+
+
+SHAPES = [
+    # B, H, W, Cout, folded BN, ReLU
+    (4, 200, 200, 64, True, True),     # the benched stem: 9 x 7 tiles per image (rows 100 = 8 x 12 + 4, columns 6 x 16 + 4)
+    (1, 200, 200, 64, True, True),     # batch 1: 63 workgroups
+    (4, 199, 197, 64, True, True),     # odd H and W: the last input row / odd-plane column come from the zero page
+    (4, 200, 200, 64, False, False),   # no scale / shift, no ReLU
+    (4, 200, 200, 64, True, False),    # affine without ReLU
+    (3, 150, 170, 64, False, True),    # 75 x 85 outputs: ragged last tiles in both directions (3 rows, 5 columns)
+    (32, 23, 31, 64, True, True),      # the smallest: one whole tile per image, 32 workgroups
+    (4, 192, 256, 64, True, True),     # the largest grid: 4 x 8 x 8 = 256 workgroups, exact tiles
+    (2, 177, 221, 128, True, True),    # two 64-channel blocks, odd sizes: 2 x 8 x 7 x 2 = 224
+]
+
+
+def _case(cfg):
+    B, H, W, Cout, bn, relu = cfg
+    gen = torch.Generator().manual_seed(sum(int(c) for c in cfg))
+    x = _q(torch.randn(B, 64, H, W, generator=gen))
+    w = _q(torch.randn(Cout, 64, 7, 7, generator=gen) * (64 * 49) ** -0.5)
+    scale = (torch.rand(Cout, generator=gen) + 0.5) if bn else None
+    shift = (torch.randn(Cout, generator=gen) * 0.1) if bn else None
+    ref = torch.nn.functional.conv2d(x, w, None, stride=2, padding=3)
+    if bn:
+        ref = ref * scale.view(1, -1, 1, 1) + shift.view(1, -1, 1, 1)
+    if relu:
+        ref = ref.relu()
+    return x, w, scale, shift, ref
+
+
+@pytest.mark.parametrize("cfg", SHAPES)
+def test_ks_stem_vs_torch_with_the_tile_kernels_error_as_bound(ops, report, cfg):
+    B, H, W, Cout, bn, relu = cfg
+    assert ops.conv_ks_stem_ok(B, H, W, 64, Cout), "test shape must be a case for the stem mode"
+    x, w, scale, shift, ref = _case(cfg)
+    xg = ops.nchw_to_nhwc(x.cuda(), 1)
+    sg, hg = (scale.cuda(), shift.cuda()) if bn else (None, None)
+    wk = ops.pack_conv_weight_ks_stem(w.cuda())
+    y = [ops.conv2d_ks_stem_nhwc(xg, wk, sg, hg, relu=relu) for _ in range(3)]
+    old = ops.conv2d_s2_nhwc(xg, ops.pack_conv_weight_s2d(w.cuda(), 3), 7, 3, sg, hg, None, relu)
+    torch.cuda.synchronize()
+    assert torch.equal(y[0], y[1]) and torch.equal(y[0], y[2])   # one wave, one fixed order: bit-reproducible
+    new_o, old_o = ops.nhwc_to_nchw(y[0], 1).cpu(), ops.nhwc_to_nchw(old, 1).cpu()
+    assert new_o.shape == ref.shape == old_o.shape
+    tag = "x".join(str(int(c)) for c in cfg)
+    e_new = ((new_o - ref).abs().max(), (new_o - ref).norm() / ref.norm())
+    e_old = ((old_o - ref).abs().max(), (old_o - ref).norm() / ref.norm())
+    vs = report("k8k_stem_vs_tile_rel_l2_%s" % tag, (new_o - old_o).norm() / old_o.norm())
+    for nm, a, b in (("max_abs", e_new[0], e_old[0]), ("rel_l2", e_new[1], e_old[1])):
+        report("k8k_stem_%s_new_%s" % (nm, tag), a)
+        report("k8k_stem_%s_tile_%s" % (nm, tag), b)
+    print("%s: max-abs new %.4e tile %.4e | rel-L2 new %.4e tile %.4e | new vs tile rel-L2 %.3e"
+          % (tag, e_new[0], e_old[0], e_new[1], e_old[1], vs))
+    assert float(e_new[0]) <= 1.05 * float(e_old[0])
+    assert float(e_new[1]) <= 1.05 * float(e_old[1])
+    if relu:
+        assert float(new_o.min()) >= 0
+    else:
+        assert float(new_o.min()) < 0
+
+
+def test_padding_is_zero(ops):
+    """x = 1024 everywhere, every weight 2^-10: an output is 64 x (the number of its taps inside the image), exactly
+    representable in bf16.  A patch piece read from outside the image instead of the zero page would see 1024 too."""
+    B, H, W = 4, 61, 75                                   # odd both ways: 31 x 38 outputs, 4 x 3 x 3 = 36 workgroups
+    assert ops.conv_ks_stem_ok(B, H, W, 64, 64)
+    x = torch.full((B, H, W, 64), 1024.0, device="cuda").bfloat16()
+    wk = ops.pack_conv_weight_ks_stem(torch.full((64, 64, 7, 7), 2.0 ** -10, device="cuda"))
+    y = ops.conv2d_ks_stem_nhwc(x, wk, None, None, relu=False).float().cpu()
+    Ho, Wo = 31, 38
+    ny = torch.tensor([sum(0 <= 2 * o + k - 3 < H for k in range(7)) for o in range(Ho)], dtype=torch.float32)
+    nx = torch.tensor([sum(0 <= 2 * o + k - 3 < W for k in range(7)) for o in range(Wo)], dtype=torch.float32)
+    want = (64.0 * ny.view(Ho, 1) * nx.view(1, Wo)).view(1, Ho, Wo, 1).expand(B, Ho, Wo, 64)
+    assert float(want.min()) == 64.0 * 4 * 4 and float(want.max()) == 64.0 * 49
+    assert torch.equal(y, want)
+
+
+REFUSED = [
+    (2, 400, 400, 64, 64),    # the hires workload: 442 workgroups, a second round
+    (4, 200, 200, 128, 64),   # Cin 128
+    (4, 200, 200, 64, 96),    # Cout not a multiple of 64
+    (32, 21, 31, 64, 64),     # 11 output rows: below the tile
+    (1, 100, 100, 64, 64),    # 20 workgroups: under the plan's 32
+]
+
+
+@pytest.mark.parametrize("shape", REFUSED)
+def test_ks_stem_refuses_shapes_outside_its_plan(ops, shape):
+    """An argument error from the C entry, not a silent fallback inside it."""
+    from lss2_multimodal_nu_amd import _native as N
+    B, H, W, Cin, Cout = shape
+    assert not ops.conv_ks_stem_ok(B, H, W, Cin, Cout)
+    x = torch.zeros(B, H, W, Cin, device="cuda").bfloat16()
+    y = torch.zeros(B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, Cout, device="cuda").bfloat16()
+    w = torch.zeros(Cout * Cin * 49, device="cuda").bfloat16()
+    rc = N.lib().lss_conv2d_ks_stem_fwd(N.ptr(x), N.ptr(w), None, None, N.ptr(y), B, H, W, Cin, Cout, 1, N.stream())
+    assert rc == -2   # LSS_E_SHAPE
+    torch.cuda.synchronize()
+
+
+def _bevencode(seed=3):
+    import lss2_multimodal_nu_amd as L
+    torch.manual_seed(seed)
+    be = L.BevEncode(64, 4, precision="bf16")
+    with torch.no_grad():
+        for m in be.modules():
+            if isinstance(m, torch.nn.BatchNorm2d):
+                m.weight.uniform_(0.5, 1.5)
+                m.bias.normal_(0, 0.1)
+                m.running_mean.normal_(0, 0.1)
+                m.running_var.uniform_(0.5, 1.5)
+    return be.cuda().eval()
+
+
+def test_bevencode_switches_and_refused_shape_give_the_parent_paths_bits(ops, monkeypatch):
+    """BevEncode's stem takes the new launch (recorded kind 5) on the benched shape; with LSS_NO_STEM_KS, with
+    LSS_CONV_KS=0 and on a shape the plan refuses it is the tile kernel's launch (kind 1) and the whole network's output
+    equals, byte for byte, the one computed with the stem forced onto `ops.conv2d_s2_nhwc`."""
+    monkeypatch.delenv("LSS_CONV_KS", raising=False)
+    monkeypatch.delenv("LSS_NO_STEM_KS", raising=False)
+    be = _bevencode()
+
+    def run(x, force_tile=False):
+        rec = ops.ConvRecorder()
+        ops.set_recorder(rec)
+        saved = be._stem.stem_case
+        if force_tile:
+            be._stem.stem_case = lambda *a, **k: False
+        try:
+            with torch.no_grad():
+                y = be._forward_nhwc(x, ops.DT_BF16)
+        finally:
+            ops.set_recorder(None)
+            be._stem.stem_case = saved
+        torch.cuda.synchronize()
+        return y, [k for k, _ in rec.launches]
+
+    x = torch.randn(4, 200, 200, 64, device="cuda").bfloat16()
+    y_new, kinds = run(x)
+    assert kinds[0] == 5 and kinds.count(4) == 2 and len(kinds) == 16
+    y_tile, kinds = run(x, force_tile=True)
+    assert kinds[0] == 1 and kinds.count(4) == 2 and len(kinds) == 16
+    e = float((y_new - y_tile).norm() / y_tile.norm())
+    print("BevEncode @ 4 x 200 x 200, stem on the new kernel vs on the tile kernel: rel-L2 %.3e" % e)
+    assert e <= 2e-2   # tests/test_bench_config_gpu.py's bound on the whole bf16 network
+    monkeypatch.setenv("LSS_NO_STEM_KS", "1")
+    y_sw, kinds = run(x)
+    assert kinds[0] == 1 and kinds.count(4) == 2 and torch.equal(y_sw, y_tile)
+    # the stem alone under the switch: the tile kernel's bits
+    w, scale, shift = be._stem.get(ops.DT_BF16)
+    with torch.no_grad():
+        assert torch.equal(be._stem.run(x, ops.DT_BF16, relu=True), ops.conv2d_s2_nhwc(x, w, 7, 3, scale, shift, None, True))
+    monkeypatch.delenv("LSS_NO_STEM_KS")
+    monkeypatch.setenv("LSS_CONV_KS", "0")
+    y_off, kinds = run(x)
+    assert kinds[0] == 1 and 4 not in kinds and 5 not in kinds
+    y_off2, kinds2 = run(x, force_tile=True)
+    assert kinds2 == kinds and torch.equal(y_off, y_off2)
+    with torch.no_grad():
+        assert torch.equal(be._stem.run(x, ops.DT_BF16, relu=True), ops.conv2d_s2_nhwc(x, w, 7, 3, scale, shift, None, True))
+    monkeypatch.delenv("LSS_CONV_KS")
+    # refused shape: 1 x 96 x 96 -> 4 x 3 = 12 workgroups (a size the x4 upsample path of the network accepts)
+    xs = torch.randn(1, 96, 96, 64, device="cuda").bfloat16()
+    assert not ops.conv_ks_stem_ok(1, 96, 96, 64, 64)
+    y_a, kinds = run(xs)
+    y_b, kinds_b = run(xs, force_tile=True)
+    assert kinds[0] == 1 and kinds == kinds_b and torch.equal(y_a, y_b)
+
+
+def test_bevencode_plan_replays_the_stem_launch(ops, monkeypatch):
+    """BevEncode at the benched shape: 16 recorded launches, the first of kind 5, two of kind 4; the replay equals the
+    recording (eager) pass byte for byte; no bounded wait was hit."""
+    monkeypatch.delenv("LSS_CONV_KS", raising=False)
+    monkeypatch.delenv("LSS_NO_STEM_KS", raising=False)
+    be = _bevencode()
+    x = torch.randn(4, 200, 200, 64, device="cuda").bfloat16()
+    with torch.no_grad():
+        a = be.forward_nhwc(x, ops.DT_BF16)
+        b = be.forward_nhwc(x, ops.DT_BF16)
+        c = be.forward_nhwc(x, ops.DT_BF16)
+    torch.cuda.synchronize()
+    (plan, _), = be._plans.values()
+    kinds = [int(plan.arr[i].kind) for i in range(plan.n)]
+    assert plan.n == 16 and kinds[0] == 5 and kinds.count(5) == 1 and kinds.count(4) == 2 and 3 not in kinds and 1 not in kinds
+    assert torch.equal(a, b) and torch.equal(a, c)
+    assert all(v == 0 for v in ops.timeout_counters().values())

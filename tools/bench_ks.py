@@ -31,6 +31,63 @@ def _s2_operands(B, H, W, Cin, Cout):
     return x, wcat, ops.pack_conv_weight_ks_s2_dual(w1, wd), sc, sh
 
 
+STEM = ("stem 7x7/2 64->64 @200", 4, 200, 200, 64)
+
+
+def _stem_operands(B, H, W, Cout):
+    x = torch.randn(B, H, W, 64, device="cuda").bfloat16()
+    w = torch.randn(Cout, 64, 7, 7, device="cuda") * (64 * 49) ** -0.5
+    sc, sh = torch.rand(Cout, device="cuda") + 0.5, torch.randn(Cout, device="cuda") * 0.1
+    return x, ops.pack_conv_weight_s2d(w, 3), ops.pack_conv_weight_ks_stem(w), sc, sh
+
+
+def stamps_stem():
+    """Stem mode: no reduce phase (slot 4 = slot 3); 98 k-steps x 12 = 1 176 MFMAs per wave.  L2 -> CU bytes per
+    workgroup, from the layout: patch 1 088 positions x 128 B = 136 KiB + weights 392 KiB requested by two waves each."""
+    name, B, H, W, Cout = STEM
+    x, _, wk, sc, sh = _stem_operands(B, H, W, Cout)
+    for _ in range(5):
+        ops.conv2d_ks_stem_nhwc(x, wk, sc, sh)
+    buf = torch.zeros(1024 * 8, dtype=torch.int64, device="cuda")
+    os.environ["LSS_KS_STAMPS"] = "%x" % buf.data_ptr()
+    torch.cuda.synchronize()
+    ops.conv2d_ks_stem_nhwc(x, wk, sc, sh)
+    torch.cuda.synchronize()
+    del os.environ["LSS_KS_STAMPS"]
+    _print_stamps(name, buf, 1176.0)
+
+
+def bench_stem(rounds, chain):
+    """Per-launch time of the stem on the tile kernel (phase-plane form) and on the stem mode: `chain` launches over the
+    same input inside one recorded list."""
+    name, B, H, W, Cout = STEM
+    x, ws2d, wk, sc, sh = _stem_operands(B, H, W, Cout)
+    plans, res = [], {}
+    for tag in ("tile", "ks"):
+        rec = ops.ConvRecorder()
+        ops.set_recorder(rec)
+        for _ in range(chain):
+            y = ops.conv2d_s2_nhwc(x, ws2d, 7, 3, sc, sh, None, True) if tag == "tile" else \
+                ops.conv2d_ks_stem_nhwc(x, wk, sc, sh)
+        ops.set_recorder(None)
+        plans.append((tag, ops.ConvPlan(rec, x, y), y))
+    for _ in range(3):
+        for tag, plan, y in plans:
+            plan.run(x, y)
+    torch.cuda.synchronize()
+    for _ in range(rounds):
+        for tag, plan, y in plans:
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            plan.run(x, y)
+            e.record()
+            torch.cuda.synchronize()
+            res.setdefault(tag, []).append(s.elapsed_time(e) * 1e3 / chain)
+    t, k = sorted(res["tile"]), sorted(res["ks"])
+    print("%-22s tile %5.2f us (min %6.2f)   ks %6.2f us (min %6.2f)   per launch incl. its boundary"
+          % (name, t[len(t) // 2], t[0], k[len(k) // 2], k[0]))
+
+
 def _print_stamps(name, buf, n_mfma):
     import numpy as np
     t = buf.view(-1, 8).cpu().numpy().astype(np.float64) * 0.01
@@ -120,6 +177,7 @@ def stamps():
         print("%-22s        main phase: %.0f s_memtime ticks (median) = %.1f per MFMA of a wave; ticks per us of s_memrealtime %.0f"
               % ("", np.median(clk), np.median(clk) / 180.0, np.median(clk / np.maximum(t[:, 3] - t[:, 2], 1e-3))))
     stamps_s2()
+    stamps_stem()
 
 
 def main():
@@ -163,6 +221,7 @@ def main():
         print("%-22s tile %6.2f us (min %6.2f)   ks %6.2f us (min %6.2f)   per launch incl. its boundary"
               % (name, t[len(t) // 2], t[0], k[len(k) // 2], k[0]))
     bench_s2(a.rounds, a.chain)
+    bench_stem(a.rounds, a.chain)
 
 
 if __name__ == "__main__":
