@@ -282,6 +282,36 @@ int lss_deform_attn_bwd(const float* value, const float* offsets_logits, const f
  * (samples are reduced one after another); 0 if a size is <= 0 */
 size_t lss_deform_attn_bwd_workspace_bytes(int B, int H, int W);
 
+/* ---------------------------------------------------------------------------
+ * K10  backward of a pointwise (1x1) conv  y[b, m, p] = sum_k w[m, k] x[b, k, p] + bias[m]:
+ *        dx[b, k, p] = sum_m w[m, k] g[b, m, p]
+ *        dw[m, k]    = sum_b sum_p g[b, m, p] x[b, k, p]
+ *        db[m]       = sum_b sum_p g[b, m, p]
+ * replaces: the ConvolutionBackward of src/model_vovnet_transformer.py:31,39 (MultiScaleDepthNet's 1x1 convs),
+ *           :82 (StandardDepthNet's), :97 (CamEncodeV2.feat_proj) and of src/modules.py:83 (CamEncode.depthnet).
+ *   g          output gradient, fp32 channel-major: element (b, m, p) at g[b * g_bstride + (g_ch_off + m) * HW + p],
+ *              so a channel range of a wider (BN, ., HW) tensor (K7's g_logits) is read where it lies
+ *              (g_ch_off >= 0, g_bstride >= (g_ch_off + M) * HW, in floats)
+ *   x, dx      in x_layout: LSS_PW_NCHW_F32 (BN, K, HW) fp32; LSS_PW_NHWC_F32 / LSS_PW_NHWC_BF16 rows (BN*HW, K).
+ *              x may be NULL when dw is; dx is fully written
+ *   w          (M, K) fp32 (may be NULL when dx is); dw (M, K) fp32, db (M) fp32, fully written
+ *   each of dx, dw, db may be NULL (= not computed)
+ *   workspace  >= lss_pointwise_conv_bwd_workspace_bytes(BN, K, M, HW) bytes when dw or db is asked for (per-slice
+ *              partial sums; contents need not be zero)
+ * fp32 operands and accumulation on the f32 MFMA (bf16 x widened exactly; bf16 dx rounded once on store).  dw and db
+ * are reduced over BN * HW in an order fixed by the shape: no float atomics, bit-reproducible.  A non-finite g element
+ * comes out non-finite in the outputs it reaches.  lss_pointwise_conv_bwd_ok: 1 for the accepted shapes (K % 64 == 0,
+ * K <= 1024, M <= 192, HW >= 1, BN <= 4096, BN * HW <= 2^22); everything else is LSS_E_SHAPE.  Also LSS_E_NULL,
+ * LSS_E_LAYOUT, LSS_E_ALIGN (element alignment), LSS_E_WORKSPACE; nothing is written when a check fails. */
+#define LSS_PW_NCHW_F32 0
+#define LSS_PW_NHWC_F32 1
+#define LSS_PW_NHWC_BF16 2
+int lss_pointwise_conv_bwd_ok(int BN, int K, int M, int HW);
+size_t lss_pointwise_conv_bwd_workspace_bytes(int BN, int K, int M, int HW);
+int lss_pointwise_conv_bwd(const float* g, int g_ch_off, long long g_bstride, const void* x, int x_layout,
+                           const float* w, int BN, int K, int M, int HW, void* workspace, size_t workspace_bytes,
+                           void* dx, float* dw, float* db, void* stream);
+
 /* nn.LayerNorm(C) over rows.  replaces: src/transformer_modules.py:204,208 (norm1, norm2)
  *   x (rows, C) in x_dt; y (rows, C) in y_dt; gamma, beta (C) fp32 */
 int lss_layernorm_fwd(const void* x, int x_dt, const float* gamma, const float* beta,

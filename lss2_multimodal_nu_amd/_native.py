@@ -17,6 +17,7 @@ BEV_NCHW_F32, BEV_NHWC_F32, BEV_NHWC_BF16 = 0, 1, 2
 DT_F32, DT_BF16 = 0, 1
 ACT_NONE, ACT_RELU, ACT_GELU, OUT_F32, OUT_HEAD_MAJOR32, W_RING, W_KS = 0, 1, 2, 16, 32, 64, 128
 VALUE_NHWC, VALUE_HEAD_MAJOR = 0, 1
+PW_NCHW_F32, PW_NHWC_F32, PW_NHWC_BF16 = 0, 1, 2
 
 _vp, _i, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t
 
@@ -35,6 +36,9 @@ SIGNATURES = {
     "lss_deform_attn_pts_fwd": (_i, [_vp] * 3 + [ctypes.c_longlong] + [_i] * 6 + [_vp, _vp]),
     "lss_deform_attn_bwd": (_i, [_vp] * 3 + [ctypes.c_longlong, _vp] + [_i] * 6 + [_vp, _sz, _vp, _vp, _vp]),
     "lss_deform_attn_bwd_workspace_bytes": (_sz, [_i] * 3),
+    "lss_pointwise_conv_bwd_ok": (_i, [_i] * 4),
+    "lss_pointwise_conv_bwd_workspace_bytes": (_sz, [_i] * 4),
+    "lss_pointwise_conv_bwd": (_i, [_vp, _i, ctypes.c_longlong, _vp, _i, _vp] + [_i] * 4 + [_vp, _sz] + [_vp] * 4),
     "lss_layernorm_fwd": (_i, [_vp, _i, _vp, _vp, ctypes.c_longlong, _i, ctypes.c_float, _vp, _i, _vp]),
     "lss_depthnet_voxels_fwd": (_i, [_vp] * 10 + [_i] * 10 + [_vp] * 5),
     "lss_linear_res_ln_fwd": (_i, [_vp] * 4 + [ctypes.c_longlong, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),

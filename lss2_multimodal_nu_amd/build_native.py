@@ -28,6 +28,7 @@ SOURCES = {
     "layout.hip": [],
     "bev_transformer.hip": [],
     "deform_grad.hip": [],
+    "pointwise_grad.hip": [],
     "linear_mfma.hip": [],
     "ffn_fused.hip": [],
     "conv_grad.hip": [],

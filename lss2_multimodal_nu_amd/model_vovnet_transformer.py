@@ -18,8 +18,11 @@ any module returning {'c3': (B*N,768,H/16,W/16), 'c4': (B*N,1024,H/32,W/32)};
 the default passes such feature maps straight through.  The TXT branch is stock
 PyTorch (outside the hot path).
 """
+import os
+
 import torch
 from torch import nn
+from torch.autograd.function import once_differentiable
 from torch.nn import functional as F
 
 from . import ops
@@ -28,6 +31,80 @@ from .model_BEV_TXT import _LiftSplatMixin, _histogram_guard
 from .modules import _FoldedConv, _PRECISIONS, _needs_autograd, _to_nhwc, default_precision
 from .tools import QuickCumsum, gen_dx_bx  # noqa: F401  (reference's import surface)
 from .transformer_modules import LightweightBEVTransformer
+
+
+# ----------------------------------------------------------------------------
+# Autograd nodes of the lift-splat level (training): the 1x1 heads and the splat run on the inference kernels, their
+# backward on K7 + K10; the lifted (B,N,D,fH,fW,C) tensor exists in neither direction.
+# ----------------------------------------------------------------------------
+LIFT_CALLS = {"native": 0, "composition": 0}  # which form `get_voxels` took when it had to be differentiable
+
+
+class _HeadProjFn(torch.autograd.Function):
+    """The 1x1 convs behind the depth heads' hidden map (BN,Cd,fH,fW) and (optionally, same launch) `feat_proj`
+    over C3.
+    forward = K2v without softmax, fp32 math: logits (BN,D,fH,fW) [, context rows (BN,fH,fW,C)];
+    backward = K10 once per projection, reading the gradients where K7 left them."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, hidden, w_depth, b_depth, c3, w_feat, b_feat):
+        hidden = hidden.contiguous()  # (BN,Cd,fH,fW): kept for K10 as it is (the tensor the ReLU's backward holds)
+        rows = hidden.permute(0, 2, 3, 1).contiguous()  # the NHWC rows K2v reads; freed when the node returns
+        with_feat = c3 is not None
+        if with_feat:
+            c3 = c3.contiguous()
+        logits, feat = ops.camencode_v2(rows, w_depth.contiguous(), b_depth.contiguous(), w_depth.shape[0], c3,
+                                        w_feat.contiguous() if with_feat else None,
+                                        b_feat.contiguous() if with_feat else None, softmax=False, math=ops.DT_F32)
+        ctx.save_for_backward(hidden, w_depth, c3, w_feat)
+        ctx.with_feat = with_feat
+        return (logits, feat) if with_feat else logits
+
+    @staticmethod
+    @once_differentiable
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, g_logits, g_feat=None):
+        hidden, w_depth, c3, w_feat = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        out = [None] * 6
+        if need[0] or need[1] or need[2]:
+            out[0], out[1], out[2] = ops.pointwise_conv_bwd(g_logits, hidden, w_depth.contiguous(), layout="nchw",
+                                                            want_dx=need[0], want_dw=need[1], want_db=need[2])
+        if ctx.with_feat and (need[3] or need[4] or need[5]):
+            # (BN,fH,fW,C) rows as autograd sees them; K7 wrote them channel-major, and that is how K10 reads them
+            out[3], out[4], out[5] = ops.pointwise_conv_bwd(g_feat.permute(0, 3, 1, 2), c3, w_feat.contiguous(),
+                                                            layout="nchw", want_dx=need[3], want_dw=need[4],
+                                                            want_db=need[5])
+        return tuple(out)
+
+
+class _HeadsLiftSplatFn(torch.autograd.Function):
+    """(pre-softmax depth map u (BN,D,fH,fW), context rows (BN,fH,fW,C), calibration) -> BEV grid.  forward = softmax
+    over D + `lift_splat_from_heads` (K3 / K4 / K5 behind one native call); backward = K7, which applies the softmax
+    backward itself and returns both gradients in one (BN, D + C, fH, fW) tensor: they are handed on as views of it."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, u, feat, calib, consts, ws, dims, nx, layout):
+        inv_pr, comb, ptr, trn = calib
+        frustum, dx, bx = consts
+        depth = torch.softmax(u, dim=1)
+        feat = feat.contiguous()
+        with _histogram_guard(ws):  # a failed call must not leave the zero-between-calls words of the workspace dirty
+            bev = ops.lift_splat_from_heads(frustum, inv_pr, ptr, comb, trn, dx, bx, depth, feat, ws, dims, nx, layout)
+        ctx.save_for_backward(depth, feat, ws.voxel.clone())
+        ctx.dims, ctx.nx = dims, nx
+        return bev
+
+    @staticmethod
+    @once_differentiable
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_bev):
+        depth, feat, voxel = ctx.saved_tensors
+        D = ctx.dims[2]
+        g = ops.lift_splat_bwd(grad_bev, voxel, depth, feat, ctx.dims, ctx.nx)  # (BN, D + C, fH, fW)
+        return g[:, :D], g[:, D:].permute(0, 2, 3, 1), None, None, None, None, None, None
 
 
 def _conv_bn_relu_head(cin, D):
@@ -59,6 +136,13 @@ class StandardDepthNet(nn.Module):
         return ops.camencode_v2(self.hidden(c3), last.weight.detach(), last.bias.detach(), last.out_channels,
                                 c3.float().contiguous(), cam_encode.feat_proj.weight.detach(),
                                 cam_encode.feat_proj.bias.detach())
+
+    def pre_softmax_and_context(self, c3, c4, cam_encode):
+        """Differentiable: logits (BN,D,fH,fW) + context rows (BN,fH,fW,C); the 3x3 conv-BN-ReLU is torch autograd
+        (a biased conv), the two 1x1 convs are one `_HeadProjFn` node."""
+        last, fp = self.depth_head[3], cam_encode.feat_proj
+        h = self.depth_head[2](self.depth_head[1](self.depth_head[0](c3)))
+        return _HeadProjFn.apply(h, last.weight, last.bias, c3, fp.weight, fp.bias)
 
     def forward(self, c3, c4=None):
         if _needs_autograd(self, c3):
@@ -100,6 +184,18 @@ class MultiScaleDepthNet(nn.Module):
                                     None if fp is None else fp.bias.detach(), softmax=False)
         d4, _ = ops.camencode_v2(h4, l4.weight.detach(), l4.bias.detach(), D, softmax=False)
         return self._fuse(d3, d4), feat
+
+    def pre_softmax_and_context(self, c3, c4, cam_encode):
+        """Differentiable: the fusion conv-BN-ReLU output (the softmax's input) + context rows.  The 3x3 convs, the
+        bilinear upsample of the C4 logits and the fusion tail are torch autograd; the three 1x1 projections are two
+        `_HeadProjFn` nodes."""
+        l3, l4, fp = self.depth_c3[3], self.depth_c4[3], cam_encode.feat_proj
+        h3 = self.depth_c3[2](self.depth_c3[1](self.depth_c3[0](c3)))
+        h4 = self.depth_c4[2](self.depth_c4[1](self.depth_c4[0](c4)))
+        d3, feat = _HeadProjFn.apply(h3, l3.weight, l3.bias, c3, fp.weight, fp.bias)
+        d4 = _HeadProjFn.apply(h4, l4.weight, l4.bias, None, None, None)
+        d4 = F.interpolate(d4, size=d3.shape[2:], mode="bilinear", align_corners=False)
+        return self.fusion(torch.cat([d3, d4], dim=1)), feat
 
     def forward(self, c3, c4):
         if _needs_autograd(self, c3, c4):
@@ -308,7 +404,11 @@ class VoVNetBEVTransformer(_LiftSplatMixin, nn.Module):
             raise RuntimeError("feature map %dx%d / D=%d does not match the frustum %s"
                                % (fH, fW, self.D, tuple(self.frustum.shape[:3])))
         if _needs_autograd(self.depth_net, c3, c4) or _needs_autograd(self.cam_encode, c3):
-            # training: library ops for the heads, then the differentiable voxel pooling
+            if self._lift_native_ok(c3, c4):
+                return _native_lift(self, c3, c4, (rots, trans, intrins, post_rots, post_trans), B, Ncam, layout)
+            # the torch composition: library ops for the heads, then the differentiable voxel pooling on the
+            # materialised lifted tensor (CPU tensors, shapes the kernels refuse, LSS_VOVNET_LIFT_NATIVE=0)
+            LIFT_CALLS["composition"] += 1
             depth = self.depth_net(c3, c4)
             cam = self.cam_encode(c3, depth).view(B, Ncam, self.C, self.D, fH, fW).permute(0, 1, 3, 4, 5, 2)
             return self.voxel_pooling(self.get_geometry(rots, trans, intrins, post_rots, post_trans), cam)
@@ -324,6 +424,34 @@ class VoVNetBEVTransformer(_LiftSplatMixin, nn.Module):
                 return ops.lift_splat_from_heads(self.frustum.detach(), inv_pr, ptr, comb, trn, self.dx.detach(),
                                                  self.bx.detach(), depth, feat, ws, (B, Ncam, self.D, fH, fW, self.C),
                                                  nx, layout)
+
+    def _lift_native_ok(self, c3, c4):
+        """May a differentiable `get_voxels` take the native nodes?  GPU tensors, constant grid, and shapes K2v, K7,
+        K10 and the splat accept; LSS_VOVNET_LIFT_NATIVE=0 keeps the torch composition."""
+        if os.environ.get("LSS_VOVNET_LIFT_NATIVE", "1") == "0":
+            return False
+        v2 = self.lss_version == "v2"
+        if not (c3.is_cuda and self.frustum.is_cuda and (c4.is_cuda if v2 else True)):
+            return False
+        if self.frustum.requires_grad or self.dx.requires_grad or self.bx.requires_grad:
+            return False
+        # the nodes compute in fp32: fp32 modules, and fp32 maps unless autocast casts them at the nodes' door
+        params = list(self.depth_net.parameters()) + list(self.cam_encode.parameters()) + [self.frustum]
+        if any(p.dtype != torch.float32 for p in params):
+            return False
+        maps = [c3] + ([c4] if v2 else [])
+        if any(t.dtype != torch.float32 for t in maps) and not torch.is_autocast_enabled("cuda"):
+            return False
+        BN, Cf, fH, fW = c3.shape
+        heads = [self.depth_net.depth_c3, self.depth_net.depth_c4] if v2 else [self.depth_net.depth_head]
+        Cd = heads[0][3].in_channels
+        if any(h[3].in_channels != Cd or h[3].out_channels != self.D for h in heads) or self.D > 64:
+            return False
+        if Cd % 64 or Cf % 64 or self.C not in (64, 128) or self.cam_encode.feat_proj.in_channels != Cf:
+            return False
+        hws = [fH * fW] + ([c4.shape[2] * c4.shape[3]] if v2 else [])
+        return (all(ops.pointwise_conv_bwd_ok(BN, Cd, self.D, hw) for hw in hws)
+                and ops.pointwise_conv_bwd_ok(BN, Cf, self.C, fH * fW))
 
     def forward(self, imgs, rots, trans, intrins, post_rots, post_trans):
         """imgs: (B*N,3,H,W) / (B,N,3,H,W) camera images for a real trunk, or the
@@ -355,6 +483,21 @@ class VoVNetBEVTransformer(_LiftSplatMixin, nn.Module):
             tokens = self.bev_fusion(tokens, bev_pooled)
         action, description = self.unified_predictor(tokens)
         return bev_seg, action, description
+
+
+def _native_lift(model, c3, c4, calib, B, Ncam, layout):
+    """The differentiable lift-splat level on the native nodes: torch 3x3 conv-BN-ReLU (+ v2's fusion tail) ->
+    `_HeadProjFn` -> `_HeadsLiftSplatFn`."""
+    LIFT_CALLS["native"] += 1
+    BN, _, fH, fW = c3.shape
+    with ops.region("lift_splat_level_train"):
+        dev = model.frustum.device
+        nx = model._nx_ints()
+        dcal = tuple(model._device_calib(dev, *calib))
+        ws = model._workspace(BN * model.D * fH * fW, B * nx[0] * nx[1] * nx[2], dev)
+        u, feat = model.depth_net.pre_softmax_and_context(c3, c4, model.cam_encode)
+        return _HeadsLiftSplatFn.apply(u, feat, dcal, (model.frustum.detach(), model.dx.detach(), model.bx.detach()),
+                                       ws, (B, Ncam, model.D, fH, fW, model.C), nx, layout)
 
 
 def compile_model_vovnet_transformer(bsize, grid_conf, data_aug_conf, outC, vovnet_type="vovnet39", pretrained=True,

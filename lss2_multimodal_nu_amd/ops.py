@@ -12,7 +12,8 @@ import torch
 
 from . import _native as N
 from ._native import (ACT_GELU, ACT_NONE, ACT_RELU, BEV_NCHW_F32, BEV_NHWC_BF16, BEV_NHWC_F32, DT_BF16,  # noqa: F401
-                      DT_F32, OUT_F32, OUT_HEAD_MAJOR32, VALUE_HEAD_MAJOR, VALUE_NHWC, W_KS, W_RING)
+                      DT_F32, OUT_F32, OUT_HEAD_MAJOR32, PW_NCHW_F32, PW_NHWC_BF16, PW_NHWC_F32, VALUE_HEAD_MAJOR,
+                      VALUE_NHWC, W_KS, W_RING)
 
 
 def _f32c(t, name, shape=None):
@@ -558,6 +559,77 @@ def lift_splat_bwd(grad_bev, voxel, depth, feat, dims, nx):
                                        B, Ncam, D, fH, fW, C, X, Y, Z, N.ptr(g_logits), N.stream()),
             "lss_lift_splat_bwd")
     return g_logits
+
+
+def pointwise_conv_bwd_ok(BN, K, M, HW):
+    """True when `pointwise_conv_bwd` accepts the shape (K % 64 == 0, K <= 1024, M <= 192, HW >= 1)."""
+    return bool(N.lib().lss_pointwise_conv_bwd_ok(int(BN), int(K), int(M), int(HW)))
+
+
+def pointwise_conv_bwd(g, x, w, layout="nchw", g_ch_off=0, M=None, want_dx=True, want_dw=True, want_db=True):
+    """K10: backward of a 1x1 conv y = w x + bias (lss_pointwise_conv_bwd).
+    g  fp32 output gradient (BN, Mg, *spatial), channel-major: pixel stride 1, channel stride HW, any image stride
+       >= Mg * HW (a channel slice of a wider tensor is read in place); channels [g_ch_off, g_ch_off + M) are used
+       (M defaults to Mg - g_ch_off);
+    x  layout "nchw": (BN, K, *spatial) fp32; "nhwc": (BN, *spatial, K) fp32 | bf16, contiguous;
+    w  (M, K[, 1, 1]) fp32.
+    Returns (dx like x | None, dw like w | None, db (M) | None); dw and db are bit-reproducible."""
+    if layout not in ("nchw", "nhwc"):
+        raise ValueError("layout must be 'nchw' or 'nhwc'")
+    if g.dim() < 3 or g.dtype != torch.float32:
+        raise ValueError("g must be an fp32 (BN, M, *spatial) tensor, got %s %s" % (g.dtype, tuple(g.shape)))
+    BN, Mg = g.shape[0], g.shape[1]
+    spatial = tuple(g.shape[2:])
+    HW = 1
+    for v in spatial:
+        HW *= v
+    M = Mg - g_ch_off if M is None else M
+    if g_ch_off < 0 or M <= 0 or g_ch_off + M > Mg:
+        raise ValueError("channels [%d, %d) are not inside g's %d" % (g_ch_off, g_ch_off + M, Mg))
+    w2 = w.reshape(w.shape[0], -1)
+    if w2.dtype != torch.float32 or w2.shape[0] != M or not w.is_contiguous():  # (dw is written dense, in w's shape)
+        raise ValueError("w must be contiguous fp32 (%d, K[, 1, 1]), got %s %s" % (M, w.dtype, tuple(w.shape)))
+    K = w2.shape[1]
+    want = (BN, K) + spatial if layout == "nchw" else (BN,) + spatial + (K,)
+    ok_dt = (torch.float32,) if layout == "nchw" else (torch.float32, torch.bfloat16)
+    if x.dtype not in ok_dt or tuple(x.shape) != want or not x.is_contiguous():
+        raise ValueError("x must be contiguous %s of %s, got %s %s"
+                         % (want, " | ".join(str(d) for d in ok_dt), tuple(x.shape), x.dtype))
+    if not pointwise_conv_bwd_ok(BN, K, M, HW):
+        raise ValueError("pointwise_conv_bwd needs K %% 64 == 0, K <= 1024, M <= 192, BN <= 4096, BN * HW <= 2^22 "
+                         "(got BN=%d, K=%d, M=%d, HW=%d)" % (BN, K, M, HW))
+    if not (g.is_cuda and x.is_cuda and w2.is_cuda):
+        raise ValueError("g, x and w must be GPU tensors")
+    # channel-major with unit pixel stride; anything else (a transposed gradient autograd made contiguous its own way)
+    # is copied once
+    gs = g
+    if not _flat_ok(g) or (Mg > 1 and g.stride(1) != HW) or (BN > 1 and g.stride(0) < Mg * HW):
+        gs = g.contiguous()
+    g_bstride = gs.stride(0) if BN > 1 else Mg * HW
+    layout_id = PW_NCHW_F32 if layout == "nchw" else (PW_NHWC_F32 if x.dtype == torch.float32 else PW_NHWC_BF16)
+    dev = x.device
+    dx = torch.empty_like(x) if want_dx else None
+    dw = torch.empty_like(w) if want_dw else None
+    db = torch.empty(M, dtype=torch.float32, device=dev) if want_db else None
+    ws, nbytes = None, 0
+    if want_dw or want_db:
+        nbytes = N.lib().lss_pointwise_conv_bwd_workspace_bytes(BN, K, M, HW)
+        ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dev)
+    with _timed("pointwise_conv_bwd"):
+        N.check(N.lib().lss_pointwise_conv_bwd(N.ptr(gs), g_ch_off, g_bstride, N.ptr(x), layout_id, N.ptr(w2), BN, K, M,
+                                               HW, N.ptr(ws), nbytes, N.ptr(dx), N.ptr(dw), N.ptr(db), N.stream()),
+                "lss_pointwise_conv_bwd")
+    return dx, dw, db
+
+
+def _flat_ok(t):
+    """True when the trailing (spatial) dims of t can be flattened without a copy."""
+    exp = 1
+    for size, stride in zip(reversed(t.shape[2:]), reversed(t.stride()[2:])):
+        if size != 1 and stride != exp:
+            return False
+        exp *= size
+    return True
 
 
 def segmented_sum(x, seg_start):
