@@ -47,15 +47,14 @@ __global__ __launch_bounds__(256) void weighted_ce_kernel(const float* __restric
       }
     const long long t = tgt[i];
     const bool ok = t >= 0 && t < C;
-    float wt = 0.f, pt = 1.f;
+    float wt = 0.f;
 #pragma unroll
     for (int c = 0; c < CE_MAXC; ++c)
-      if (c < C && ok && c == (int)t) {
-        wt = wc[c];
-        pt = v[c] / se;
-      }
+      if (c < C && ok && c == (int)t) wt = wc[c];
     if (!BWD) {
-      s_loss += ok ? -wt * logf(pt) : 0.f;
+      // max + log(sum) - x_t, not -log(exp(x_t - max) / sum): the quotient underflows to 0 once the target is ~88 - 104
+      // below the maximum, and the loss became +inf (NaN for a zero-weight class: 0 * inf)
+      s_loss += ok ? wt * (logf(se) - (xp[(size_t)t * HW] - mx)) : 0.f;
       s_w += wt;
     } else {
       float* gp = gx + (size_t)b * C * HW + p;

@@ -484,7 +484,7 @@ def _train_conv_bn_act(conv, bn, x1, relu, residual=None, up=None, x2=None):
     if (x1.is_cuda and _native_training() and _bn_native_ok(bn, True) and conv.kernel_size == (3, 3)
             and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1
             and conv.bias is None and conv.weight.dtype == torch.float32 and x1.shape[1] % 64 == 0 and c2 % 64 == 0
-            and conv.out_channels % 8 == 0 and (scale == 1 or (x1.shape[2] > 1 and x1.shape[3] > 1))):
+            and conv.out_channels % 64 == 0 and (scale == 1 or (x1.shape[2] > 1 and x1.shape[3] > 1))):
         if "_lss_sync" not in bn.__dict__:
             y = _ConvBNActFn.apply(x1, x2, conv.weight, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var,
                                    float(bn.momentum), float(bn.eps), bool(relu), scale)
@@ -523,7 +523,7 @@ def _train_up_conv(conv, up, x1, x2):
     """conv(cat([x2, upsample(x1)])) on the autograd path (x2 may be None)."""
     c2 = 0 if x2 is None else x2.shape[1]
     if (x1.is_cuda and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
-            and conv.bias is None and x1.shape[1] % 64 == 0 and c2 % 64 == 0 and conv.out_channels % 8 == 0
+            and conv.bias is None and x1.shape[1] % 64 == 0 and c2 % 64 == 0 and conv.out_channels % 64 == 0
             and x1.shape[2] > 1 and x1.shape[3] > 1 and _native_training()):
         return _UpConv3x3Fn.apply(x1, x2, conv.weight, int(up.scale_factor))
     x1 = up(x1)
@@ -532,10 +532,11 @@ def _train_up_conv(conv, up, x1, x2):
 
 def _train_conv(conv, x):
     """conv(x) on the autograd path: the 3x3/s1/p1 shapes (95 % of BevEncode's FLOPs) run
-    forward and backward on the HIP kernels, everything else on the library."""
+    forward and backward on the HIP kernels, everything else on the library.  out_channels % 64 == 0 (here, in
+    _train_up_conv and in _train_conv_bn_act): the input-gradient conv reads the layer's Cout in K blocks of 64."""
     if (x.is_cuda and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
             and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
-            and conv.in_channels % 64 == 0 and conv.out_channels % 8 == 0 and _native_training()):
+            and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0 and _native_training()):
         return _Conv3x3Fn.apply(x, conv.weight)
     k, p = conv.kernel_size[0], conv.padding[0]
     if (x.is_cuda and conv.stride == (2, 2) and conv.kernel_size in ((1, 1), (3, 3), (7, 7)) and conv.padding == (k // 2, k // 2)

@@ -1171,6 +1171,12 @@ class WeightPrepack:
     def invalidate(self):
         self.fresh = False
 
+    def clear(self):
+        """Forget every registered image (the units pack and register again on their next call)."""
+        self.jobs = {}
+        self._table = None
+        self.fresh = False
+
 
 prepack = WeightPrepack()
 

@@ -1,0 +1,580 @@
+"""Every autograd node of the BevEncode training step on its own against fp64: `_ConvBNActFn` over the dispatch table of
+`ops.conv_bn_act_train_fwd/bwd` (ring / K-split / tile for the forward and for the gradient conv), `_Conv3x3Fn`,
+`_ConvS2Fn`, `_UpConv3x3Fn`, `_BNActFn`, `_SyncBNActFn` and the split BatchNorm entry points `ops.bn_partial_sums`,
+`ops.bn_train_fwd_from_sums`, `ops.bn_train_bwd_from_sums`, driven through the functions the model uses
+(`modules._train_conv_bn_act`, `_train_conv`, `_train_up_conv`, `_train_bn_act`); plus `ops.weighted_ce_fwd/bwd`.
+
+Reference, ReLU mask handling and tolerances: tests/train_node_ref.py.  Every bound is 3 x the rounding floor of the
+case (computed on the CPU, nothing taken from a kernel), at least 2^-8 for bf16 and 2e-4 for fp32 outputs; every measured
+error is `report`ed next to its floor."""
+import pytest
+import torch
+from torch import nn
+
+import train_node_ref as R
+
+pytestmark = pytest.mark.gpu
+
+from lss2_multimodal_nu_amd import modules as M  # noqa: E402
+from lss2_multimodal_nu_amd import ops  # noqa: E402
+
+
+def _path(B, H, W, Cx, C2, up, Cout):
+    """(forward conv kernel, gradient conv kernel) of a training unit, from the functions the C dispatch itself calls
+    (train_unit_pack in csrc/bn_train.hip)."""
+    Hh, Wh, Ct = H * up, W * up, Cx + C2
+    fwd = "ring" if ops.conv_ring_ok(B, H, W, Cx, C2, up, Cout) else (
+        "ks" if C2 == 0 and up == 1 and ops.conv_ks_ok(B, H, W, Cx, Cout) else "tile")
+    grad = "ring" if ops.conv_ring_ok(B, Hh, Wh, Cout, 0, 1, Ct) else ("ks" if ops.conv_ks_ok(B, Hh, Wh, Cout, Ct) else "tile")
+    return fwd, grad
+
+
+def _modules(op, K=3, stride=1):
+    conv = bn = up = None
+    if op.get("w") is not None:
+        Co, Ct = op["w"].shape[:2]
+        conv = nn.Conv2d(Ct, Co, K, stride=stride, padding=K // 2, bias=False).cuda()
+        with torch.no_grad():
+            conv.weight.copy_(op["w"])
+    if op["bn"]:
+        C = op["gamma"].numel()
+        bn = nn.BatchNorm2d(C, eps=R.EPS, momentum=R.MOMENTUM).cuda().train()
+        with torch.no_grad():
+            bn.weight.copy_(op["gamma"])
+            bn.bias.copy_(op["beta"])
+            bn.running_mean.copy_(op["running_mean"])
+            bn.running_var.copy_(op["running_var"])
+    if op["up"] > 1:
+        up = nn.Upsample(scale_factor=op["up"], mode="bilinear", align_corners=True)
+    return conv, bn, up
+
+
+def _nchw(t):
+    return t.detach().permute(0, 3, 1, 2).double().cpu()
+
+
+def _run(op, how, need=("x1", "x2", "w", "res"), mods=None):
+    """One forward + backward of the unit on the GPU.  how: "fused" (_train_conv_bn_act), "unfused" (_train_conv /
+    _train_up_conv, then _train_bn_act), "conv", "bn".  Returns (outputs as fp64 CPU tensors, timer tags, node names)."""
+    conv, bn, up = mods or _modules(op, K=op["w"].shape[2] if op.get("w") is not None else 3, stride=op["stride"])
+
+    def dev(k, flag):
+        return None if op.get(k) is None else op[k].cuda().to(torch.bfloat16).requires_grad_(flag)
+
+    x1, x2, z_in = dev("x1", "x1" in need), dev("x2", "x2" in need), dev("z", True)
+    res = dev("res", "res" in need)
+    if conv is not None:
+        conv.weight.requires_grad_("w" in need)
+    timer = ops.KernelTimer(fine=True)
+    ops.set_timer(timer)
+    nodes, z_mid = [], None
+    try:
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            if how == "fused":
+                y = M._train_conv_bn_act(conv, bn, x1, op["relu"], res, up, x2)
+            else:
+                if how == "bn":
+                    z_mid = z_in
+                else:
+                    z_mid = M._train_conv(conv, x1) if up is None else M._train_up_conv(conv, up, x1, x2)
+                    nodes.append(type(z_mid.grad_fn).__name__)
+                y = z_mid if how == "conv" else M._train_bn_act(bn, z_mid, op["relu"], res)
+        nodes.append(type(y.grad_fn).__name__)
+        got = {"y": y.detach().double().cpu()}
+        saved = y.grad_fn.saved_tensors if how != "conv" else None
+        if nodes[-1] == "_ConvBNActFnBackward":   # x1n, x2n, z, y, w, gamma, stat = (mean, invstd)
+            assert len(saved) == 7 and saved[2].dtype == torch.bfloat16 and saved[2].shape == saved[3].shape \
+                and tuple(saved[6].shape) == (2, saved[2].shape[-1]), "save_for_backward of _ConvBNActFn changed"
+            got.update(z=_nchw(saved[2]), mean=saved[6][0].double().cpu(), invstd=saved[6][1].double().cpu())
+        elif how != "conv":         # zn, y, gamma, mean, invstd
+            assert len(saved) == 5 and saved[0].dtype == torch.bfloat16 and saved[0].shape == saved[1].shape \
+                and saved[3].shape == saved[4].shape == saved[2].shape, "save_for_backward of the BatchNorm node changed"
+            got.update(z=_nchw(saved[0]), mean=saved[3].double().cpu(), invstd=saved[4].double().cpu())
+        wanted = {"g1": x1, "g2": x2, "dres": res, "dw": None if conv is None or "w" not in need else conv.weight,
+                  "dgamma": None if bn is None else bn.weight, "dbeta": None if bn is None else bn.bias,
+                  "dz": z_mid if how in ("unfused", "bn") else None}
+        wanted = {k: v for k, v in wanted.items() if v is not None and v.requires_grad}
+        grads = torch.autograd.grad(y, list(wanted.values()), op["gy"].cuda().to(torch.bfloat16))
+        torch.cuda.synchronize()
+    finally:
+        ops.set_timer(None)
+    got.update({k: g.detach().double().cpu() for k, g in zip(wanted, grads)})
+    if bn is not None:
+        got.update(running_mean=bn.running_mean.double().cpu(), running_var=bn.running_var.double().cpu())
+        assert int(bn.num_batches_tracked) == (1 if mods is None else int(bn.num_batches_tracked))
+    return got, set(timer.spans), nodes
+
+
+def _compare(report, name, got, op, expect, ref=None, emu_kw=None):
+    """Mask check, fp64 reference with the node's own mask, floor, and the 3 x floor assertion for every output."""
+    fwd = R.reference(op) if ref is None else ref
+    mask = None
+    if op["relu"]:
+        frac, inside = R.mask_check(got["y"], fwd)
+        report("train_nodes.%s.band_fraction" % name, frac)
+        report("train_nodes.%s.mask_differs_inside_band" % name, inside)
+        mask = (got["y"] > 0).double()
+    ref = R.reference(op, mask)
+    emu = R.evaluate(op, mask, emulate=True, **(emu_kw or {}))
+    assert set(expect) <= set(got) and set(expect) <= set(ref), (sorted(expect), sorted(got), sorted(ref))
+    return _assert_within(report, name, {k: got[k] for k in expect}, ref, emu), ref, emu
+
+
+def _assert_within(report, name, got, ref, emu):
+    floor = R.floors(ref, emu, list(got))
+    bound = R.bounds(floor)
+    bad, worst = [], (0.0, None)
+    for k in sorted(got):
+        e = R.errors(got[k], ref[k])
+        for metric, ev, fv, bv in zip(("max", "l2"), e, floor[k], bound[k]):
+            report("train_nodes.%s.%s.%s" % (name, k, metric), ev)
+            report("train_nodes.%s.%s.%s_floor" % (name, k, metric), fv)
+            if not ev <= bv:
+                bad.append("%s %s: %.3e > %.3e (floor %.3e)" % (k, metric, ev, bv, fv))
+            if bv > 0 and ev / bv >= worst[0]:
+                worst = (ev / bv, "%s.%s measured %.3e floor %.3e" % (k, metric, ev, fv))
+    print("worst %-40s %s" % (name, worst[1]))
+    assert not bad, (name, bad)
+    return worst
+
+
+def _same_bits(a, b):
+    assert sorted(a) == sorted(b)
+    for k in a:
+        assert torch.equal(a[k], b[k]), "%s differs between two runs of the same node" % k
+
+
+def _expected_outputs(op, need, how):
+    u = op["unit"]
+    e = ["y"]
+    if how != "conv":
+        e += ["z", "mean", "invstd", "running_mean", "running_var", "dgamma", "dbeta"]
+    if how in ("unfused", "bn"):
+        e.append("dz")
+    if how != "bn":
+        e += [k for k, n in (("g1", "x1"), ("dw", "w")) if n in need]
+        if u.C2 and "x2" in need:
+            e.append("g2")
+    if op.get("res") is not None and "res" in need and how != "conv":
+        e.append("dres")
+    return e
+
+
+FUSED_TAGS = {"conv_bn_act_train_fwd", "conv_bn_act_train_bwd"}
+
+
+def _fused_case(report, u, name=None, op=None):
+    op = op or R.make_operands(u)
+    ops.prepack.clear()
+    got, tags, nodes = _run(op, "fused", u.need)
+    assert nodes == ["_ConvBNActFnBackward"] and tags == FUSED_TAGS, (nodes, tags)
+    again, _, _ = _run(op, "fused", u.need)
+    _same_bits(got, again)
+    out = _compare(report, name or u.name, got, op, _expected_outputs(op, u.need, "fused"))
+    ops.assert_no_timeouts(name or u.name)
+    return got, out
+
+
+@pytest.mark.parametrize("u", R.FUSED, ids=lambda u: u.name)
+def test_conv_bn_act_node_vs_fp64(u, report):
+    """`_ConvBNActFn` (ops.conv_bn_act_train_fwd / bwd) at the benched units and at small odd shapes: the forward conv
+    and the gradient conv each take the kernel the case names, and y, z, the batch statistics, the running statistics and
+    every gradient the `needs_input_grad` subset asks for are within 3 x the rounding floor of the fp64 reference."""
+    assert _path(u.B, u.H, u.W, u.Cx, u.C2, u.up, u.Cout) == (u.fwd, u.grad)
+    _fused_case(report, u)
+
+
+def test_cout_32_takes_the_library_conv(report):
+    """A Cout of 32 passes the BatchNorm kernels' channel rule (C % 8 == 0, 256 % (C / 8) == 0) but not the gradient
+    conv's (it reads the layer's Cout channels in K blocks of 64).  With `out_channels % 8 == 0` in the guards of
+    _train_conv_bn_act / _train_conv / _train_up_conv the forward ran and the backward raised
+    "lss_conv_bn_act_train_bwd failed (-2): lss: size out of range for this kernel" (`_Conv3x3Fn`: the same from
+    lss_conv2d_fwd in the input-gradient conv).  The guards now ask for % 64: the conv goes to the library, the
+    BatchNorm to `_BNActFn`, and the unit is within the bound (the library's weight gradient is stored in bf16)."""
+    u = R.COUT32
+    op = R.make_operands(u)
+    got, tags, nodes = _run(op, "fused")
+    assert nodes == ["_BNActFnBackward"] and tags == {"bn_train_fwd", "bn_train_bwd"}, (nodes, tags)
+    again = _run(op, "fused")[0]   # the library's conv gradients are not promised to be bit-reproducible: the native part is
+    for k in ("y", "z", "mean", "invstd", "running_mean", "running_var", "dgamma", "dbeta", "dres"):
+        assert torch.equal(got[k], again[k]), k
+    _compare(report, u.name, got, op, _expected_outputs(op, u.need, "fused"), emu_kw={"bf16_dw": True})
+    conv = _modules(op)[0]
+    x = op["x1"].cuda().to(torch.bfloat16).requires_grad_(True)
+    with torch.autocast("cuda", dtype=torch.bfloat16):
+        z = M._train_conv(conv, x)
+    assert "Conv3x3Fn" not in type(z.grad_fn).__name__
+    z.float().sum().backward()
+    assert bool(torch.isfinite(x.grad).all()) and bool(torch.isfinite(conv.weight.grad).all())
+    ops.assert_no_timeouts(u.name)
+
+
+def test_conv_bn_act_cases_cover_the_dispatch_table():
+    paths = {_path(u.B, u.H, u.W, u.Cx, u.C2, u.up, u.Cout) for u in R.FUSED}
+    assert {p[0] for p in paths} == {"ring", "ks", "tile"} and {p[1] for p in paths} == {"ring", "ks", "tile"}
+    assert any(f != g for f, g in paths)
+
+
+def test_conv_bn_act_ring_switched_off_gives_the_same_result(report, monkeypatch):
+    """LSS_CONV_RING=0 on a ring shape: the tile kernel, within the same bound (A/B of the dispatch)."""
+    u = next(x for x in R.FUSED if x.name == R.RING_AB)
+    assert _path(u.B, u.H, u.W, u.Cx, u.C2, u.up, u.Cout)[0] == "ring"
+    monkeypatch.setenv("LSS_CONV_RING", "0")
+    assert _path(u.B, u.H, u.W, u.Cx, u.C2, u.up, u.Cout) == ("tile", "tile")
+    _fused_case(report, u, name=u.name + ".ring_off")
+
+
+@pytest.mark.parametrize("u", [R.FUSED[8], R.FUSED[9]], ids=lambda u: u.name)
+def test_prepacked_weight_images_of_a_unit(u, report):
+    """(a) the unit packs inside the call, (b) after ops.prepack.run(params): bit-equal outputs; after
+    prepack.invalidate() and an in-place weight change the next call sees the new weights."""
+    op = R.make_operands(u)
+    need = ("x1", "x2", "w")
+    ops.prepack.clear()
+    mods = _modules(op)
+    conv, bn, _ = mods
+
+    def reset():
+        with torch.no_grad():
+            bn.running_mean.copy_(op["running_mean"])
+            bn.running_var.copy_(op["running_var"])
+
+    try:
+        a, _, _ = _run(op, "fused", need, mods)
+        assert len(ops.prepack.jobs) == 2 and not ops.prepack.fresh     # forward and gradient image registered
+        reset()
+        ops.prepack.run([conv.weight])
+        kinds = [("unit", d, u.B, u.H, u.W, u.Cx, u.C2, u.up) for d in (0, 1)]
+        assert ops.prepack.fresh and all(ops.prepack.lookup(conv.weight.detach(), k) is not None for k in kinds)
+        b, _, _ = _run(op, "fused", need, mods)
+        _same_bits(a, b)
+        _compare(report, u.name + ".prepacked", b, op, _expected_outputs(op, need, "fused"))
+        ops.prepack.invalidate()
+        with torch.no_grad():
+            conv.weight.mul_(-0.5)
+        reset()
+        c, _, _ = _run(op, "fused", need, mods)
+        op2 = dict(op, w=op["w"] * -0.5)
+        ops.prepack.clear()
+        fresh, _, _ = _run(op2, "fused", need)
+        _same_bits(c, fresh)
+        assert not torch.equal(c["y"], a["y"])
+        _compare(report, u.name + ".new_weights", c, op2, _expected_outputs(op2, need, "fused"))
+    finally:
+        ops.prepack.clear()
+    ops.assert_no_timeouts(u.name)
+
+
+@pytest.mark.parametrize("u", R.CONV + R.UPCONV, ids=lambda u: u.name)
+def test_conv_nodes_vs_fp64(u, report):
+    """`_Conv3x3Fn` (_train_conv) and `_UpConv3x3Fn` (_train_up_conv; with and without x2, up 2 and 4)."""
+    op = R.make_operands(u)
+    op["bn"], op["relu"] = False, False
+    got, tags, nodes = _run(op, "conv")
+    node = "_Conv3x3FnBackward" if u.up == 1 else "_UpConv3x3FnBackward"
+    assert nodes == [node, node], nodes
+    assert {"conv2d_train_fwd", "conv2d_dgrad", "conv2d_wgrad"} <= tags and (u.up == 1 or "upsample_bwd" in tags), tags
+    _same_bits(got, _run(op, "conv")[0])
+    _compare(report, u.name, got, op, _expected_outputs(op, u.need, "conv"))
+    ops.assert_no_timeouts(u.name)
+
+
+@pytest.mark.parametrize("u", R.BN, ids=lambda u: u.name)
+def test_bn_act_node_vs_fp64(u, report):
+    """`_BNActFn` (_train_bn_act): y, statistics, dz, dres, dgamma, dbeta."""
+    op = R.make_operands(u)
+    got, tags, nodes = _run(op, "bn")
+    assert nodes == ["_BNActFnBackward"] and tags == {"bn_train_fwd", "bn_train_bwd"}, (nodes, tags)
+    _same_bits(got, _run(op, "bn")[0])
+    _compare(report, u.name, got, op, _expected_outputs(op, u.need, "bn"))
+    ops.assert_no_timeouts(u.name)
+
+
+@pytest.mark.parametrize("case", R.S2, ids=lambda c: c[0])
+def test_stride2_conv_node_vs_fp64(case, report):
+    """`_ConvS2Fn` for K in {1, 3, 7}, also where `_s2_wgrad_native_ok` is false (W // 2 < 8: the im2col + GEMM weight
+    gradient, whose per-sample bf16 GEMM results the floor emulates)."""
+    name, K, B, H, W, C, Co, native = case
+    op = R.make_s2_operands(name, K, B, H, W, C, Co)
+    probe = torch.empty(B, H, W, C, device="cuda")
+    assert M._s2_wgrad_native_ok(probe, Co, K) == native and M._s2_dgrad_native_ok(probe, Co, K)
+    got, tags, nodes = _run(op, "conv")
+    assert nodes == ["_ConvS2FnBackward"] * 2, nodes
+    assert {"conv2d_train_fwd", "conv2d_dgrad"} <= tags and ("conv2d_wgrad" in tags) == native, tags
+    _same_bits(got, _run(op, "conv")[0])
+    _compare(report, name, got, op, ["y", "g1", "dw"], emu_kw={"per_sample_bf16_dw": not native})
+    ops.assert_no_timeouts(name)
+
+
+@pytest.mark.parametrize("case", [R.S2[0], R.S2[1], R.S2[2]], ids=lambda c: c[0])
+@pytest.mark.parametrize("switch", ["LSS_S2_DGRAD_LIB", "LSS_S2_DGRAD_GEMM"])
+def test_stride2_conv_node_data_gradient_fallbacks_vs_fp64(case, switch, report, monkeypatch):
+    """The two data-gradient fallbacks of `_ConvS2Fn` (no shape reaches them behind _train_conv's in_channels % 64 guard;
+    their A/B switches do): the library's convolution_backward and the GEMM + col2im form, whose per-tap columns are a
+    bf16 tensor (emulated in the floor).  The library's kernels are documented as not bit-reproducible, so only the GEMM
+    form is run twice for equality."""
+    name, K, B, H, W, C, Co, native = case
+    op = R.make_s2_operands(name, K, B, H, W, C, Co)
+    monkeypatch.setenv(switch, "1")
+    assert not M._s2_dgrad_native_ok(torch.empty(B, H, W, C, device="cuda"), Co, K)
+    got, tags, nodes = _run(op, "conv")
+    assert nodes == ["_ConvS2FnBackward"] * 2 and "conv2d_dgrad" not in tags and "conv2d_wgrad" in tags, (nodes, tags)
+    gemm = switch == "LSS_S2_DGRAD_GEMM"
+    if gemm:
+        _same_bits(got, _run(op, "conv")[0])
+    _compare(report, "%s.%s" % (name, "dgrad_gemm" if gemm else "dgrad_lib"), got, op, ["y", "g1", "dw"],
+             emu_kw={"col2im_bf16": gemm})
+    ops.assert_no_timeouts(name)
+
+
+@pytest.mark.parametrize("u", R.FUSED_VS_UNFUSED, ids=lambda u: u.name)
+def test_fused_node_vs_conv_node_plus_bn_node(u, report):
+    """Both compositions of the same unit are within the bound of the reference; their mutual difference is reported."""
+    op = R.make_operands(u)
+    need = ("x1", "x2", "w", "res")
+    ops.prepack.clear()
+    fused, _, n1 = _run(op, "fused", need)
+    parts, tags, n2 = _run(op, "unfused", need)
+    _same_bits(fused, _run(op, "fused", need)[0])
+    _same_bits(parts, _run(op, "unfused", need)[0])
+    assert n1 == ["_ConvBNActFnBackward"] and n2 == ["_Conv3x3FnBackward" if u.up == 1 else "_UpConv3x3FnBackward",
+                                                    "_BNActFnBackward"], (n1, n2)
+    assert {"bn_train_fwd", "bn_train_bwd", "conv2d_train_fwd", "conv2d_dgrad", "conv2d_wgrad"} <= tags, tags
+    _compare(report, u.name + ".fused", fused, op, _expected_outputs(op, need, "fused"))
+    _compare(report, u.name + ".unfused", parts, op, _expected_outputs(op, need, "unfused"))
+    for k in sorted(set(fused) & set(parts)):
+        report("train_nodes.%s.fused_vs_unfused.%s.max" % (u.name, k), R.errors(fused[k], parts[k])[0])
+    ops.assert_no_timeouts(u.name)
+
+
+def _channels(d, sel):
+    """The entries of an output dict that are indexed by the output channel, restricted to channels `sel`."""
+    out = {}
+    for k, v in d.items():
+        if k in ("y", "z", "dz", "dres", "t"):
+            out[k] = v[:, sel]
+        elif k in ("dw", "dgamma", "dbeta", "mean", "invstd", "running_mean", "running_var"):
+            out[k] = v[sel]
+    return out
+
+
+def test_degenerate_channels(report):
+    """A constant output channel (variance 0: invstd = eps^-1/2, dz finite and equal to the reference's), a channel
+    whose y is <= 0 everywhere (mask all zero: dgamma = dbeta = 0, dz = 0, dw = 0), a channel with gamma = 0 (the
+    zero_init_residual start of every real run: dz = 0, dgamma != 0).  The constant channel's dz is 316 times the
+    others', so each of the three channels and the rest are compared separately, each against its own floor."""
+    op = R.make_degenerate_operands()
+    u = op["unit"]
+    ops.prepack.clear()
+    fused, tags, _ = _run(op, "fused")
+    assert tags == FUSED_TAGS
+    parts, _, _ = _run(op, "unfused")
+    _same_bits(fused, _run(op, "fused")[0])
+    for how, got in (("fused", fused), ("unfused", parts)):
+        fwd = R.reference(op)
+        R.mask_check(got["y"], fwd)
+        mask = (got["y"] > 0).double()
+        ref, emu = R.reference(op, mask), R.evaluate(op, mask, emulate=True)
+        assert all(bool(torch.isfinite(v).all()) for v in got.values())
+        keys = _expected_outputs(op, u.need, how)
+        for nm, sel in (("constant", slice(0, 1)), ("all_masked", slice(1, 2)), ("gamma0", slice(2, 3)), ("rest", slice(3, None))):
+            g = _channels({k: got[k] for k in keys}, sel)
+            _assert_within(report, "%s.%s.%s" % (u.name, how, nm), g, _channels(ref, sel), _channels(emu, sel))
+        _assert_within(report, "%s.%s.inputs" % (u.name, how), {"g1": got["g1"]}, ref, emu)
+        assert float(ref["invstd"][0]) == pytest.approx(R.EPS ** -0.5) and float(got["y"][:, 0].min()) == 0.5
+        assert float(got["y"][:, 1].max()) == 0.0
+        for k in ("dgamma", "dbeta"):
+            assert float(got[k][1]) == 0.0
+        assert float(got["dw"][1].abs().max()) == 0.0 and float(got["dw"][2].abs().max()) == 0.0
+        assert float(got["dgamma"][2]) != 0.0
+        if how == "unfused":
+            assert float(got["dz"][:, 1:3].abs().max()) == 0.0 and float(got["dz"][:, 0].abs().max()) > 0.0
+    ops.assert_no_timeouts(u.name)
+
+
+def test_small_gamma(report):
+    """gamma in [0.02, 0.12] on every channel of a fused unit."""
+    _fused_case(report, R.SMALL_GAMMA, op=R.make_small_gamma_operands())
+
+
+def test_all_zero_upstream_gradient(report):
+    op = R.make_zero_grad_operands()
+    got, _ = _fused_case(report, R.ZERO_GRAD, op=op)
+    for k in ("g1", "dw", "dgamma", "dbeta", "dres"):
+        assert float(got[k].abs().max()) == 0.0, k
+
+
+def test_bn_act_node_on_one_row(report):
+    """M = 1: variance 0, y = beta + residual, dz = 0, dbeta = g, dgamma = 0; the running variance moves towards 0."""
+    op = R.make_operands(R.ONE_ROW)
+    got, _, nodes = _run(op, "bn")
+    assert nodes == ["_BNActFnBackward"]
+    _same_bits(got, _run(op, "bn")[0])
+    _compare(report, R.ONE_ROW.name, got, op, _expected_outputs(op, R.ONE_ROW.need, "bn"))
+    assert float(got["dz"].abs().max()) == 0.0 and float(got["dgamma"].abs().max()) == 0.0
+    ops.assert_no_timeouts(R.ONE_ROW.name)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# split BatchNorm (the halves `_SyncBNActFn` is made of) without a process group: the all-reduce is a torch addition
+
+def _nhwc(t):
+    return t.permute(0, 2, 3, 1).contiguous().cuda().to(torch.bfloat16)
+
+
+def _split_forward(op, shards):
+    zn, rn = _nhwc(op["z"]), None if op["res"] is None else _nhwc(op["res"])
+    n = zn.shape[0] // shards
+    zs = [zn[s * n:(s + 1) * n].contiguous() for s in range(shards)]
+    rs = [None if rn is None else rn[s * n:(s + 1) * n].contiguous() for s in range(shards)]
+    gamma, beta = op["gamma"].cuda(), op["beta"].cuda()
+    # one copy of the running statistics per simulated rank: bn_train_fwd_from_sums reads running_mean as the pivot of
+    # the sums and then updates it in place
+    rms = [op["running_mean"].clone().cuda() for _ in range(shards)]
+    rvs = [op["running_var"].clone().cuda() for _ in range(shards)]
+    sums = sum(ops.bn_partial_sums(zs[s], 0, mean=rms[s]) for s in range(shards))
+    m_total = zn.numel() // zn.shape[-1]
+    outs = [ops.bn_train_fwd_from_sums(zs[s], sums, m_total, gamma, beta, rms[s], rvs[s], R.MOMENTUM, R.EPS, op["relu"], rs[s])
+            for s in range(shards)]
+    for s in range(1, shards):   # every rank holds the same global statistics
+        assert torch.equal(outs[s][1], outs[0][1]) and torch.equal(outs[s][2], outs[0][2])
+        assert torch.equal(rms[s], rms[0]) and torch.equal(rvs[s], rvs[0])
+    return zs, gamma, m_total, outs, rms[0], rvs[0]
+
+
+def _split_bn(op, shards):
+    zs, gamma, m_total, outs, rm, rv = _split_forward(op, shards)
+    n = zs[0].shape[0]
+    gyn = _nhwc(op["gy"])
+    gs = [gyn[s * n:(s + 1) * n].contiguous() for s in range(shards)]
+    mean, invstd = outs[0][1], outs[0][2]
+    local = [ops.bn_partial_sums(zs[s], 1, dy=gs[s], y=outs[s][0], mean=mean, invstd=invstd, relu=op["relu"])
+             for s in range(shards)]
+    glob = sum(local)
+    back = [ops.bn_train_bwd_from_sums(gs[s], outs[s][0], zs[s], glob, m_total, gamma, mean, invstd, op["relu"],
+                                       op["res"] is not None) for s in range(shards)]
+    torch.cuda.synchronize()
+    got = {"y": _nchw(torch.cat([o[0] for o in outs])), "mean": mean.double().cpu(), "invstd": invstd.double().cpu(),
+           "running_mean": rm.double().cpu(), "running_var": rv.double().cpu(),
+           "dz": _nchw(torch.cat([b[0] for b in back])), "dbeta": glob[0].double().cpu(), "dgamma": glob[1].double().cpu()}
+    if op["res"] is not None:
+        got["dres"] = _nchw(torch.cat([b[1] for b in back]))
+    return got
+
+
+@pytest.mark.parametrize("shards,relu,res", R.SPLIT_BN)
+def test_split_batchnorm_vs_fp64_whole_batch(shards, relu, res, report):
+    """ops.bn_partial_sums (mode 0 about running_mean, mode 1) + bn_train_fwd_from_sums + bn_train_bwd_from_sums on 2 and
+    3 shards with different statistics against fp64 BatchNorm of the whole batch: y, mean, invstd, the running statistics
+    (updated once, with the unbiased global variance), dz, dres; the local dgamma / dbeta sums add up to the
+    whole-batch ones."""
+    op = R.make_split_bn_operands(shards, relu=relu, res=res)
+    got = _split_bn(op, shards)
+    _same_bits(got, _split_bn(op, shards))
+    name = "split_bn_%d_relu%d_res%d" % (shards, relu, res)
+    _compare(report, name, got, op, sorted(got))
+    ops.assert_no_timeouts(name)
+
+
+def test_split_batchnorm_statistics_with_the_shared_pivot(report):
+    """The split form sums about a pivot every rank shares (running_mean: 0 on a fresh model) where the local form uses
+    the tensor's first row, so its variance is E[z^2] - mean^2 in fp32 and cancels with (mean / std)^2.  Channels of
+    unit spread with |mean| = 2, 4, 6, 8, 10 in both signs and a 10 / 10 channel (R.LARGE_MEAN, ratios up to 10) must
+    meet the local path's bound (invstd relative error < 2e-4, as test_bn_train_statistics_of_large_mean_channels);
+    ratios of 20, 50 and 100 and the 300 / 2 and -2000 / 8 channels of that test are measured and reported, not
+    asserted - DESIGN.md section 9 has what they give."""
+    shards = 2
+    op = R.make_split_bn_operands(shards, relu=False, res=False, large=True, H=100, W=100)
+    _, _, m_total, outs, _, _ = _split_forward(op, shards)
+    assert m_total == 40000
+    z = op["z"].double()
+    m_ref, v_ref = z.mean((0, 2, 3)), z.var((0, 2, 3), unbiased=False)
+    i_ref = (v_ref + R.EPS).rsqrt()
+    ratio = m_ref.abs() / v_ref.sqrt()
+    mean, invstd = outs[0][1].double().cpu(), outs[0][2].double().cpu()
+    rel_i = (invstd - i_ref).abs() / i_ref
+    rel_m = (mean - m_ref).abs() / m_ref.abs().clamp(min=1.0)
+    n = len(R.LARGE_MEAN)
+    for c in range(1, n + 1):
+        print("shared pivot: channel %2d mean %8.1f std %5.1f ratio %6.1f invstd rel %.3e mean rel %.3e"
+              % (c, float(m_ref[c]), float(v_ref[c].sqrt()), float(ratio[c]), float(rel_i[c]), float(rel_m[c])))
+        report("train_nodes.split_bn_shared_pivot.ch%d.ratio" % c, ratio[c])
+        report("train_nodes.split_bn_shared_pivot.ch%d.invstd_rel" % c, rel_i[c])
+        report("train_nodes.split_bn_shared_pivot.ch%d.mean_rel" % c, rel_m[c])
+    asserted = list(range(1, R.LARGE_MEAN_ASSERTED + 1))
+    assert float(ratio[asserted[:-1]].min()) > 1.9 and float(ratio[9:11].min()) > 9.8   # the cases are what they claim
+    keep = [0] + asserted + list(range(n + 1, 64))
+    assert float(rel_i[keep].max()) < 2e-4, rel_i[:n + 1]
+    assert float(rel_m[keep].max()) < 1e-5, rel_m[:n + 1]
+    assert bool(torch.isfinite(invstd).all())
+    ops.assert_no_timeouts("split_bn_shared_pivot")
+
+
+def test_sync_bn_node_on_a_one_rank_group_equals_the_local_node(report, tmp_path):
+    """`_SyncBNActFn` through _train_bn_act + enable_sync_bn on a world-size-1 group (file store, created and destroyed
+    here): within the bound of fp64, and equal to `_BNActFn` on the same tensors up to the fp32 summation order (the two
+    sum about different pivots)."""
+    import torch.distributed as dist
+    u = R.BN[0]
+    op = R.make_operands(u)
+    local, _, _ = _run(op, "bn")
+    assert not dist.is_initialized()
+    dist.init_process_group("gloo", store=dist.FileStore(str(tmp_path / "store"), 1), rank=0, world_size=1)
+    try:
+        mods = _modules(op)
+        M.enable_sync_bn(mods[1])
+        sync, _, nodes = _run(op, "bn", mods=mods)
+        assert nodes == ["_SyncBNActFnBackward"], nodes
+        mods = _modules(op)
+        M.enable_sync_bn(mods[1])
+        _same_bits(sync, _run(op, "bn", mods=mods)[0])
+    finally:
+        dist.destroy_process_group()
+    expect = _expected_outputs(op, u.need, "bn")
+    _compare(report, u.name + ".sync", sync, op, expect)
+    _compare(report, u.name + ".local", local, op, expect)
+    for k in expect:
+        report("train_nodes.%s.sync_vs_local.%s.max" % (u.name, k), R.errors(sync[k], local[k])[0])
+    for k in ("mean", "invstd", "running_mean", "running_var"):
+        assert R.errors(sync[k], local[k])[0] < 1e-5, k
+    assert R.errors(sync["y"], local["y"])[0] <= 2.0 ** -7
+    ops.assert_no_timeouts(u.name)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the loss node
+
+@pytest.mark.parametrize("gap", [0.0, 50.0, 90.0, 120.0, 200.0])
+def test_weighted_ce_at_large_logit_gaps_vs_fp64(gap, report):
+    """ops.weighted_ce_fwd / bwd (csrc/loss.hip) with the target class `gap` below the maximum logit and class weights
+    that include 0, against F.cross_entropy(weight=...) in fp64.  -w * log(exp(x_t - max) / sum) is +inf (0 * inf = NaN
+    for a zero-weight class) once exp underflows near a gap of 88 - 104; max + log(sum) - x_t is finite.  Measured with
+    the quotient form: finite and within 1e-7 at gaps 0, 50 and 90, loss = NaN at 120 (reference 56.638) and at 200
+    (reference 95.013); the forward now takes the stable form."""
+    g = torch.Generator().manual_seed(int(gap) + 3)
+    B, C, H, W = 2, 4, 16, 12
+    logits = torch.randn(B, C, H, W, generator=g)
+    tgt = torch.randint(0, C, (B, H, W), generator=g)
+    if gap:
+        top = logits.max(1, keepdim=True).values
+        far = torch.rand(B, 1, H, W, generator=g) < 0.5          # half of the pixels get the large gap
+        logits = torch.where(far & (torch.arange(C).view(1, C, 1, 1) == tgt.unsqueeze(1)), top - gap, logits)
+    weight = torch.tensor([1.0, 0.0, 5.0, 10.0])
+    assert int((tgt == 1).sum()) > 0
+    ld = logits.double().requires_grad_(True)
+    ref = torch.nn.functional.cross_entropy(ld, tgt, weight=weight.double())
+    ref_g, = torch.autograd.grad(ref, ld)
+    lg, tg, wg = logits.cuda(), tgt.cuda(), weight.cuda()
+    loss, sums = ops.weighted_ce_fwd(lg, tg, wg)
+    grad = ops.weighted_ce_bwd(lg, tg, wg, sums, torch.ones((), device="cuda"))
+    loss2, sums2 = ops.weighted_ce_fwd(lg, tg, wg)
+    assert torch.equal(loss, loss2)
+    assert torch.equal(grad, ops.weighted_ce_bwd(lg, tg, wg, sums2, torch.ones((), device="cuda")))
+    e_loss = abs(float(loss) - float(ref)) / abs(float(ref))
+    e_grad = R.errors(grad, ref_g)
+    print("weighted_ce gap %g: loss %r reference %.9g" % (gap, float(loss), float(ref)))
+    report("train_nodes.weighted_ce.gap%d.loss_rel" % gap, e_loss if e_loss == e_loss else float("inf"))
+    report("train_nodes.weighted_ce.gap%d.grad.max" % gap, e_grad[0])
+    assert e_loss <= R.MIN_F32, (float(loss), float(ref))
+    assert e_grad[0] <= R.MIN_F32 and e_grad[1] <= R.MIN_F32, e_grad
+    ops.assert_no_timeouts("weighted_ce")
