@@ -746,6 +746,31 @@ int lss_head1x1_bwd(const void* y, const float* head_w, const float* head_b, con
                     long long HW, int Cin, int K, float* workspace, void* dy, float* d_head_w, float* d_head_b,
                     void* stream);
 
+/* ---------------------------------------------------------------------------
+ * Validation metrics of the segmentation head in one pass: confusion-matrix counts and the weighted cross-entropy.
+ * replaces: ConfusionMatrix.update (src/tools.py:541-551: mask, n*a + b, bincount, reshape, +=), the
+ *           `preds.argmax(1)` in front of it and `total_loss += loss_fn(preds, binimgs).item() * preds.shape[0]`
+ *           of get_val_info / get_val_info_new (src/tools.py:281-282, 322).
+ *   logits (B, C, HW) NCHW contiguous, dtype LSS_DT_F32 or LSS_DT_BF16, 1 <= C <= 16, B*HW < 2^31;
+ *   target (B, HW) int64: a pixel with target t outside [0, C) counts nowhere and carries loss weight 0;
+ *   prediction p = the FIRST maximal class, a NaN counting as the maximum (torch.argmax); confmat[t*C + p] += 1.
+ *   confmat (C*C) int64, a running total: the call ADDS to it.
+ *   class_weight (C) fp32 or NULL.  With weights: batch_loss[0] = sum w[t] (logsumexp(x) - x_t) / sum w[t] in fp32
+ *   (NaN when every target is ignored), and, when loss_acc is given, loss_acc[0] += (double)batch_loss * B.
+ *   Without: batch_loss and loss_acc are not touched.
+ * lss_seg_eval_update_labels: the prediction comes from an int64 label tensor pred (n) instead (target (n));
+ *   a pred outside [0, C) on a counted target adds 1 to invalid[0] and nothing to the matrix.
+ * workspace: lss_seg_eval_workspace_bytes(C) bytes (0 for an unsupported C).  Two launches, no atomics on global
+ * memory, per-workgroup partials summed in a fixed order: the counts are exact, the loss is bit-reproducible.
+ * Argument checks: LSS_E_NULL, LSS_E_SHAPE (sizes <= 0, C > 16, B*HW >= 2^31), LSS_E_LAYOUT (dtype), LSS_E_ALIGN
+ * (element alignment), LSS_E_WORKSPACE; nothing is written when a check fails. */
+size_t lss_seg_eval_workspace_bytes(int C);
+int lss_seg_eval_update(const void* logits, int dtype, const long long* target, const float* class_weight, int B, int C,
+                        long long HW, void* workspace, size_t workspace_bytes, long long* confmat, float* batch_loss,
+                        double* loss_acc, void* stream);
+int lss_seg_eval_update_labels(const long long* pred, const long long* target, long long n, int C, void* workspace,
+                               size_t workspace_bytes, long long* confmat, long long* invalid, void* stream);
+
 /* ---- data-parallel gradient step (the reference has no collective on this path: its loop is
  * `loss.backward(); clip_grad_norm_(5.0); opt.step()`, train.py:63-65, on one device) --------------------------
  * One process per GPU; the flat fp32 gradient buffer (every p.grad is a view of it) is summed in place over

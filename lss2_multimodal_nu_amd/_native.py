@@ -111,6 +111,9 @@ SIGNATURES = {
     "lss_head_ce_bwd": (_i, [_vp] * 5 + [ctypes.c_longlong, _i, _i] + [_vp] * 7),
     "lss_head1x1_fwd": (_i, [_vp] * 3 + [ctypes.c_longlong, ctypes.c_longlong, _i, _i, _vp, _vp]),
     "lss_head1x1_bwd": (_i, [_vp] * 4 + [ctypes.c_longlong, ctypes.c_longlong, _i, _i] + [_vp] * 5),
+    "lss_seg_eval_workspace_bytes": (_sz, [_i]),
+    "lss_seg_eval_update": (_i, [_vp, _i, _vp, _vp, _i, _i, ctypes.c_longlong, _vp, _sz, _vp, _vp, _vp, _vp]),
+    "lss_seg_eval_update_labels": (_i, [_vp, _vp, ctypes.c_longlong, _i, _vp, _sz, _vp, _vp, _vp]),
     "lss_rccl_unique_id_bytes": (_sz, []),
     "lss_rccl_version": (_i, [_vp]),
     "lss_rccl_get_unique_id": (_i, [_vp]),

@@ -35,6 +35,8 @@ SOURCES = {
     "conv_wgrad.hip": [],
     "bn_train.hip": [],
     "loss.hip": [],
+    # the double loss accumulator must round product and sum as the host's `total += loss * B` does
+    "metrics.hip": ["-ffp-contract=off"],
     "optim.hip": [],
     "rccl_bucket.hip": [],  # host code only: RCCL resolved with dlsym at run time (no -lrccl)
 }

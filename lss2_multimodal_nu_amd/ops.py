@@ -1381,6 +1381,86 @@ def head1x1_bwd(y, head_w, head_b, grad_logits):
     return dy, dw, db
 
 
+_seg_eval_ws = {}
+SEG_EVAL_MAXC = 16
+_SEG_EVAL_DT = {torch.float32: DT_F32, torch.bfloat16: DT_BF16}
+
+
+def _seg_eval_workspace(C, device):
+    key = (C, str(device))
+    ws = _seg_eval_ws.get(key)
+    if ws is None:
+        nbytes = N.lib().lss_seg_eval_workspace_bytes(C)
+        if nbytes == 0:
+            raise ValueError("the fused confusion-matrix pass supports 1..%d classes (got %d)" % (SEG_EVAL_MAXC, C))
+        ws = _seg_eval_ws[key] = torch.empty(nbytes // 4, dtype=torch.int32, device=device)
+    return ws
+
+
+def _seg_eval_counter(t, name, numel, dtype=torch.int64):
+    if t.dtype != dtype or not t.is_cuda or not t.is_contiguous() or t.numel() != numel:
+        raise ValueError("%s must be a contiguous %s GPU tensor of %d elements" % (name, dtype, numel))
+    return t
+
+
+def seg_eval_update(logits, target, confmat, class_weight=None, loss_acc=None, invalid=None):
+    """One pass over the segmentation logits of a batch (csrc/metrics.hip): `confmat` (C, C) int64 += the counts of
+    (target, first maximal class) over the pixels whose target lies in [0, C); with `class_weight` (C) fp32 also the
+    batch's weighted cross-entropy, returned as a 0-d fp32 tensor, and `loss_acc` (1 double) += loss * B.  logits
+    (B, C, ...) contiguous fp32 or bf16, target (B, ...) contiguous int64.  Two launches, no host synchronisation.
+    `invalid` (1 int64) is only checked: an argmax is always a class, so this form never adds to it."""
+    if logits.dtype not in _SEG_EVAL_DT or not logits.is_cuda or not logits.is_contiguous() or logits.dim() < 2:
+        raise ValueError("logits must be a contiguous fp32 or bf16 GPU tensor of shape (B, C, ...)")
+    B, C = logits.shape[:2]
+    if not 1 <= C <= SEG_EVAL_MAXC or logits.numel() == 0:
+        raise ValueError("logits need 1..%d classes and at least one pixel (got shape %s)"
+                         % (SEG_EVAL_MAXC, tuple(logits.shape)))
+    HW = logits.numel() // (B * C)
+    if B * HW >= 2 ** 31:
+        raise ValueError("B * H * W must stay below 2^31")
+    if (target.dtype != torch.int64 or not target.is_cuda or not target.is_contiguous() or target.numel() != B * HW
+            or target.shape[0] != B):
+        raise ValueError("target must be a contiguous int64 GPU tensor of shape (B, ...) matching the logits")
+    _seg_eval_counter(confmat, "confmat", C * C)
+    if invalid is not None:
+        _seg_eval_counter(invalid, "invalid", 1)
+    loss = None
+    if class_weight is not None:
+        _f32c(class_weight, "class_weight", (C,))
+        if loss_acc is not None:
+            _seg_eval_counter(loss_acc, "loss_acc", 1, torch.float64)
+        loss = torch.empty(1, dtype=torch.float32, device=logits.device)
+    elif loss_acc is not None:
+        raise ValueError("loss_acc needs class_weight")
+    ws = _seg_eval_workspace(C, logits.device)
+    with _timed("seg_eval_update"):
+        N.check(N.lib().lss_seg_eval_update(N.ptr(logits), _SEG_EVAL_DT[logits.dtype], N.ptr(target), N.ptr(class_weight),
+                                            B, C, HW, N.ptr(ws), ws.numel() * 4, N.ptr(confmat), N.ptr(loss),
+                                            N.ptr(loss_acc), N.stream()), "lss_seg_eval_update")
+    return None if loss is None else loss.view(())
+
+
+def seg_eval_update_labels(pred, target, confmat, invalid):
+    """`confmat` (C, C) int64 += the counts of (target, pred) over the elements whose target lies in [0, C); pred and
+    target contiguous int64 GPU tensors of one size.  A pred outside [0, C) on a counted target adds 1 to `invalid`
+    (1 int64) instead of the matrix.  Two launches, no host synchronisation."""
+    C = confmat.shape[0] if confmat.dim() == 2 else 0
+    if not 1 <= C <= SEG_EVAL_MAXC:
+        raise ValueError("confmat must be (C, C) with 1..%d classes" % SEG_EVAL_MAXC)
+    _seg_eval_counter(confmat, "confmat", C * C)
+    _seg_eval_counter(invalid, "invalid", 1)
+    n = pred.numel()
+    if not 0 < n < 2 ** 31:
+        raise ValueError("pred needs 1..2^31-1 elements")
+    _seg_eval_counter(pred, "pred", n)
+    _seg_eval_counter(target, "target", n)
+    ws = _seg_eval_workspace(C, pred.device)
+    with _timed("seg_eval_update"):
+        N.check(N.lib().lss_seg_eval_update_labels(N.ptr(pred), N.ptr(target), n, C, N.ptr(ws), ws.numel() * 4,
+                                                   N.ptr(confmat), N.ptr(invalid), N.stream()),
+                "lss_seg_eval_update_labels")
+
+
 def pack_conv_weight_s2d(w_oihw, pad):
     """OIHW fp32 of a stride-2 k x k conv -> bf16 [tap'][Cout][4*Cin] for conv2d_s2_nhwc."""
     Cout, Cin, K, K2 = w_oihw.shape
