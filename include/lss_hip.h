@@ -175,15 +175,6 @@ int lss_depth_fuse_softmax_fwd(const float* d3, const float* d4, const float* w_
                                const float* scale, const float* shift, int BN, int D, int H, int W,
                                int H4, int W4, float* depth, void* stream);
 
-/* K3 (voxel ids + histogram, no geom output) and K2 (f32-MFMA depthnet + softmax) in ONE launch: the
- * two are independent and neither fills the chip, so their workgroups share it.  Same arguments and
- * results as lss_points_to_voxels + lss_depthnet_softmax_fwd(math = LSS_DT_F32). */
-int lss_depthnet_voxels_fwd(const float* frustum, const float* inv_post_rots, const float* post_trans,
-                            const float* combine, const float* trans, const float* dx, const float* bx,
-                            const float* x, const float* w, const float* bias, int B, int N, int D, int fH,
-                            int fW, int Cin, int C, int X, int Y, int Z, int32_t* voxel,
-                            int32_t* vox_count, float* depth, float* feat, void* stream);
-
 /* ---------------------------------------------------------------------------
  * K5/K6  fused lift + splat: bev[v, c] = sum_{p in voxel v} w[p] * feat[row(p), c]
  *        (w = the depth weight K4 stored next to the point id)
@@ -599,29 +590,41 @@ int lss_conv2d_head_fwd(const void* x, const void* x2, const void* w_packed, con
                         int B, int H, int W, int Cx, int C2, int up, int Cout, int head_n,
                         int relu, void* stream);
 
-/* Lift-splat of depth / context tensors that other kernels produced - the vovnet model's depth heads and
- * CamEncodeV2 (replaces src/model_vovnet_transformer.py:513-554 `get_voxels`' geometry + voxel_pooling for those
- * tensors): K3 geometry, bucketing and splat behind one call, on the region-bucketed pipeline when the problem fits
- * it (lss_region_pipeline_ok; C = 64 or 128), else K3 -> K4 -> K5.
- *   depth (B*N, D, fH, fW) fp32 softmax weights; feat (B*N*fH*fW, C) fp32 channels-last context
- *   workspace words as lss_lift_splat_forward; bev / layout as lss_lift_splat_fwd */
-int lss_lift_splat_from_heads(const float* frustum, const float* inv_post_rots, const float* post_trans,
-                              const float* combine, const float* trans, const float* dx, const float* bx,
-                              const float* depth, const float* feat, int B, int N, int D, int fH, int fW, int C,
-                              int X, int Y, int Z, int32_t* voxel, int32_t* vox_count, int32_t* vox_list,
-                              int32_t* entries, int32_t* cursor, void* bev, int layout, void* stream);
-
-/* Descriptor form of lss_lift_splat_forward / _hostcal / _from_heads (same replaced reference lines:
- * src/model_BEV_TXT.py:50-126 get_geometry + get_cam_feats + voxel_pooling, src/modules.py:82-84, src/tools.py:181-218),
- * with one more workspace: `direct_entries` (lss_lift_splat_direct_bytes(...) bytes, 8-byte aligned, contents
+/* The whole lift-splat level in one call: every form of it is described by one lss_lift_splat_desc_t.
+ * replaces: src/model_BEV_TXT.py:50-126 (get_geometry + get_cam_feats + voxel_pooling), src/modules.py:82-84,
+ *           src/tools.py:181-218; with x == NULL, src/model_vovnet_transformer.py:513-554 (`get_voxels`' geometry +
+ *           voxel_pooling of the depth / context tensors of the vovnet depth heads and CamEncodeV2).
+ * Operands and workspaces as the individual entries (lss_points_to_voxels, lss_depthnet_softmax_fwd, lss_bucket_points,
+ * lss_lift_splat_fwd); three forms:
+ *   x != NULL, calib_host == NULL : K3 + K2 + K4 + K5.  depth (B*N, D, fH, fW) and feat (B*N*fH*fW, C) are OUTPUTS.
+ *   x != NULL, calib_host != NULL : the same with the four per-camera arrays handed over as ONE HOST buffer of B*N*24
+ *       floats, [inv_post_rots (B*N*9) | combine (B*N*9) | post_trans (B*N*3) | trans (B*N*3)]: read during the call,
+ *       they travel inside the kernel arguments (B*N <= 36) - no H2D copy, no staging buffer, one launch boundary
+ *       less.  inv_post_rots .. trans are ignored; f32 depthnet math only (else LSS_E_LAYOUT).
+ *   x == NULL : depth (softmax weights) and feat (channels-last context) are INPUTS produced by other kernels; w, bias,
+ *       Cin and math are ignored; C = 64 or 128.  Pointers, sizes, C and layout are checked up front.
+ * With math = LSS_DT_F32 or x == NULL, C = 64 or 128 and a problem that fits (lss_region_pipeline_ok: 64*Z <= 256,
+ * B*X*Y*Z large enough to hold the region words below, bev 16-byte aligned) it runs the REGION-BUCKETED pipeline, three
+ * launches:
+ *   1. K2 || K3: depthnet + softmax (for D <= 64, C <= 64 two workgroups per 16-pixel tile: the depth rows + softmax
+ *      and the context rows; the K sum is associated in 32-deep blocks, so depth / feat may differ from
+ *      lss_depthnet_softmax_fwd's in the last ulp; x == NULL: the max |feature| of each tile instead)  ||  points ->
+ *      voxel ids, each workgroup counting its 256 points per 8 x 8-cell region in LDS and issuing one global atomic
+ *      per non-empty region (no per-point atomics);
+ *   2. fill: per-workgroup LDS ranks + one global atomic per (workgroup, region) -> entries grouped by region;
+ *   3. region splat: one workgroup per region, int64 fixed-point sums in an LDS tile (associative, so the
+ *      result is bit-reproducible whatever order the atomics produced), coalesced BEV stores incl. zeros.
+ * It lays its words out inside the same workspace: vox_count = [region_count | region_cursor] (zero on entry, zero
+ * on return, like the voxel histogram), vox_list = [region_start | per-workgroup max|feature|], entries as K4's,
+ * voxel as K3's (exact ids; the backward needs them).  Otherwise (bf16 depthnet math, Z > 4, LSS_SPLAT_LEGACY=1)
+ * the voxel-list pipeline K3 -> K2 -> K4 -> K5 of the individual entries runs.
+ * `direct_entries` is one more workspace (lss_lift_splat_direct_bytes(...) bytes, 8-byte aligned, contents
  * irrelevant).  With it the region pipeline runs as TWO launches - the geometry workgroups write their points straight
  * into fixed-capacity per-region buckets, the splat gathers the depth weights itself - instead of three (no fill
  * launch).  A region that overflows its bucket (1024 points; hi-res rigs do, next to the ego vehicle) sends the rest
  * to one overflow list in the same workspace (65 536 records); if that overflows too (degenerate calibrations only) the
  * region is rebuilt from the voxel ids: results are the exact, order-independent fixed-point sums every way.  NULL / too
- * small: the three-launch form.
- *   calib_host != NULL : host calibration, B*N <= 36 (inv_post_rots .. trans ignored), f32 depthnet math only
- *   x == NULL          : depth (B*N, D, fH, fW) and feat (B*N*fH*fW, C) are INPUTS (the vovnet heads' form) */
+ * small: the three-launch form. */
 typedef struct lss_lift_splat_desc {
   const float *frustum, *inv_post_rots, *post_trans, *combine, *trans, *calib_host, *dx, *bx;
   const float *x, *w, *bias;
@@ -635,9 +638,9 @@ typedef struct lss_lift_splat_desc {
 size_t lss_lift_splat_direct_bytes(int B, int N, int D, int fH, int fW, int C, int X, int Y, int Z);
 int lss_lift_splat_forward_desc(const lss_lift_splat_desc_t* desc, void* stream);
 
-/* 1 when lss_lift_splat_forward (f32 depthnet math) runs (B,N,D,fH,fW,C | X,Y,Z) on the region-bucketed pipeline
- * (K2 || K3 with LDS region histograms -> region fill -> fixed-point region splat), 0 when the problem exceeds its
- * limits and the voxel-list pipeline (K3, K4, K2, K5) is used.  Honours LSS_SPLAT_LEGACY. */
+/* 1 when lss_lift_splat_forward_desc (f32 depthnet math, or x == NULL) runs (B,N,D,fH,fW,C | X,Y,Z) on the
+ * region-bucketed pipeline (K2 || K3 with LDS region histograms -> region fill -> fixed-point region splat), 0 when
+ * the problem exceeds its limits and the voxel-list pipeline (K3, K4, K2, K5) is used.  Honours LSS_SPLAT_LEGACY. */
 int lss_region_pipeline_ok(int B, int N, int D, int fH, int fW, int C, int X, int Y, int Z);
 
 /* ---------------------------------------------------------------------------
@@ -659,27 +662,6 @@ typedef struct lss_conv_launch {
 /* Enqueue `n` conv launches in order on `stream`; returns the first non-zero code. */
 int lss_conv2d_sequence(const lss_conv_launch_t* launches, int n, void* stream);
 
-/* The whole lift-splat level in one call (same arguments as the individual entries).
- * With math = LSS_DT_F32 (and 64*Z <= 256, B*X*Y*Z large enough to hold the region words below) it runs the
- * REGION-BUCKETED pipeline, three launches:
- *   1. K2 || K3: depthnet + softmax (for D <= 64, C <= 64 two workgroups per 16-pixel tile: the depth rows + softmax
- *      and the context rows; the K sum is associated in 32-deep blocks, so depth / feat may differ from
- *      lss_depthnet_softmax_fwd's in the last ulp)  ||  points -> voxel ids, each workgroup counting its 256 points per
- *      8 x 8-cell region in LDS and issuing one global atomic per non-empty region (no per-point atomics);
- *   2. fill: per-workgroup LDS ranks + one global atomic per (workgroup, region) -> entries grouped by region;
- *   3. region splat: one workgroup per region, int64 fixed-point sums in an LDS tile (associative, so the
- *      result is bit-reproducible whatever order the atomics produced), coalesced BEV stores incl. zeros.
- * It lays its words out inside the same workspace: vox_count = [region_count | region_cursor] (zero on entry, zero
- * on return, like the voxel histogram), vox_list = [region_start | per-workgroup max|feature|], entries as below,
- * voxel as below (exact ids; the backward needs them).  Otherwise (bf16 depthnet math, Z > 4, LSS_SPLAT_LEGACY=1)
- * the voxel-list pipeline K3 -> K2 -> K4 -> K5 of the individual entries runs. */
-int lss_lift_splat_forward(const float* frustum, const float* inv_post_rots, const float* post_trans,
-                           const float* combine, const float* trans, const float* dx, const float* bx,
-                           const float* x, const float* w, const float* bias, int B, int N, int D,
-                           int fH, int fW, int Cin, int C, int X, int Y, int Z, int32_t* voxel,
-                           int32_t* vox_count, int32_t* vox_list, int32_t* entries, int32_t* cursor,
-                           float* depth, float* feat, void* bev, int layout, int math, void* stream);
-
 /* Position-wise feed-forward block of the BEV transformer layer in one launch (the hidden activation never
  * leaves the CU): y = x + b2 + W2 . gelu(W1 . x + b1), erf GELU.
  * ref: src/transformer_modules.py:170-172 (linear1 / activation / linear2) + the residual add of :208.
@@ -698,22 +680,6 @@ int lss_ffn_fused_fwd(const void* x, const void* w1, const float* b1, const void
 int lss_linear_res_ln_fwd(const void* x, const void* w, const float* bias, const void* residual, long long M,
                           int d_model, float* y, const float* ln_gamma, const float* ln_beta, float ln_eps,
                           void* y_ln, void* stream);
-
-/* Host-calibration forms: the four per-camera arrays arrive as ONE HOST buffer of B*N*24 floats,
- * [inv_post_rots (B*N*9) | combine (B*N*9) | post_trans (B*N*3) | trans (B*N*3)], are read during the call
- * and travel inside the kernel arguments (B*N <= 36): no H2D copy, no staging buffer, one launch boundary
- * less.  Otherwise identical to lss_depthnet_voxels_fwd / lss_lift_splat_forward (f32 depthnet math). */
-int lss_depthnet_voxels_hostcal_fwd(const float* frustum, const float* calib_host, const float* dx,
-                                    const float* bx, const float* x, const float* w, const float* bias,
-                                    int B, int N, int D, int fH, int fW, int Cin, int C, int X, int Y,
-                                    int Z, int32_t* voxel, int32_t* vox_count, float* depth, float* feat,
-                                    void* stream);
-int lss_lift_splat_forward_hostcal(const float* frustum, const float* calib_host, const float* dx,
-                                   const float* bx, const float* x, const float* w, const float* bias,
-                                   int B, int N, int D, int fH, int fW, int Cin, int C, int X, int Y,
-                                   int Z, int32_t* voxel, int32_t* vox_count, int32_t* vox_list,
-                                   int32_t* entries, int32_t* cursor, float* depth, float* feat,
-                                   void* bev, int layout, void* stream);
 
 /* ---------------------------------------------------------------------------
  * Fused 1x1 head + log-softmax + weighted NLL, forward and backward.

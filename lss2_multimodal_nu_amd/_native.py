@@ -40,11 +40,8 @@ SIGNATURES = {
     "lss_pointwise_conv_bwd_workspace_bytes": (_sz, [_i] * 4),
     "lss_pointwise_conv_bwd": (_i, [_vp, _i, ctypes.c_longlong, _vp, _i, _vp] + [_i] * 4 + [_vp, _sz] + [_vp] * 4),
     "lss_layernorm_fwd": (_i, [_vp, _i, _vp, _vp, ctypes.c_longlong, _i, ctypes.c_float, _vp, _i, _vp]),
-    "lss_depthnet_voxels_fwd": (_i, [_vp] * 10 + [_i] * 10 + [_vp] * 5),
     "lss_linear_res_ln_fwd": (_i, [_vp] * 4 + [ctypes.c_longlong, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
     "lss_ffn_fused_fwd": (_i, [_vp] * 5 + [ctypes.c_longlong, _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
-    "lss_depthnet_voxels_hostcal_fwd": (_i, [_vp] * 7 + [_i] * 10 + [_vp] * 5),
-    "lss_lift_splat_forward_hostcal": (_i, [_vp] * 7 + [_i] * 10 + [_vp] * 8 + [_i, _vp]),
     "lss_lift_splat_fwd": (_i, [_vp] * 3 + [_i] * 9 + [_vp, _i, _vp]),
     "lss_lift_splat_bwd": (_i, [_vp, _i, _vp, _vp, _vp] + [_i] * 9 + [_vp, _vp]),
     "lss_segmented_sum": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
@@ -101,9 +98,7 @@ SIGNATURES = {
     "lss_conv2d_head_fwd": (_i, [_vp] * 8 + [_i] * 9 + [_vp]),
     "lss_conv2d_s2_dual_fwd": (_i, [_vp] * 6 + [_i] * 9 + [_vp]),
     "lss_conv2d_sequence": (_i, [_vp, _i, _vp]),
-    "lss_lift_splat_forward": (_i, [_vp] * 10 + [_i] * 10 + [_vp] * 8 + [_i, _i, _vp]),
     "lss_region_pipeline_ok": (_i, [_i] * 9),
-    "lss_lift_splat_from_heads": (_i, [_vp] * 9 + [_i] * 9 + [_vp] * 6 + [_i, _vp]),
     "lss_lift_splat_direct_bytes": (_sz, [_i] * 9),
     "lss_lift_splat_forward_desc": (_i, [_vp, _vp]),
     "lss_head_ce_workspace_bytes": (_sz, [_i]),

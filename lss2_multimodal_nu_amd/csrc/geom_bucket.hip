@@ -558,36 +558,34 @@ extern "C" const char* lss_error_string(int code) {
   return "lss: unknown error";
 }
 
-// K3 (voxel ids + histogram) and K2 (depthnet + softmax, f32 MFMA) as one launch; arguments as
+// K3 (voxel ids + histogram) and K2 (depthnet + softmax, f32 MFMA) as one launch (region_plan.h); checks as
 // lss_points_to_voxels (without geom) and lss_depthnet_softmax_fwd (math = LSS_DT_F32).
-static int depthnet_voxels_impl(const float* frustum, const float* inv_post_rots, const float* post_trans,
-                                const float* combine, const float* trans, const float* calib_host, const float* dx,
-                                const float* bx, const float* x, const float* w, const float* bias, int B, int N,
-                                int D, int fH, int fW, int Cin, int C, int X, int Y, int Z, int32_t* voxel,
-                                int32_t* vox_count, float* depth, float* feat, void* stream,
-                                const LssRegionPlan* plan = nullptr) {
-  LSS_CHECK_PTR(frustum);
-  if (calib_host == nullptr) {
-    LSS_CHECK_PTR(inv_post_rots); LSS_CHECK_PTR(post_trans); LSS_CHECK_PTR(combine); LSS_CHECK_PTR(trans);
+int lss_depthnet_voxels(const lss_lift_splat_desc_t& d, const LssRegionPlan* plan, void* stream) {
+  const float* const calib_host = d.calib_host;
+  const int B = d.B, N = d.N, D = d.D, fH = d.fH, fW = d.fW, Cin = d.Cin, C = d.C, X = d.X, Y = d.Y, Z = d.Z;
+  FusedK2K3Args a = {};
+  LSS_CHECK_PTR(d.frustum);
+  if (calib_host == nullptr) {  // (host calibration: the four device arrays are ignored)
+    LSS_CHECK_PTR(d.inv_post_rots); LSS_CHECK_PTR(d.post_trans); LSS_CHECK_PTR(d.combine); LSS_CHECK_PTR(d.trans);
+    a.inv_post_rots = d.inv_post_rots; a.post_trans = d.post_trans; a.combine = d.combine; a.trans = d.trans;
   } else if (B * N > CAL_MAX) {
     return LSS_E_SHAPE;
   }
-  LSS_CHECK_PTR(dx); LSS_CHECK_PTR(bx); LSS_CHECK_PTR(voxel); LSS_CHECK_PTR(x);
-  LSS_CHECK_PTR(w); LSS_CHECK_PTR(bias); LSS_CHECK_PTR(depth); LSS_CHECK_PTR(feat);
+  LSS_CHECK_PTR(d.dx); LSS_CHECK_PTR(d.bx); LSS_CHECK_PTR(d.voxel); LSS_CHECK_PTR(d.x);
+  LSS_CHECK_PTR(d.w); LSS_CHECK_PTR(d.bias); LSS_CHECK_PTR(d.depth); LSS_CHECK_PTR(d.feat);
   LSS_CHECK_POS(B); LSS_CHECK_POS(N); LSS_CHECK_POS(D); LSS_CHECK_POS(fH); LSS_CHECK_POS(fW);
   LSS_CHECK_POS(X); LSS_CHECK_POS(Y); LSS_CHECK_POS(Z); LSS_CHECK_POS(Cin); LSS_CHECK_POS(C);
   const long long DHW = (long long)D * fH * fW, P = DHW * B * N, nvox = (long long)B * X * Y * Z;
   if (P >= (1LL << 31) || nvox >= (1LL << 31) || B * N > 65535 || Cin % 64 != 0 || X >= (1 << 24) ||
       Y >= (1 << 24) || Z >= (1 << 24))
     return LSS_E_SHAPE;
-  if ((reinterpret_cast<uintptr_t>(w) & 15) != 0) return LSS_E_ALIGN;
-  FusedK2K3Args a;
-  a.x = x; a.w = w; a.bias = bias; a.Cin = Cin; a.HW = fH * fW; a.D = D; a.C = C; a.depth = depth; a.feat = feat;
+  if ((reinterpret_cast<uintptr_t>(d.w) & 15) != 0) return LSS_E_ALIGN;
+  a.x = d.x; a.w = d.w; a.bias = d.bias; a.Cin = Cin; a.HW = fH * fW; a.D = D; a.C = C; a.depth = d.depth; a.feat = d.feat;
   a.gx2 = lss_cdiv(a.HW, lss_depthnet::PIX);
   a.n2 = a.gx2 * B * N;
-  a.frustum = frustum; a.inv_post_rots = inv_post_rots; a.post_trans = post_trans; a.combine = combine;
-  a.trans = trans; a.dx = dx; a.bx = bx; a.Ncam = N; a.DHW = (int)DHW; a.X = X; a.Y = Y; a.Z = Z;
-  a.voxel = voxel; a.vox_count = vox_count;
+  a.frustum = d.frustum; a.dx = d.dx; a.bx = d.bx; a.Ncam = N; a.DHW = (int)DHW; a.X = X; a.Y = Y; a.Z = Z;
+  // with a plan: no per-voxel histogram, no per-point global atomics
+  a.voxel = d.voxel; a.vox_count = plan != nullptr ? nullptr : d.vox_count;
   a.use_regions = plan != nullptr;
   a.diag = getenv("LSS_K2K3_DIAG") ? atoi(getenv("LSS_K2K3_DIAG")) : 0;
   a.k2_xcd = getenv("LSS_K2_XCD") == nullptr || atoi(getenv("LSS_K2_XCD")) != 0;
@@ -600,8 +598,6 @@ static int depthnet_voxels_impl(const float* frustum, const float* inv_post_rots
     a.rg.wg_absmax = plan->wg_absmax; a.rg.nRy = plan->nRy; a.rg.rps = plan->rps;
     a.rg.dentries = reinterpret_cast<int2*>(plan->dentries); a.rg.cap = plan->cap; a.rg.HW = fH * fW;
     a.rg.ovf = reinterpret_cast<int4*>(plan->ovf); a.rg.ovf_ctl = plan->ovf_ctl; a.rg.ovf_cap = plan->ovf_cap;
-  } else {
-    a.rg = RegionArgs{nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, 0, nullptr, nullptr, 0};
   }
   a.gx3 = lss_cdiv(DHW, 256);
   const long long nblk = (long long)a.n2 + (long long)a.gx3 * B * N;
@@ -653,38 +649,7 @@ static int depthnet_voxels_impl(const float* frustum, const float* inv_post_rots
   return lss_launch_status();
 }
 
-extern "C" int lss_depthnet_voxels_fwd(const float* frustum, const float* inv_post_rots, const float* post_trans,
-                                       const float* combine, const float* trans, const float* dx, const float* bx,
-                                       const float* x, const float* w, const float* bias, int B, int N, int D, int fH,
-                                       int fW, int Cin, int C, int X, int Y, int Z, int32_t* voxel,
-                                       int32_t* vox_count, float* depth, float* feat, void* stream) {
-  return depthnet_voxels_impl(frustum, inv_post_rots, post_trans, combine, trans, nullptr, dx, bx, x, w, bias, B, N, D,
-                              fH, fW, Cin, C, X, Y, Z, voxel, vox_count, depth, feat, stream);
-}
-
-// calib_host: HOST pointer to B*N*24 floats laid out [inv_post_rots (B*N*9) | combine (B*N*9) | post_trans (B*N*3) |
-// trans (B*N*3)] (= data.CalibrationPack.buffer); read during this call and shipped inside the kernel arguments.
-extern "C" int lss_depthnet_voxels_hostcal_fwd(const float* frustum, const float* calib_host, const float* dx,
-                                               const float* bx, const float* x, const float* w, const float* bias,
-                                               int B, int N, int D, int fH, int fW, int Cin, int C, int X, int Y,
-                                               int Z, int32_t* voxel, int32_t* vox_count, float* depth, float* feat,
-                                               void* stream) {
-  LSS_CHECK_PTR(calib_host);
-  return depthnet_voxels_impl(frustum, nullptr, nullptr, nullptr, nullptr, calib_host, dx, bx, x, w, bias, B, N, D, fH,
-                              fW, Cin, C, X, Y, Z, voxel, vox_count, depth, feat, stream);
-}
-
 int lss_region_k2_blocks(int B, int N, int fH, int fW) { return lss_cdiv(fH * fW, lss_depthnet::PIX) * B * N; }
-
-int lss_region_depthnet_voxels(const float* frustum, const float* inv_post_rots, const float* post_trans,
-                               const float* combine, const float* trans, const float* calib_host, const float* dx,
-                               const float* bx, const float* x, const float* w, const float* bias, int B, int N, int D,
-                               int fH, int fW, int Cin, int C, int X, int Y, int Z, int32_t* voxel, float* depth,
-                               float* feat, const LssRegionPlan& plan, void* stream) {
-  // vox_count = nullptr: no per-voxel histogram, no per-point global atomics on this path
-  return depthnet_voxels_impl(frustum, inv_post_rots, post_trans, combine, trans, calib_host, dx, bx, x, w, bias, B, N,
-                              D, fH, fW, Cin, C, X, Y, Z, voxel, nullptr, depth, feat, stream, &plan);
-}
 
 // Region pipeline for depth / context tensors that OTHER kernels produced (the vovnet depth heads + CamEncodeV2, ref
 // src/model_vovnet_transformer.py:22-122): launch 1 without the depthnet.  Blocks [0, n2): max |finite feature| of one
@@ -714,22 +679,20 @@ __global__ __launch_bounds__(256) void absmax_and_voxels_kernel(FusedK2K3Args a,
   }
 }
 
-int lss_region_voxels_absmax(const float* frustum, const float* inv_post_rots, const float* post_trans,
-                             const float* combine, const float* trans, const float* dx, const float* bx,
-                             const float* feat, int B, int N, int D, int fH, int fW, int C, int X, int Y, int Z,
-                             int32_t* voxel, const LssRegionPlan& plan, void* stream) {
-  LSS_CHECK_PTR(frustum); LSS_CHECK_PTR(inv_post_rots); LSS_CHECK_PTR(post_trans); LSS_CHECK_PTR(combine);
-  LSS_CHECK_PTR(trans); LSS_CHECK_PTR(dx); LSS_CHECK_PTR(bx); LSS_CHECK_PTR(feat); LSS_CHECK_PTR(voxel);
-  const long long DHW = (long long)D * fH * fW;
+int lss_region_voxels_absmax(const lss_lift_splat_desc_t& d, const LssRegionPlan& plan, void* stream) {
+  const int B = d.B, N = d.N, fH = d.fH, fW = d.fW;
+  LSS_CHECK_PTR(d.frustum); LSS_CHECK_PTR(d.inv_post_rots); LSS_CHECK_PTR(d.post_trans); LSS_CHECK_PTR(d.combine);
+  LSS_CHECK_PTR(d.trans); LSS_CHECK_PTR(d.dx); LSS_CHECK_PTR(d.bx); LSS_CHECK_PTR(d.feat); LSS_CHECK_PTR(d.voxel);
+  const long long DHW = (long long)d.D * fH * fW;
   if (DHW * B * N >= (1LL << 31) || B * N > 65535) return LSS_E_SHAPE;
   FusedK2K3Args a = {};
-  a.feat = const_cast<float*>(feat); a.HW = fH * fW; a.D = D; a.C = C;
+  a.feat = d.feat; a.HW = fH * fW; a.D = d.D; a.C = d.C;
   a.gx2 = lss_cdiv(a.HW, lss_depthnet::PIX);
   a.n2 = a.gx2 * B * N;
   if (plan.n2 != a.n2 || plan.rps != plan.nRx * plan.nRy) return LSS_E_WORKSPACE;
-  a.frustum = frustum; a.inv_post_rots = inv_post_rots; a.post_trans = post_trans; a.combine = combine;
-  a.trans = trans; a.dx = dx; a.bx = bx; a.Ncam = N; a.DHW = (int)DHW; a.X = X; a.Y = Y; a.Z = Z;
-  a.voxel = voxel; a.vox_count = nullptr; a.use_regions = 1;
+  a.frustum = d.frustum; a.inv_post_rots = d.inv_post_rots; a.post_trans = d.post_trans; a.combine = d.combine;
+  a.trans = d.trans; a.dx = d.dx; a.bx = d.bx; a.Ncam = N; a.DHW = (int)DHW; a.X = d.X; a.Y = d.Y; a.Z = d.Z;
+  a.voxel = d.voxel; a.vox_count = nullptr; a.use_regions = 1;
   a.rg.region_count = plan.region_count; a.rg.region_cursor = plan.region_cursor; a.rg.region_start = plan.region_start;
   a.rg.wg_absmax = plan.wg_absmax; a.rg.nRy = plan.nRy; a.rg.rps = plan.rps;
   a.rg.dentries = reinterpret_cast<int2*>(plan.dentries); a.rg.cap = plan.cap; a.rg.HW = fH * fW;
@@ -740,7 +703,7 @@ int lss_region_voxels_absmax(const float* frustum, const float* inv_post_rots, c
   size_t lds_bytes = (size_t)plan.rps * sizeof(int);
   if (lds_bytes < 64) lds_bytes = 64;
   if (lds_bytes > 64 * 1024) return LSS_E_SHAPE;
-  hipLaunchKernelGGL(absmax_and_voxels_kernel, dim3((unsigned)nblk), dim3(256), lds_bytes, lss_stream(stream), a, C);
+  hipLaunchKernelGGL(absmax_and_voxels_kernel, dim3((unsigned)nblk), dim3(256), lds_bytes, lss_stream(stream), a, d.C);
   return lss_launch_status();
 }
 

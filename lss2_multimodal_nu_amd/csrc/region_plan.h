@@ -9,6 +9,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "../../include/lss_hip.h"
+
 struct LssRegionPlan {
   int32_t* region_count;   // [B*rps]  zero between calls
   int32_t* region_cursor;  // [B*rps]  zero between calls
@@ -35,17 +37,15 @@ struct LssRegionPlan {
 
 constexpr int LSS_REGION_SIDE = 8;  // cells per region side
 
-// launch 1 (calib_host: HOST calibration buffer or nullptr, as lss_depthnet_voxels_hostcal_fwd)
-int lss_region_depthnet_voxels(const float* frustum, const float* inv_post_rots, const float* post_trans,
-                               const float* combine, const float* trans, const float* calib_host, const float* dx,
-                               const float* bx, const float* x, const float* w, const float* bias, int B, int N, int D,
-                               int fH, int fW, int Cin, int C, int X, int Y, int Z, int32_t* voxel, float* depth,
-                               float* feat, const LssRegionPlan& plan, void* stream);
-// launch 1 without the depthnet: depth / context come from other kernels (vovnet heads); feat (B*N*fH*fW, C) fp32
-int lss_region_voxels_absmax(const float* frustum, const float* inv_post_rots, const float* post_trans,
-                             const float* combine, const float* trans, const float* dx, const float* bx,
-                             const float* feat, int B, int N, int D, int fH, int fW, int C, int X, int Y, int Z,
-                             int32_t* voxel, const LssRegionPlan& plan, void* stream);
+// Launch 1 of the depthnet forms, and K2 || K3 of their voxel-list pipeline: depthnet + softmax (f32 MFMA)  ||  frustum
+// points -> voxel ids.  Reads the problem, the operands and the outputs from the descriptor (d.x / d.w / d.bias set).
+// d.calib_host (nullable): the HOST calibration buffer, shipped inside the kernel arguments instead of the four device
+// arrays.  plan (nullable): with it the geometry workgroups count per region in LDS (and, DIRECT, write the entries);
+// without it they fill the per-voxel histogram d.vox_count (nullable: no histogram).
+int lss_depthnet_voxels(const lss_lift_splat_desc_t& d, const LssRegionPlan* plan, void* stream);
+// launch 1 without the depthnet (d.x == NULL): d.depth / d.feat come from other kernels (vovnet heads); d.feat
+// (B*N*fH*fW, C) fp32
+int lss_region_voxels_absmax(const lss_lift_splat_desc_t& d, const LssRegionPlan& plan, void* stream);
 // launch 2
 int lss_region_fill(const int32_t* voxel, const float* depth, int B, int N, int D, int HW, int X, int Y, int Z,
                     const LssRegionPlan& plan, int32_t* entries, void* stream);

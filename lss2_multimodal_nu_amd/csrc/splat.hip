@@ -883,7 +883,7 @@ extern "C" size_t lss_lift_splat_direct_bytes(int B, int N, int D, int fH, int f
   return (size_t)B * rp.rps * LSS_DIRECT_CAP * 8 + (size_t)LSS_DIRECT_OVF * 16;
 }
 
-// Does lss_lift_splat_forward run this problem on the region-bucketed pipeline (f32 depthnet math assumed)?  The same
+// Does lss_lift_splat_forward_desc run this problem on the region-bucketed pipeline (f32 depthnet math assumed)?  The same
 // limits as region_plan_for, without touching a workspace: lets a test assert which pipeline produced its result.
 extern "C" int lss_region_pipeline_ok(int B, int N, int D, int fH, int fW, int C, int X, int Y, int Z) {
   if (B <= 0 || N <= 0 || D <= 0 || fH <= 0 || fW <= 0 || X <= 0 || Y <= 0 || Z <= 0 || (C != 64 && C != 128)) return 0;
@@ -940,147 +940,62 @@ static int region_splat_launch(const float* feat, const int32_t* entries, const 
   return lss_launch_status();
 }
 
-static int lift_splat_forward_impl(const float* frustum, const float* inv_post_rots, const float* post_trans,
-                                   const float* combine, const float* trans, const float* calib_host, const float* dx,
-                                   const float* bx, const float* x, const float* w, const float* bias, int B, int N,
-                                   int D, int fH, int fW, int Cin, int C, int X, int Y, int Z, int32_t* voxel,
-                                   int32_t* vox_count, int32_t* vox_list, int32_t* entries, int32_t* cursor,
-                                   float* depth, float* feat, void* bev, int layout, int math, void* stream,
-                                   void* direct_entries = nullptr, unsigned long long direct_bytes = 0) {
-  int rc;
-  // Region-bucketed pipeline (3 launches: K2 || K3 + LDS region histograms, fill, region splat) whenever the
-  // depthnet runs in f32 and the problem fits its limits; LSS_SPLAT_LEGACY=1 forces the voxel-list pipeline.
+// The fused lift-splat level (include/lss_hip.h: lss_lift_splat_desc_t).  Launch 1 is chosen once; then ONE region tail
+// or ONE voxel-list tail.
+//   d.x != NULL  depthnet forms: depth / feat are outputs.  Region pipeline whenever the depthnet runs in f32 and the
+//                problem fits the plan's limits (LSS_SPLAT_LEGACY=1 forces the voxel-list pipeline); argument checks
+//                are left to the entries called.
+//   d.x == NULL  depth / feat come from other kernels (vovnet depth heads, CamEncodeV2): checked here, up front; region
+//                pipeline when the problem fits it (C = 128 included), else K3 -> K4 -> K5.
+static int lift_splat_dispatch(const lss_lift_splat_desc_t& d, void* stream) {
+  const bool heads = d.x == nullptr;
+  const int HW = d.fH * d.fW;
+  if (heads) {
+    LSS_CHECK_PTR(d.depth); LSS_CHECK_PTR(d.feat); LSS_CHECK_PTR(d.voxel); LSS_CHECK_PTR(d.vox_count);
+    LSS_CHECK_PTR(d.vox_list); LSS_CHECK_PTR(d.entries); LSS_CHECK_PTR(d.cursor); LSS_CHECK_PTR(d.bev);
+    LSS_CHECK_POS(d.B); LSS_CHECK_POS(d.N); LSS_CHECK_POS(d.D); LSS_CHECK_POS(d.fH); LSS_CHECK_POS(d.fW);
+    LSS_CHECK_POS(d.X); LSS_CHECK_POS(d.Y); LSS_CHECK_POS(d.Z);
+    if (d.C != 64 && d.C != 128) return LSS_E_SHAPE;
+    if (d.layout < 0 || d.layout > 2) return LSS_E_LAYOUT;
+  } else if (d.calib_host != nullptr && d.math != LSS_DT_F32) {
+    return LSS_E_LAYOUT;
+  }
   LssRegionPlan rp;
-  if (math == LSS_DT_F32 && (C == 64 || C == 128) && layout >= 0 && layout <= 2 && vox_count != nullptr &&
-      vox_list != nullptr && entries != nullptr && bev != nullptr && B > 0 && N > 0 && D > 0 && fH > 0 && fW > 0 &&
-      X > 0 && Y > 0 && Z > 0 && (reinterpret_cast<uintptr_t>(bev) & 15) == 0 &&
-      region_plan_for(B, N, D, fH, fW, C, X, Y, Z, vox_count, vox_list, &rp, direct_entries, direct_bytes)) {
-    rc = lss_region_depthnet_voxels(frustum, inv_post_rots, post_trans, combine, trans, calib_host, dx, bx, x, w, bias,
-                                    B, N, D, fH, fW, Cin, C, X, Y, Z, voxel, depth, feat, rp, stream);
-    if (rc) return rc;
-    if (rp.dentries != nullptr) {  // direct form: launch 1 wrote the entries, no fill launch
-      const DirectArgs da = {depth, voxel, N, D * fH * fW, fH * fW};
-      return region_splat_launch(feat, entries, rp, B, C, X, Y, Z, bev, layout, lss_stream(stream), &da);
-    }
-    rc = lss_region_fill(voxel, depth, B, N, D, fH * fW, X, Y, Z, rp, entries, stream);
-    if (rc) return rc;
-    return region_splat_launch(feat, entries, rp, B, C, X, Y, Z, bev, layout, lss_stream(stream));
-  }
-  if (calib_host != nullptr) {
-    if (math != LSS_DT_F32) return LSS_E_LAYOUT;
-    rc = lss_depthnet_voxels_hostcal_fwd(frustum, calib_host, dx, bx, x, w, bias, B, N, D, fH, fW, Cin, C, X, Y, Z,
-                                         voxel, vox_count, depth, feat, stream);
-    if (rc) return rc;
-  } else if (math == LSS_DT_F32 && getenv("LSS_NO_K2K3") == nullptr) {
-    // K2 || K3 as one launch (independent, both latency-bound)
-    rc = lss_depthnet_voxels_fwd(frustum, inv_post_rots, post_trans, combine, trans, dx, bx, x, w, bias, B, N, D, fH,
-                                 fW, Cin, C, X, Y, Z, voxel, vox_count, depth, feat, stream);
-    if (rc) return rc;
-  } else {
-    rc = lss_points_to_voxels(frustum, inv_post_rots, post_trans, combine, trans, dx, bx, B, N, D, fH, fW, X, Y, Z,
-                              voxel, vox_count, nullptr, stream);
-    if (rc) return rc;
-    rc = lss_depthnet_softmax_fwd(x, w, bias, B * N, Cin, fH * fW, D, C, depth, feat, math, stream);
-    if (rc) return rc;
-  }
-  rc = lss_bucket_points(voxel, depth, B * N * D * fH * fW, D, fH * fW, B * X * Y * Z, vox_count, vox_list,
-                         entries, cursor, stream);
-  if (rc) return rc;
-  return lss_lift_splat_fwd(feat, vox_list, entries, B, N, D, fH, fW, C, X, Y, Z, bev, layout, stream);
-}
-
-// Lift-splat of depth / context tensors produced elsewhere (vovnet depth heads, CamEncodeV2): geometry + bucketing +
-// splat behind one call.  Region pipeline when the problem fits it (C = 128 included), else K3 -> K4 -> K5.
-static int lift_splat_from_heads_impl(const float* frustum, const float* inv_post_rots, const float* post_trans,
-                                      const float* combine, const float* trans, const float* dx, const float* bx,
-                                      const float* depth, const float* feat, int B, int N, int D, int fH, int fW,
-                                      int C, int X, int Y, int Z, int32_t* voxel, int32_t* vox_count,
-                                      int32_t* vox_list, int32_t* entries, int32_t* cursor, void* bev, int layout,
-                                      void* stream, void* direct_entries, unsigned long long direct_bytes) {
-  LSS_CHECK_PTR(depth); LSS_CHECK_PTR(feat); LSS_CHECK_PTR(voxel); LSS_CHECK_PTR(vox_count); LSS_CHECK_PTR(vox_list);
-  LSS_CHECK_PTR(entries); LSS_CHECK_PTR(cursor); LSS_CHECK_PTR(bev);
-  LSS_CHECK_POS(B); LSS_CHECK_POS(N); LSS_CHECK_POS(D); LSS_CHECK_POS(fH); LSS_CHECK_POS(fW);
-  LSS_CHECK_POS(X); LSS_CHECK_POS(Y); LSS_CHECK_POS(Z);
-  if (C != 64 && C != 128) return LSS_E_SHAPE;
-  if (layout < 0 || layout > 2) return LSS_E_LAYOUT;
+  const bool region =
+      (heads || d.math == LSS_DT_F32) && (d.C == 64 || d.C == 128) && d.layout >= 0 && d.layout <= 2 &&
+      d.vox_count != nullptr && d.vox_list != nullptr && d.entries != nullptr && d.bev != nullptr && d.B > 0 && d.N > 0 &&
+      d.D > 0 && d.fH > 0 && d.fW > 0 && d.X > 0 && d.Y > 0 && d.Z > 0 && (reinterpret_cast<uintptr_t>(d.bev) & 15) == 0 &&
+      region_plan_for(d.B, d.N, d.D, d.fH, d.fW, d.C, d.X, d.Y, d.Z, d.vox_count, d.vox_list, &rp, d.direct_entries,
+                      d.direct_bytes);
+  // launch 1
   int rc;
-  LssRegionPlan rp;
-  if ((reinterpret_cast<uintptr_t>(bev) & 15) == 0 &&
-      region_plan_for(B, N, D, fH, fW, C, X, Y, Z, vox_count, vox_list, &rp, direct_entries, direct_bytes)) {
-    rc = lss_region_voxels_absmax(frustum, inv_post_rots, post_trans, combine, trans, dx, bx, feat, B, N, D, fH, fW, C, X,
-                                  Y, Z, voxel, rp, stream);
-    if (rc) return rc;
-    if (rp.dentries != nullptr) {
-      const DirectArgs da = {depth, voxel, N, D * fH * fW, fH * fW};
-      return region_splat_launch(feat, entries, rp, B, C, X, Y, Z, bev, layout, lss_stream(stream), &da);
-    }
-    rc = lss_region_fill(voxel, depth, B, N, D, fH * fW, X, Y, Z, rp, entries, stream);
-    if (rc) return rc;
-    return region_splat_launch(feat, entries, rp, B, C, X, Y, Z, bev, layout, lss_stream(stream));
+  if (heads && region) {
+    rc = lss_region_voxels_absmax(d, rp, stream);
+  } else if (!heads && (region || d.calib_host != nullptr || (d.math == LSS_DT_F32 && getenv("LSS_NO_K2K3") == nullptr))) {
+    rc = lss_depthnet_voxels(d, region ? &rp : nullptr, stream);  // K2 || K3 (independent, both latency-bound)
+  } else {  // un-fused: K3, then K2 unless depth / feat are inputs
+    rc = lss_points_to_voxels(d.frustum, d.inv_post_rots, d.post_trans, d.combine, d.trans, d.dx, d.bx, d.B, d.N, d.D, d.fH,
+                              d.fW, d.X, d.Y, d.Z, d.voxel, d.vox_count, nullptr, stream);
+    if (rc == 0 && !heads)
+      rc = lss_depthnet_softmax_fwd(d.x, d.w, d.bias, d.B * d.N, d.Cin, HW, d.D, d.C, d.depth, d.feat, d.math, stream);
   }
-  rc = lss_points_to_voxels(frustum, inv_post_rots, post_trans, combine, trans, dx, bx, B, N, D, fH, fW, X, Y, Z, voxel,
-                            vox_count, nullptr, stream);
   if (rc) return rc;
-  rc = lss_bucket_points(voxel, depth, B * N * D * fH * fW, D, fH * fW, B * X * Y * Z, vox_count, vox_list, entries,
-                         cursor, stream);
+  if (region) {
+    const DirectArgs da = {d.depth, d.voxel, d.N, d.D * HW, HW};
+    if (rp.dentries == nullptr) {  // three-launch form: the fill (direct form: launch 1 wrote the entries itself)
+      rc = lss_region_fill(d.voxel, d.depth, d.B, d.N, d.D, HW, d.X, d.Y, d.Z, rp, d.entries, stream);
+      if (rc) return rc;
+    }
+    return region_splat_launch(d.feat, d.entries, rp, d.B, d.C, d.X, d.Y, d.Z, d.bev, d.layout, lss_stream(stream), &da);
+  }
+  rc = lss_bucket_points(d.voxel, d.depth, d.B * d.N * d.D * HW, d.D, HW, d.B * d.X * d.Y * d.Z, d.vox_count, d.vox_list,
+                         d.entries, d.cursor, stream);
   if (rc) return rc;
-  return lss_lift_splat_fwd(feat, vox_list, entries, B, N, D, fH, fW, C, X, Y, Z, bev, layout, stream);
+  return lss_lift_splat_fwd(d.feat, d.vox_list, d.entries, d.B, d.N, d.D, d.fH, d.fW, d.C, d.X, d.Y, d.Z, d.bev, d.layout,
+                            stream);
 }
 
-extern "C" int lss_lift_splat_from_heads(const float* frustum, const float* inv_post_rots, const float* post_trans,
-                                         const float* combine, const float* trans, const float* dx, const float* bx,
-                                         const float* depth, const float* feat, int B, int N, int D, int fH, int fW,
-                                         int C, int X, int Y, int Z, int32_t* voxel, int32_t* vox_count,
-                                         int32_t* vox_list, int32_t* entries, int32_t* cursor, void* bev, int layout,
-                                         void* stream) {
-  return lift_splat_from_heads_impl(frustum, inv_post_rots, post_trans, combine, trans, dx, bx, depth, feat, B, N, D, fH,
-                                    fW, C, X, Y, Z, voxel, vox_count, vox_list, entries, cursor, bev, layout, stream,
-                                    nullptr, 0);
-}
-
-// Descriptor form of the three entries above / below (lss_lift_splat_forward, _hostcal, _from_heads): the same
-// arguments in one struct, plus the DIRECT entry workspace (lss_lift_splat_direct_bytes) that lets the region pipeline
-// run in two launches instead of three (region_plan.h).  calib_host != NULL: host calibration (the four device
-// calibration pointers are ignored); x == NULL: depth / feat are INPUTS (the _from_heads form).
 extern "C" int lss_lift_splat_forward_desc(const lss_lift_splat_desc_t* d, void* stream) {
   LSS_CHECK_PTR(d);
-  if (d->x == nullptr) {
-    return lift_splat_from_heads_impl(d->frustum, d->inv_post_rots, d->post_trans, d->combine, d->trans, d->dx, d->bx,
-                                      d->depth, d->feat, d->B, d->N, d->D, d->fH, d->fW, d->C, d->X, d->Y, d->Z, d->voxel,
-                                      d->vox_count, d->vox_list, d->entries, d->cursor, d->bev, d->layout, stream,
-                                      d->direct_entries, d->direct_bytes);
-  }
-  if (d->calib_host != nullptr && d->math != LSS_DT_F32) return LSS_E_LAYOUT;
-  return lift_splat_forward_impl(d->frustum, d->calib_host ? nullptr : d->inv_post_rots,
-                                 d->calib_host ? nullptr : d->post_trans, d->calib_host ? nullptr : d->combine,
-                                 d->calib_host ? nullptr : d->trans, d->calib_host, d->dx, d->bx, d->x, d->w, d->bias, d->B,
-                                 d->N, d->D, d->fH, d->fW, d->Cin, d->C, d->X, d->Y, d->Z, d->voxel, d->vox_count,
-                                 d->vox_list, d->entries, d->cursor, d->depth, d->feat, d->bev, d->layout, d->math, stream,
-                                 d->direct_entries, d->direct_bytes);
-}
-
-extern "C" int lss_lift_splat_forward(const float* frustum, const float* inv_post_rots,
-                                      const float* post_trans, const float* combine, const float* trans,
-                                      const float* dx, const float* bx, const float* x, const float* w,
-                                      const float* bias, int B, int N, int D, int fH, int fW, int Cin,
-                                      int C, int X, int Y, int Z, int32_t* voxel, int32_t* vox_count,
-                                      int32_t* vox_list, int32_t* entries, int32_t* cursor, float* depth,
-                                      float* feat, void* bev, int layout, int math, void* stream) {
-  return lift_splat_forward_impl(frustum, inv_post_rots, post_trans, combine, trans, nullptr, dx, bx, x, w, bias, B, N,
-                                 D, fH, fW, Cin, C, X, Y, Z, voxel, vox_count, vox_list, entries, cursor, depth, feat,
-                                 bev, layout, math, stream);
-}
-
-// The same with the calibration handed over as ONE HOST buffer (layout of lss_depthnet_voxels_hostcal_fwd,
-// B*N <= 36, f32 depthnet math): it travels inside the kernel arguments - no H2D copy, no staging.
-extern "C" int lss_lift_splat_forward_hostcal(const float* frustum, const float* calib_host, const float* dx,
-                                              const float* bx, const float* x, const float* w, const float* bias,
-                                              int B, int N, int D, int fH, int fW, int Cin, int C, int X, int Y,
-                                              int Z, int32_t* voxel, int32_t* vox_count, int32_t* vox_list,
-                                              int32_t* entries, int32_t* cursor, float* depth, float* feat,
-                                              void* bev, int layout, void* stream) {
-  LSS_CHECK_PTR(calib_host);
-  return lift_splat_forward_impl(frustum, nullptr, nullptr, nullptr, nullptr, calib_host, dx, bx, x, w, bias, B, N, D,
-                                 fH, fW, Cin, C, X, Y, Z, voxel, vox_count, vox_list, entries, cursor, depth, feat,
-                                 bev, layout, LSS_DT_F32, stream);
+  return lift_splat_dispatch(*d, stream);
 }

@@ -65,7 +65,7 @@ class TrunkFeatures(nn.Module):
 
 class _LiftSplatFn(torch.autograd.Function):
     """geometry -> depthnet -> softmax -> lift -> splat as ONE differentiable op.  The forward is the inference
-    pipeline (`lss_lift_splat_forward`: K2 || K3, region fill, region splat - LDS-privatised histograms, no per-point
+    pipeline (`lss_lift_splat_forward_desc`: K2 || K3, region fill, region splat - LDS-privatised histograms, no per-point
     global atomics); it leaves the voxel ids, depth and context tensors K7 needs for the backward."""
 
     @staticmethod

@@ -197,33 +197,85 @@ class SplatWorkspace:
         return self._direct[key]
 
 
-def _lift_splat_desc(ws, dims, nx, layout, math, bev, depth, feat, frustum, dx, bx, x=None, w=None, bias=None, Cin=0,
-                     calib_dev=None, calib_host=None):
-    """One lss_lift_splat_desc_t for the three forms of the fused lift-splat call (include/lss_hip.h)."""
+def _check_geometry(frustum, dx, bx, dims, calib_dev=None):
+    """frustum (D,fH,fW,3), dx / bx (3,) and - unless the calibration travels as a host buffer - the per-camera
+    tensors calib_dev = (inv_post_rots, post_trans, combine, trans): (B,N,3,3) / (B,N,3)."""
+    B, Ncam, D, fH, fW = dims[:5]
+    _f32c(frustum, "frustum", (D, fH, fW, 3))
+    if calib_dev is not None:
+        inv_post_rots, post_trans, combine, trans = calib_dev
+        _f32c(inv_post_rots, "inv_post_rots", (B, Ncam, 3, 3))
+        _f32c(combine, "combine", (B, Ncam, 3, 3))
+        _f32c(post_trans, "post_trans", (B, Ncam, 3))
+        _f32c(trans, "trans", (B, Ncam, 3))
+    _f32c(dx, "dx", (3,))
+    _f32c(bx, "bx", (3,))
+
+
+def _check_depthnet(x, weight, bias, dims):
+    """x (B*N,Cin,fH,fW), weight (D+C,Cin[,1,1]), bias (D+C).  Returns (x, 2-D weight, bias)."""
     B, Ncam, D, fH, fW, C = dims
+    Cin = x.shape[1]
+    _f32c(x, "x", (B * Ncam, Cin, fH, fW))
+    w2 = weight.reshape(weight.shape[0], -1)
+    _f32c(w2, "depthnet.weight", (D + C, Cin))
+    _f32c(bias, "depthnet.bias", (D + C,))
+    return x, w2, bias
+
+
+def _check_workspace(ws, dims, nx):
+    B, Ncam, D, fH, fW = dims[:5]
     X, Y, Z = nx
-    d = N.LiftSplatDesc()
+    P = B * Ncam * D * fH * fW
+    if ws.P != P or ws.nvox != B * X * Y * Z:
+        raise ValueError("workspace sized for P=%d nvox=%d, problem has P=%d nvox=%d" % (ws.P, ws.nvox, P, B * X * Y * Z))
+
+
+def _alloc_bev(dims, nx, layout, device):
+    """BEV storage for `layout` and its LOGICAL (B, Z*C, X, Y) view: contiguous for NCHW_F32, channels_last strides for
+    NHWC_*."""
+    B, C = dims[0], dims[5]
+    X, Y, Z = nx
+    if layout == BEV_NCHW_F32:
+        bev = torch.empty(B, Z * C, X, Y, dtype=torch.float32, device=device)
+        return bev, bev
+    bev = torch.empty(B, X, Y, Z * C, dtype=torch.float32 if layout == BEV_NHWC_F32 else torch.bfloat16, device=device)
+    return bev, bev.permute(0, 3, 1, 2)
+
+
+def _lift_splat_run(what, ws, dims, nx, layout, math, frustum, dx, bx, calib_dev=None, calib_host=None, depthnet=None,
+                    heads=None):
+    """Fill one lss_lift_splat_desc_t (include/lss_hip.h) for any of the three forms of the fused lift-splat call and
+    run it.  depthnet = (x, 2-D weight, bias): depth / feat are allocated here; heads = (depth, feat): they are inputs.
+    Returns (bev as its logical view, depth, feat)."""
+    B, Ncam, D, fH, fW, C = dims
+    _check_workspace(ws, dims, nx)
     P = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+    d = N.LiftSplatDesc()
+    if depthnet is not None:
+        x, w, bias = depthnet
+        d.x, d.w, d.bias, d.Cin = P(x), P(w), P(bias), x.shape[1]
+        depth = torch.empty(B * Ncam, D, fH, fW, dtype=torch.float32, device=x.device)
+        feat = torch.empty(B * Ncam, fH, fW, C, dtype=torch.float32, device=x.device)
+    else:
+        depth, feat = heads
+    bev, out = _alloc_bev(dims, nx, layout, feat.device)
     d.frustum, d.dx, d.bx = P(frustum), P(dx), P(bx)
     if calib_host is not None:
         d.calib_host = calib_host.data_ptr()
     else:
         d.inv_post_rots, d.post_trans, d.combine, d.trans = (P(t) for t in calib_dev)
-    d.x, d.w, d.bias = P(x), P(w), P(bias)
     d.voxel, d.vox_count, d.vox_list = P(ws.voxel), P(ws.vox_count), P(ws.vox_list)
     d.entries, d.cursor = P(ws.entries), P(ws.cursor)
     direct = ws.direct_buffer(dims, nx)
     d.direct_entries = P(direct)
     d.direct_bytes = 0 if direct is None else direct.numel()
     d.depth, d.feat, d.bev = P(depth), P(feat), P(bev)
-    d.B, d.N, d.D, d.fH, d.fW, d.Cin, d.C, d.X, d.Y, d.Z = B, Ncam, D, fH, fW, Cin, C, X, Y, Z
+    d.B, d.N, d.D, d.fH, d.fW, d.C = dims
+    d.X, d.Y, d.Z = nx
     d.layout, d.math = layout, math
-    return d
-
-
-def _run_desc(d, what):
-    import ctypes
     N.check(N.lib().lss_lift_splat_forward_desc(ctypes.byref(d), N.stream()), what)
+    return out, depth, feat
 
 
 def points_to_voxels(frustum, inv_post_rots, post_trans, combine, trans, dx, bx, nx, ws,
@@ -233,17 +285,9 @@ def points_to_voxels(frustum, inv_post_rots, post_trans, combine, trans, dx, bx,
     D, fH, fW, _ = frustum.shape
     B, Ncam = inv_post_rots.shape[:2]
     X, Y, Z = nx
-    _f32c(frustum, "frustum", (D, fH, fW, 3))
-    _f32c(inv_post_rots, "inv_post_rots", (B, Ncam, 3, 3))
-    _f32c(combine, "combine", (B, Ncam, 3, 3))
-    _f32c(post_trans, "post_trans", (B, Ncam, 3))
-    _f32c(trans, "trans", (B, Ncam, 3))
-    _f32c(dx, "dx", (3,))
-    _f32c(bx, "bx", (3,))
-    P = B * Ncam * D * fH * fW
-    if ws.P != P or ws.nvox != B * X * Y * Z:
-        raise ValueError("workspace sized for P=%d nvox=%d, problem has P=%d nvox=%d"
-                         % (ws.P, ws.nvox, P, B * X * Y * Z))
+    dims = (B, Ncam, D, fH, fW)
+    _check_geometry(frustum, dx, bx, dims, (inv_post_rots, post_trans, combine, trans))
+    _check_workspace(ws, dims, nx)
     geom = torch.empty(B, Ncam, D, fH, fW, 3, dtype=torch.float32, device=frustum.device) if want_geom else None
     N.check(N.lib().lss_points_to_voxels(
         N.ptr(frustum), N.ptr(inv_post_rots), N.ptr(post_trans), N.ptr(combine), N.ptr(trans),
@@ -362,16 +406,8 @@ def lift_splat_fwd(feat, ws, dims, nx, layout=BEV_NCHW_F32, tag="lift_splat_fwd"
     _f32c(feat, "feat")
     if feat.numel() != B * Ncam * fH * fW * C:
         raise ValueError("feat size does not match dims %s" % (dims,))
-    if ws.P != B * Ncam * D * fH * fW or ws.nvox != B * X * Y * Z:
-        raise ValueError("workspace does not match dims")
-    dev = feat.device
-    if layout == BEV_NCHW_F32:
-        bev = torch.empty(B, Z * C, X, Y, dtype=torch.float32, device=dev)
-        out = bev
-    else:
-        dt = torch.float32 if layout == BEV_NHWC_F32 else torch.bfloat16
-        bev = torch.empty(B, X, Y, Z * C, dtype=dt, device=dev)
-        out = bev.permute(0, 3, 1, 2)
+    _check_workspace(ws, dims, nx)
+    bev, out = _alloc_bev(dims, nx, layout, feat.device)
     with _timed(tag):
         N.check(N.lib().lss_lift_splat_fwd(N.ptr(feat), N.ptr(ws.vox_list), N.ptr(ws.entries),
                                            B, Ncam, D, fH, fW, C, X, Y, Z, N.ptr(bev), layout, N.stream()),
@@ -382,31 +418,10 @@ def lift_splat_fwd(feat, ws, dims, nx, layout=BEV_NCHW_F32, tag="lift_splat_fwd"
 def lift_splat_forward(frustum, inv_post_rots, post_trans, combine, trans, dx, bx, x, weight, bias, ws, dims, nx,
                        layout=BEV_NCHW_F32, math=DT_F32):
     """K3 -> K2 -> K4 -> K5 with ONE native call (inference path).  Returns (bev, depth, feat)."""
-    B, Ncam, D, fH, fW, C = dims
-    X, Y, Z = nx
-    for t, name, shp in ((frustum, "frustum", (D, fH, fW, 3)), (inv_post_rots, "inv_post_rots", (B, Ncam, 3, 3)),
-                         (combine, "combine", (B, Ncam, 3, 3)), (post_trans, "post_trans", (B, Ncam, 3)),
-                         (trans, "trans", (B, Ncam, 3)), (dx, "dx", (3,)), (bx, "bx", (3,))):
-        _f32c(t, name, shp)
-    Cin = x.shape[1]
-    _f32c(x, "x", (B * Ncam, Cin, fH, fW))
-    w2 = weight.reshape(weight.shape[0], -1)
-    _f32c(w2, "depthnet.weight", (D + C, Cin))
-    _f32c(bias, "depthnet.bias", (D + C,))
-    if ws.P != B * Ncam * D * fH * fW or ws.nvox != B * X * Y * Z:
-        raise ValueError("workspace does not match dims")
-    dev = x.device
-    depth = torch.empty(B * Ncam, D, fH, fW, dtype=torch.float32, device=dev)
-    feat = torch.empty(B * Ncam, fH, fW, C, dtype=torch.float32, device=dev)
-    if layout == BEV_NCHW_F32:
-        bev = torch.empty(B, Z * C, X, Y, dtype=torch.float32, device=dev)
-        out = bev
-    else:
-        bev = torch.empty(B, X, Y, Z * C, dtype=torch.float32 if layout == BEV_NHWC_F32 else torch.bfloat16, device=dev)
-        out = bev.permute(0, 3, 1, 2)
-    _run_desc(_lift_splat_desc(ws, dims, nx, layout, math, bev, depth, feat, frustum, dx, bx, x, w2, bias, Cin,
-                               calib_dev=(inv_post_rots, post_trans, combine, trans)), "lss_lift_splat_forward_desc")
-    return out, depth, feat
+    calib_dev = (inv_post_rots, post_trans, combine, trans)
+    _check_geometry(frustum, dx, bx, dims, calib_dev)
+    return _lift_splat_run("lss_lift_splat_forward_desc", ws, dims, nx, layout, math, frustum, dx, bx, calib_dev=calib_dev,
+                           depthnet=_check_depthnet(x, weight, bias, dims))
 
 
 def ffn_fused(x, w1, b1, w2, b2, ln=None):
@@ -479,60 +494,27 @@ def lift_splat_from_heads(frustum, inv_post_rots, post_trans, combine, trans, dx
     produced (the vovnet depth heads + CamEncodeV2) with ONE native call; region-bucketed pipeline when the problem
     fits it.  Returns the BEV grid (logical (B, Z*C, X, Y))."""
     B, Ncam, D, fH, fW, C = dims
-    X, Y, Z = nx
-    for t, name, shp in ((frustum, "frustum", (D, fH, fW, 3)), (inv_post_rots, "inv_post_rots", (B, Ncam, 3, 3)),
-                         (combine, "combine", (B, Ncam, 3, 3)), (post_trans, "post_trans", (B, Ncam, 3)),
-                         (trans, "trans", (B, Ncam, 3)), (dx, "dx", (3,)), (bx, "bx", (3,)),
-                         (depth, "depth", (B * Ncam, D, fH, fW))):
-        _f32c(t, name, shp)
+    calib_dev = (inv_post_rots, post_trans, combine, trans)
+    _check_geometry(frustum, dx, bx, dims, calib_dev)
+    _f32c(depth, "depth", (B * Ncam, D, fH, fW))
     _f32c(feat, "feat")
     if feat.numel() != B * Ncam * fH * fW * C or C not in (64, 128):
         raise ValueError("feat must hold (B*N*fH*fW, C) context rows with C in (64, 128)")
-    if ws.P != B * Ncam * D * fH * fW or ws.nvox != B * X * Y * Z:
-        raise ValueError("workspace does not match dims")
-    dev = feat.device
-    if layout == BEV_NCHW_F32:
-        bev = torch.empty(B, Z * C, X, Y, dtype=torch.float32, device=dev)
-        out = bev
-    else:
-        bev = torch.empty(B, X, Y, Z * C, dtype=torch.float32 if layout == BEV_NHWC_F32 else torch.bfloat16, device=dev)
-        out = bev.permute(0, 3, 1, 2)
-    _run_desc(_lift_splat_desc(ws, dims, nx, layout, DT_F32, bev, depth, feat, frustum, dx, bx,
-                               calib_dev=(inv_post_rots, post_trans, combine, trans)),
-              "lss_lift_splat_forward_desc (from heads)")
-    return out
+    return _lift_splat_run("lss_lift_splat_forward_desc (from heads)", ws, dims, nx, layout, DT_F32, frustum, dx, bx,
+                           calib_dev=calib_dev, heads=(depth, feat))[0]
 
 
 def lift_splat_forward_hostcal(frustum, calib_host, dx, bx, x, weight, bias, ws, dims, nx, layout=BEV_NCHW_F32):
     """lift_splat_forward with the calibration as ONE CPU fp32 buffer of B*N*24 floats
     ([inv_post_rots | combine | post_trans | trans] = data.CalibrationPack.buffer): it is read during the
     call and rides in the kernel arguments - no H2D copy.  B*N <= HOSTCAL_MAX_CAMS; f32 depthnet math."""
-    B, Ncam, D, fH, fW, C = dims
-    X, Y, Z = nx
+    B, Ncam = dims[:2]
     if calib_host.is_cuda or calib_host.dtype != torch.float32 or not calib_host.is_contiguous() \
             or calib_host.numel() != B * Ncam * 24 or B * Ncam > HOSTCAL_MAX_CAMS:
         raise ValueError("calib_host must be a contiguous CPU fp32 buffer of B*N*24 floats (B*N <= %d)" % HOSTCAL_MAX_CAMS)
-    for t, name, shp in ((frustum, "frustum", (D, fH, fW, 3)), (dx, "dx", (3,)), (bx, "bx", (3,))):
-        _f32c(t, name, shp)
-    Cin = x.shape[1]
-    _f32c(x, "x", (B * Ncam, Cin, fH, fW))
-    w2 = weight.reshape(weight.shape[0], -1)
-    _f32c(w2, "depthnet.weight", (D + C, Cin))
-    _f32c(bias, "depthnet.bias", (D + C,))
-    if ws.P != B * Ncam * D * fH * fW or ws.nvox != B * X * Y * Z:
-        raise ValueError("workspace does not match dims")
-    dev = x.device
-    depth = torch.empty(B * Ncam, D, fH, fW, dtype=torch.float32, device=dev)
-    feat = torch.empty(B * Ncam, fH, fW, C, dtype=torch.float32, device=dev)
-    if layout == BEV_NCHW_F32:
-        bev = torch.empty(B, Z * C, X, Y, dtype=torch.float32, device=dev)
-        out = bev
-    else:
-        bev = torch.empty(B, X, Y, Z * C, dtype=torch.float32 if layout == BEV_NHWC_F32 else torch.bfloat16, device=dev)
-        out = bev.permute(0, 3, 1, 2)
-    _run_desc(_lift_splat_desc(ws, dims, nx, layout, DT_F32, bev, depth, feat, frustum, dx, bx, x, w2, bias, Cin,
-                               calib_host=calib_host), "lss_lift_splat_forward_desc (host calibration)")
-    return out, depth, feat
+    _check_geometry(frustum, dx, bx, dims)
+    return _lift_splat_run("lss_lift_splat_forward_desc (host calibration)", ws, dims, nx, layout, DT_F32, frustum, dx, bx,
+                           calib_host=calib_host, depthnet=_check_depthnet(x, weight, bias, dims))
 
 
 def lift_splat_bwd(grad_bev, voxel, depth, feat, dims, nx):

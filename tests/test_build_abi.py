@@ -48,6 +48,25 @@ def test_argument_checks_without_gpu(built):
     assert L.lss_lift_splat_fwd(one, one, one, 1, 1, 1, 1, 1, 64, 1, 1, 1, one, 7, None) == -3  # bad layout
     assert L.lss_depthnet_softmax_fwd(one, one, one, 1, 100, 4, 4, 4, one, one, 0, None) == -2  # Cin % 64
 
+    def desc(**fields):  # x == NULL form, every pointer it needs set, every size 1
+        d = _native.LiftSplatDesc()
+        for n in ("frustum", "inv_post_rots", "post_trans", "combine", "trans", "dx", "bx", "voxel", "vox_count",
+                  "vox_list", "entries", "cursor", "depth", "feat", "bev"):
+            setattr(d, n, one)
+        d.B = d.N = d.D = d.fH = d.fW = d.X = d.Y = d.Z = 1
+        d.C = 64
+        for n, v in fields.items():
+            setattr(d, n, v)
+        return ctypes.byref(d)
+
+    assert L.lss_lift_splat_forward_desc(None, None) == -1
+    assert L.lss_lift_splat_forward_desc(desc(depth=None), None) == -1
+    assert L.lss_lift_splat_forward_desc(desc(C=48), None) == -2
+    assert L.lss_lift_splat_forward_desc(desc(layout=7), None) == -3
+    # host calibration is an f32-depthnet form
+    assert L.lss_lift_splat_forward_desc(desc(x=one, w=one, bias=one, Cin=64, calib_host=one, math=_native.DT_BF16),
+                                         None) == -3
+
 
 def test_exact_index_kernel_has_no_contracted_fma(tmp_path):
     """geom_bucket.hip must be built with -ffp-contract=off - and the ISA it then compiles to
