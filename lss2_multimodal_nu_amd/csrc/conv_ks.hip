@@ -43,6 +43,107 @@ __device__ __forceinline__ void ks_glds16(const void* gsrc, void* lds_wave_base)
                                    (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
 }
 
+// Input patch -> LDS by LDS-DMA: [chunk][channel half][position][32 B]; a piece = 32 positions of one half; patch
+// position (pr, pc) of `rows` x `pitch` (padded to nposp) is input pixel map(pr, pc) or, outside the image, the zero page
+// (row / column of a lane's position advance by 64 positions per piece - no per-piece division: the first version
+// spent ~60 VALU instructions of address arithmetic in front of every DMA instruction.  Staging the pieces through
+// registers instead - plain 16-B loads, 24 in flight per wave, one ds_write_b128 each - was built and measured: the
+// same 3-4 us from kernel entry to "patch and weights on the CU" (layer3 7.2 -> 8.2 us per launch): what bounds this
+// phase is the 130-240 KiB every one of the 256 CUs pulls through its 64-B-per-clock L1 path at the same moment,
+// 33-62 MB out of the L2s in ~3 us, not the way the requests are issued.)
+// Layout and bank conflicts.  A ds_read_b128 is served in four groups of 16 lanes ({0-3, 12-15, 20-27}, {4-11, 16-19,
+// 28-31}, ...: MI355X_MICROARCH.md, LDS) against a 256-B window of banks.  With 64 B per position (the four channel
+// pieces side by side) the window is four positions and the lanes of a group that share a piece index - pixels n and
+// n + 12, n + 4 and n + 8 - fall on the same 16 B: 2-way conflicts on every read.  With the two channel HALVES of a
+// chunk in separate planes of 32 B per position the window is eight positions, a group's lanes of piece pair (0, 1) or
+// (2, 3) cover sixteen different 16-B cells for ANY alignment of the 16 pixels - every tap shift - and the address is
+// plane + position * 32 + (piece & 1) * 16: no arithmetic beyond the tap offset.  What that bought, measured (main
+// phase, layer1 / 2 / 3, tools/bench_ks.py --stamps): 64-B positions with the conflicts 2.60 / 2.56 / 2.36 us; the same
+// with an XOR swizzle of the piece index (conflict-free, four VALU instructions per read next to back-to-back MFMAs)
+// 3.20 / 3.16 / 2.72; this layout 2.54 / 2.48 / 2.32 - and the two timing-only builds of tools/build_diag_libs.sh say
+// why the conflicts never mattered: the 180 MFMAs of a wave alone (KS_NOREAD) take 2.06 / 2.04 / 1.84 us, the 90
+// fragment reads alone (KS_NOMFMA) 1.20 / 1.28 / 1.36: the phase is the matrix pipe plus the quarter of the reads that
+// does not hide behind it, at one wave per SIMD.
+template <int NCH, class Map>
+__device__ __forceinline__ void ks_fill_patch(unsigned char* smem, const unsigned short* ximg, int Cin, int H, int W,
+                                              int rows, int pitch, int nposp, int wave, int lane, Map map) {
+  const int ppc = nposp >> 4;                       // pieces per chunk: nposp / 32 position blocks x 2 halves
+  const int q64 = 64 / pitch, r64 = 64 - q64 * pitch;  // wave-uniform
+  const int h = wave & 1;                           // this wave's pieces: position blocks (wave >> 1) + 2 k of half h
+  const int pos0 = 32 * (wave >> 1) + (lane >> 1);
+  int pr = pos0 / pitch, pc = pos0 - pr * pitch;
+  const unsigned char* zsrc = lss_ks_zero_page + (lane & 7) * 16;
+  const unsigned short* xb = ximg + (2 * h + (lane & 1)) * 8;
+  for (int i = wave; i < ppc; i += 4) {
+    int iy, ix;
+    map(pr, pc, iy, ix);
+    const bool in = pr < rows && iy >= 0 && iy < H && ix >= 0 && ix < W;
+    const unsigned short* src = xb + (in ? (iy * W + ix) * Cin : 0);
+#pragma unroll
+    for (int c = 0; c < NCH; ++c)
+      ks_glds16(in ? (const void*)(src + c * 32) : (const void*)zsrc,
+                smem + ((size_t)(c * 2 + h) * nposp + 32 * (i >> 1)) * 32);
+    pr += q64; pc += r64;
+    if (pc >= pitch) { pc -= pitch; ++pr; }
+  }
+}
+
+// Diagnostics (LSS_KS_STAMPS=<hex device address>, tools/bench_ks.py --stamps): 8 slots per workgroup - 100-MHz
+// s_memrealtime stamps 0-6 written by thread 0, slot 7 the shader-clock cycles of the main phase.  base null: nothing.
+struct KsStamps {
+  unsigned long long* base;
+  int tid;
+  unsigned long long clk_main = 0;
+  __device__ __forceinline__ void stamp(int k) const {
+    if (base != nullptr && tid == 0) base[(size_t)blockIdx.x * 8 + k] = __builtin_amdgcn_s_memrealtime();
+  }
+  __device__ __forceinline__ void main_begin() {
+    if (base != nullptr) clk_main = __builtin_amdgcn_s_memtime();
+  }
+  // first / last: the accumulators the MFMA chain ends in (stamp 3 waits until it has retired)
+  __device__ __forceinline__ void main_end(const f32x4& first, const f32x4& last) const {
+    if (base != nullptr) asm volatile("s_nop 0" ::"v"(first), "v"(last));
+    stamp(3);
+    if (base != nullptr && tid == 0) base[(size_t)blockIdx.x * 8 + 7] = __builtin_amdgcn_s_memtime() - clk_main;
+  }
+  __device__ __forceinline__ void drain() const {
+    if (base != nullptr) {
+      stamp(5);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // stores acknowledged
+      stamp(6);
+    }
+  }
+};
+
+// epilogue constants of a lane's 8 consecutive channels ch .. ch + 7 (null scale: 1, null shift: 0)
+__device__ __forceinline__ void ks_load_affine(const float* scale, const float* shift, int ch, float (&sc)[8], float (&sh)[8]) {
+  f32x4 s0 = {1.f, 1.f, 1.f, 1.f}, s1 = s0, h0 = {0.f, 0.f, 0.f, 0.f}, h1 = h0;
+  if (scale) { s0 = *reinterpret_cast<const f32x4*>(scale + ch); s1 = *reinterpret_cast<const f32x4*>(scale + ch + 4); }
+  if (shift) { h0 = *reinterpret_cast<const f32x4*>(shift + ch); h1 = *reinterpret_cast<const f32x4*>(shift + ch + 4); }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) { sc[i] = s0[i]; sc[4 + i] = s1[i]; sh[i] = h0[i]; sh[4 + i] = h1[i]; }
+}
+
+// 8 x fp32 -> the 16-B store value of 8 consecutive bf16 channels
+typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
+__device__ __forceinline__ u32x4 ks_pack8(const float (&v)[8]) {
+  return (u32x4){lss_pack_bf2(v[0], v[1]), lss_pack_bf2(v[2], v[3]), lss_pack_bf2(v[4], v[5]), lss_pack_bf2(v[6], v[7])};
+}
+
+// the K parts of one (tile, channel tile, lane) cell meet: p0 is part kp = 0, part kp lies kstride further; summed in
+// the fixed order kp = 0 .. NKW - 1
+template <int NKW>
+__device__ __forceinline__ f32x4 ks_sum_parts(const f32x4* p0, int kstride) {
+  f32x4 sum = p0[0];
+#pragma unroll
+  for (int k = 1; k < NKW; ++k) {
+    const f32x4 pv = p0[k * kstride];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) sum[i] += pv[i];
+  }
+  return sum;
+}
+
 struct KsArgs {
   const unsigned short* x;        // (B, H, W, Cin) bf16 NHWC
   const unsigned char* w;         // lss_conv2d_pack_weights_ks
@@ -55,8 +156,7 @@ struct KsArgs {
   int npb;                        // pixel blocks per image
   int nposp;                      // patch positions per chunk, padded to a multiple of 32
   int ncb;                        // 32-channel output blocks
-  unsigned long long* stamps;     // diagnostics (LSS_KS_STAMPS=<hex device address>, tools/bench_ks.py --stamps): 8 x 100-MHz
-                                  // s_memrealtime stamps per workgroup, or null
+  unsigned long long* stamps;     // KsStamps base, or null
 };
 
 // KSW: k-steps (32 input channels x one tap) per wave; NKW: K parts; PXT: 16-pixel tiles per wave.  NKW * NPW = 4 waves.
@@ -71,19 +171,11 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(const KsArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kp = wave % NKW, ph = wave / NKW;  // K part, pixel part
   const int n = lane & 15, kq = lane >> 4;
-  auto stamp = [&](int k) {
-    if (a.stamps != nullptr && tid == 0) a.stamps[(size_t)blockIdx.x * 8 + k] = __builtin_amdgcn_s_memrealtime();
-  };
-  stamp(0);
-  unsigned long long clk_main = 0;  // shader-clock cycles of the main phase (slot 7 of the stamps)
+  KsStamps st = {a.stamps, tid};
+  st.stamp(0);
 
   // ---- which block: XCD-aware order, channel blocks of one pixel block adjacent (they share the input patch) ----
-  int t;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  }
+  const int t = lss_xcd_order(blockIdx.x, gridDim.x);
   const int cb = t % a.ncb;
   const int pbg = t / a.ncb;
   const int b = pbg / a.npb, pb = pbg - b * a.npb;
@@ -91,47 +183,9 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(const KsArgs a) {
   const int p0 = pb * a.PB;                       // first pixel of the block (flattened, inside image b)
   const int y_first = p0 / a.W;                   // patch row 0 = image row y_first - 1
 
-  // ---- input patch -> LDS by LDS-DMA: [chunk][channel half][position][32 B]; a piece = 32 positions of one half ----
-  // (row / column of a lane's position advance by 64 positions per piece - no per-piece division: the first version
-  // spent ~60 VALU instructions of address arithmetic in front of every DMA instruction.  Staging the pieces through
-  // registers instead - plain 16-B loads, 24 in flight per wave, one ds_write_b128 each - was built and measured: the
-  // same 3-4 us from kernel entry to "patch and weights on the CU" (layer3 7.2 -> 8.2 us per launch): what bounds this
-  // phase is the 130-240 KiB every one of the 256 CUs pulls through its 64-B-per-clock L1 path at the same moment,
-  // 33-62 MB out of the L2s in ~3 us, not the way the requests are issued.)
-  // Layout and bank conflicts.  A ds_read_b128 is served in four groups of 16 lanes ({0-3, 12-15, 20-27}, {4-11, 16-19,
-  // 28-31}, ...: MI355X_MICROARCH.md, LDS) against a 256-B window of banks.  With 64 B per position (the four channel
-  // pieces side by side) the window is four positions and the lanes of a group that share a piece index - pixels n and
-  // n + 12, n + 4 and n + 8 - fall on the same 16 B: 2-way conflicts on every read.  With the two channel HALVES of a
-  // chunk in separate planes of 32 B per position the window is eight positions, a group's lanes of piece pair (0, 1) or
-  // (2, 3) cover sixteen different 16-B cells for ANY alignment of the 16 pixels - every tap shift - and the address is
-  // plane + position * 32 + (piece & 1) * 16: no arithmetic beyond the tap offset.  What that bought, measured (main
-  // phase, layer1 / 2 / 3, tools/bench_ks.py --stamps): 64-B positions with the conflicts 2.60 / 2.56 / 2.36 us; the same
-  // with an XOR swizzle of the piece index (conflict-free, four VALU instructions per read next to back-to-back MFMAs)
-  // 3.20 / 3.16 / 2.72; this layout 2.54 / 2.48 / 2.32 - and the two timing-only builds of tools/build_diag_libs.sh say
-  // why the conflicts never mattered: the 180 MFMAs of a wave alone (KS_NOREAD) take 2.06 / 2.04 / 1.84 us, the 90
-  // fragment reads alone (KS_NOMFMA) 1.20 / 1.28 / 1.36: the phase is the matrix pipe plus the quarter of the reads that
-  // does not hide behind it, at one wave per SIMD.
-  constexpr int NCH = NKW * KSW / 9;           // 32-channel chunks of the input
-  {
-    const int ppc = a.nposp >> 4;                 // pieces per chunk: nposp / 32 position blocks x 2 halves
-    const int q64 = 64 / WP, r64 = 64 - q64 * WP;  // wave-uniform
-    const int h = wave & 1;                       // this wave's pieces: position blocks (wave >> 1) + 2 k of half h
-    const int pos0 = 32 * (wave >> 1) + (lane >> 1);
-    int pr = pos0 / WP, pc = pos0 - pr * WP;
-    const unsigned char* zsrc = lss_ks_zero_page + (lane & 7) * 16;
-    const unsigned short* xb = a.x + (size_t)b * HW * a.Cin + (2 * h + (lane & 1)) * 8;
-    for (int i = wave; i < ppc; i += 4) {
-      const int iy = y_first - 1 + pr, ix = pc - 1;
-      const bool in = pr < KS_ROWS && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-      const unsigned short* src = xb + (in ? (iy * a.W + ix) * a.Cin : 0);
-#pragma unroll
-      for (int c = 0; c < NCH; ++c)
-        ks_glds16(in ? (const void*)(src + c * 32) : (const void*)zsrc,
-                  smem + ((size_t)(c * 2 + h) * a.nposp + 32 * (i >> 1)) * 32);
-      pr += q64; pc += r64;
-      if (pc >= WP) { pc -= WP; ++pr; }
-    }
-  }
+  // ---- input patch -> LDS: the identity map with a one-pixel halo ----
+  ks_fill_patch<NKW * KSW / 9>(smem, a.x + (size_t)b * HW * a.Cin, a.Cin, a.H, a.W, KS_ROWS, WP, a.nposp, wave, lane,
+                               [&](int pr, int pc, int& iy, int& ix) { iy = y_first - 1 + pr; ix = pc - 1; });
 
   // ---- weights: this wave's KSW x 2 A fragments, straight into registers (coalesced 1-KiB loads) ----
   // Only the first WPRE k-steps are requested here; the main phase requests k-step s + WPRE while it computes k-step s
@@ -171,7 +225,7 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(const KsArgs a) {
       if (x >= a.W) { x -= a.W; ++y; }
     }
   }
-  stamp(1);  // every request (weights, patch pieces) has been issued
+  st.stamp(1);  // every request (weights, patch pieces) has been issued
   constexpr int NOWN = (PXT + NKW - 1) / NKW;   // tiles a wave finishes: j = kp, kp + NKW, ...
   const int ch = cb * 32 + kq * 8;             // this lane's 8 consecutive output channels
   uint4 rres[NOWN];
@@ -191,7 +245,7 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(const KsArgs a) {
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the patch pieces (and the weight fragments) have landed
   __syncthreads();
-  stamp(2);
+  st.stamp(2);
 
   // ---- main phase: KSW k-steps x PXT pixel tiles x 2 channel tiles, nothing but LDS reads and MFMAs ----
   // ONE wave per SIMD: nobody else hides an LDS round trip, so the pixel fragments of k-step s + 1 are requested - all
@@ -206,7 +260,7 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(const KsArgs a) {
 #pragma unroll
     for (int j = 0; j < PXT; ++j) fb[buf][j] = *reinterpret_cast<const bf16x8*>(cbase + ab[j] + toff);
   };
-  if (a.stamps != nullptr) clk_main = __builtin_amdgcn_s_memtime();
+  st.main_begin();
   load_frags(0, 0);
 #pragma unroll
   for (int s = 0; s < KSW; ++s) {
@@ -228,9 +282,7 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(const KsArgs a) {
   }
 
   // ---- the K parts meet: part[kp][tile][ct][lane] (16 B each), summed in the fixed order kp = 0 .. NKW - 1 ----
-  if (a.stamps != nullptr) asm volatile("s_nop 0" ::"v"(acc[0][0]), "v"(acc[PXT - 1][1]));  // the MFMA chain has retired
-  stamp(3);
-  if (a.stamps != nullptr && tid == 0) a.stamps[(size_t)blockIdx.x * 8 + 7] = __builtin_amdgcn_s_memtime() - clk_main;
+  st.main_end(acc[0][0], acc[PXT - 1][1]);
   __syncthreads();  // every wave is done reading the patch: its LDS is free
   f32x4* part = reinterpret_cast<f32x4*>(smem);
 #pragma unroll
@@ -241,15 +293,9 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(const KsArgs a) {
   }
   // epilogue constants of this lane's 8 consecutive channels, requested before the barrier
   float sc[8], sh[8];
-  {
-    f32x4 s0 = {1.f, 1.f, 1.f, 1.f}, s1 = s0, h0 = {0.f, 0.f, 0.f, 0.f}, h1 = h0;
-    if (a.scale) { s0 = *reinterpret_cast<const f32x4*>(a.scale + ch); s1 = *reinterpret_cast<const f32x4*>(a.scale + ch + 4); }
-    if (a.shift) { h0 = *reinterpret_cast<const f32x4*>(a.shift + ch); h1 = *reinterpret_cast<const f32x4*>(a.shift + ch + 4); }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { sc[i] = s0[i]; sc[4 + i] = s1[i]; sh[i] = h0[i]; sh[4 + i] = h1[i]; }
-  }
+  ks_load_affine(a.scale, a.shift, ch, sc, sh);
   __syncthreads();
-  stamp(4);
+  st.stamp(4);
   // wave (kp, ph) finishes the tiles ph * PXT + j with j % NKW == kp
   const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(
       a.y, 0, a.wt ? (int)((size_t)a.B * HW * a.Cout * 2) : 0, 0x00020000);
@@ -265,13 +311,7 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(const KsArgs a) {
     float v[8];
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) {
-      f32x4 sum = part[((0 * NT + tile) * 2 + ct) * 64 + lane];
-#pragma unroll
-      for (int k = 1; k < NKW; ++k) {
-        const f32x4 pv = part[((k * NT + tile) * 2 + ct) * 64 + lane];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) sum[i] += pv[i];
-      }
+      const f32x4 sum = ks_sum_parts<NKW>(part + (tile * 2 + ct) * 64 + lane, NT * 2 * 64);
 #pragma unroll
       for (int i = 0; i < 4; ++i) v[4 * ct + i] = sum[i];
     }
@@ -284,17 +324,12 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(const KsArgs a) {
       v[2 * k] = lo; v[2 * k + 1] = hi;
     }
     if (live) {
-      typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-      const u32x4 ov = {lss_pack_bf2(v[0], v[1]), lss_pack_bf2(v[2], v[3]), lss_pack_bf2(v[4], v[5]), lss_pack_bf2(v[6], v[7])};
+      const u32x4 ov = ks_pack8(v);
       if (a.wt) __builtin_amdgcn_raw_buffer_store_b128(ov, yrsrc, (int)(o * 2), 0, 16);  // write-through
       else *reinterpret_cast<u32x4*>(a.y + o) = ov;
     }
   }
-  if (a.stamps != nullptr) {
-    stamp(5);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // stores acknowledged
-    stamp(6);
-  }
+  st.drain();
 }
 
 // OIHW fp32 -> the kernel's register image, bf16: [co block of 32][K part][k-step][channel tile][lane][8], where k-step
@@ -320,50 +355,78 @@ __global__ void pack_weights_ks_kernel(const float* __restrict__ w, int Cout, in
   }
 }
 
-struct KsPlan {
-  int ok, PB, npb, nposp, ncb, lds, grid, variant;  // variant 0: <18, 4, 5> (Cin 256), 1: <9, 4, 10> (128), 2: <9, 2, 10> (64)
-};
-
-KsPlan ks_plan(int B, int H, int W, int Cin, int Cout) {
-  KsPlan p = {};
-  if (B <= 0 || H <= 0 || W < 4 || Cout <= 0 || Cout % 32 != 0) return p;
-  if (Cin == 256) { p.variant = 0; p.PB = 80; }
-  else if (Cin == 128) { p.variant = 1; p.PB = 160; }
-  else if (Cin == 64) { p.variant = 2; p.PB = 320; }
-  else return p;
-  const long long HW = (long long)H * W;
-  if (p.PB > 4 * W + 1) return p;                    // a pixel block spans at most five image rows
-  p.npb = (int)((HW + p.PB - 1) / p.PB);
-  p.ncb = Cout / 32;
-  p.nposp = (KS_ROWS * (W + 2) + 31) / 32 * 32;
-  const int patch = (Cin / 32) * p.nposp * KS_POSB;
-  if (patch > 112 * 1024) return p;                  // (with the 80-KiB partial tiles of the K parts in the same LDS)
-  const int ntile = p.PB / 16;
-  const int red = (p.variant == 2 ? 2 : 4) * ntile * 2 * 1024;   // the K parts' partial tiles
-  p.lds = patch > red ? patch : red;
-  if (p.lds > KS_LDS_MAX) return p;
-  const long long grid = (long long)B * p.npb * p.ncb;
-  // one workgroup per CU: worth it where the tile kernel's grid leaves the chip under-filled (at most two rounds here)
-  if (grid < 64 || grid > 512) return p;
-  if ((long long)B * HW * (Cin > Cout ? Cin : Cout) >= (1LL << 30)) return p;
-  p.grid = (int)grid;
-  p.ok = 1;
-  return p;
+// ---- host side shared by the three modes ----
+// LSS_CONV_KS=0 switches every mode of this file off (the *_ok functions answer 0)
+bool ks_enabled() {
+  const char* e = getenv("LSS_CONV_KS");
+  return e == nullptr || atoi(e) != 0;
 }
 
-template <int KSW, int NKW, int PXT>
-int ks_launch(const KsPlan& p, const KsArgs& a, hipStream_t st) {
+// the diagnostic stamp buffer of tools/bench_ks.py --stamps (every kernel of this file), or null
+unsigned long long* ks_stamps_from_env() {
+  const char* e = getenv("LSS_KS_STAMPS");
+  return e ? reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 16)) : nullptr;
+}
+
+// grid of a weight-pack kernel over n elements (256 threads, grid-stride)
+int ks_pack_grid(size_t n) { return (int)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256); }
+
+// every pointer 16-byte aligned (null passes)
+template <class... P>
+bool ks_aligned16(const P*... p) {
+  return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) == 0;
+}
+
+// one launch of kernel K: the dynamic-LDS attribute is set once per instantiation and device
+template <auto K, class Args>
+int ks_launch(int grid, int lds, const Args& a, hipStream_t st) {
   static bool attr_set[64] = {};
   int dev = -1;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
   if (dev < 0 || !attr_set[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_ks_kernel<KSW, NKW, PXT>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, KS_LDS_MAX);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       KS_LDS_MAX);
     if (e != hipSuccess) return (int)e;
     if (dev >= 0) attr_set[dev] = true;
   }
-  hipLaunchKernelGGL((conv_ks_kernel<KSW, NKW, PXT>), dim3(p.grid), dim3(256), p.lds, st, a);
+  hipLaunchKernelGGL(K, dim3(grid), dim3(256), lds, st, a);
   return lss_launch_status();
+}
+
+// A plan: is (shape) a case, the launch geometry, and the kernel's arguments with every shape-derived field filled in
+// (the entry adds the pointers and flags).
+struct KsPlan {
+  int ok, lds, grid, variant;  // variant 0: <18, 4, 5> (Cin 256), 1: <9, 4, 10> (128), 2: <9, 2, 10> (64)
+  KsArgs a;
+};
+
+KsPlan ks_plan(int B, int H, int W, int Cin, int Cout) {
+  KsPlan pl = {};
+  KsArgs& p = pl.a;
+  if (B <= 0 || H <= 0 || W < 4 || Cout <= 0 || Cout % 32 != 0) return pl;
+  if (Cin == 256) { pl.variant = 0; p.PB = 80; }
+  else if (Cin == 128) { pl.variant = 1; p.PB = 160; }
+  else if (Cin == 64) { pl.variant = 2; p.PB = 320; }
+  else return pl;
+  p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
+  const long long HW = (long long)H * W;
+  if (p.PB > 4 * W + 1) return pl;                   // a pixel block spans at most five image rows
+  p.npb = (int)((HW + p.PB - 1) / p.PB);
+  p.ncb = Cout / 32;
+  p.nposp = (KS_ROWS * (W + 2) + 31) / 32 * 32;
+  const int patch = (Cin / 32) * p.nposp * KS_POSB;
+  if (patch > 112 * 1024) return pl;                 // (with the 80-KiB partial tiles of the K parts in the same LDS)
+  const int ntile = p.PB / 16;
+  const int red = (pl.variant == 2 ? 2 : 4) * ntile * 2 * 1024;   // the K parts' partial tiles
+  pl.lds = patch > red ? patch : red;
+  if (pl.lds > KS_LDS_MAX) return pl;
+  const long long grid = (long long)B * p.npb * p.ncb;
+  // one workgroup per CU: worth it where the tile kernel's grid leaves the chip under-filled (at most two rounds here)
+  if (grid < 64 || grid > 512) return pl;
+  if ((long long)B * HW * (Cin > Cout ? Cin : Cout) >= (1LL << 30)) return pl;
+  pl.grid = (int)grid;
+  pl.ok = 1;
+  return pl;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -408,18 +471,10 @@ __global__ __launch_bounds__(256, 1) void conv_ks_s2_dual_kernel(const KsS2Args 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int kp = wave % NKW, ph = wave / NKW;
   const int n = lane & 15, kq = lane >> 4;
-  auto stamp = [&](int k) {
-    if (a.stamps != nullptr && tid == 0) a.stamps[(size_t)blockIdx.x * 8 + k] = __builtin_amdgcn_s_memrealtime();
-  };
-  stamp(0);
-  unsigned long long clk_main = 0;
+  KsStamps st = {a.stamps, tid};
+  st.stamp(0);
 
-  int t;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  }
+  const int t = lss_xcd_order(blockIdx.x, gridDim.x);
   const int cb = t % a.ncb;
   const int pbg = t / a.ncb;
   const int b = pbg / a.npb, pb = pbg - b * a.npb;
@@ -428,26 +483,10 @@ __global__ __launch_bounds__(256, 1) void conv_ks_s2_dual_kernel(const KsS2Args 
   const int r0 = p0 / a.Wo;                       // patch row 0 = input row 2 r0 - 1
 
   // ---- input patch -> LDS, columns de-interleaved: position (pr, pc) <- input (2 r0 - 1 + pr, pc < Wo ? 2 pc : 2 (pc - Wo) - 1)
-  {
-    const int ppc = a.nposp >> 4;
-    const int q64 = 64 / WP, r64 = 64 - q64 * WP;
-    const int h = wave & 1;
-    const int pos0 = 32 * (wave >> 1) + (lane >> 1);
-    int pr = pos0 / WP, pc = pos0 - pr * WP;
-    const unsigned char* zsrc = lss_ks_zero_page + (lane & 7) * 16;
-    const unsigned short* xb = a.x + (size_t)b * a.H * a.W * a.Cin + (2 * h + (lane & 1)) * 8;
-    for (int i = wave; i < ppc; i += 4) {
-      const int iy = 2 * r0 - 1 + pr, ix = pc < a.Wo ? 2 * pc : 2 * (pc - a.Wo) - 1;
-      const bool in = pr < KS_ROWS && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-      const unsigned short* src = xb + (in ? (iy * a.W + ix) * a.Cin : 0);
-#pragma unroll
-      for (int c = 0; c < NCH; ++c)
-        ks_glds16(in ? (const void*)(src + c * 32) : (const void*)zsrc,
-                  smem + ((size_t)(c * 2 + h) * a.nposp + 32 * (i >> 1)) * 32);
-      pr += q64; pc += r64;
-      if (pc >= WP) { pc -= WP; ++pr; }
-    }
-  }
+  ks_fill_patch<NCH>(smem, a.x + (size_t)b * a.H * a.W * a.Cin, a.Cin, a.H, a.W, KS_ROWS, WP, a.nposp, wave, lane,
+                     [&](int pr, int pc, int& iy, int& ix) {
+                       iy = 2 * r0 - 1 + pr; ix = pc < a.Wo ? 2 * pc : 2 * (pc - a.Wo) - 1;
+                     });
 
   // ---- weights: nine 3x3 k-steps (streamed as in the stride-1 kernel) + the 1x1 k-step, four channel tiles each ----
   constexpr int WPRE = 4;
@@ -478,7 +517,7 @@ __global__ __launch_bounds__(256, 1) void conv_ks_s2_dual_kernel(const KsS2Args 
       if (x >= a.Wo) { x -= a.Wo; ++y; }
     }
   }
-  stamp(1);
+  st.stamp(1);
   f32x4 acc[PXT][CT], acc2[PXT][CT];
 #pragma unroll
   for (int j = 0; j < PXT; ++j)
@@ -489,7 +528,7 @@ __global__ __launch_bounds__(256, 1) void conv_ks_s2_dual_kernel(const KsS2Args 
     }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  stamp(2);
+  st.stamp(2);
 
   // ---- main phase: 9 k-steps x PXT pixel tiles x 4 channel tiles, + the 1x1's 4 PXT MFMAs on the centre tap ----
   bf16x8 fb[2][PXT];
@@ -500,7 +539,7 @@ __global__ __launch_bounds__(256, 1) void conv_ks_s2_dual_kernel(const KsS2Args 
 #pragma unroll
     for (int j = 0; j < PXT; ++j) fb[buf][j] = *reinterpret_cast<const bf16x8*>(cbase + ab[j] + toff);
   };
-  if (a.stamps != nullptr) clk_main = __builtin_amdgcn_s_memtime();
+  st.main_begin();
   load_frags(0, 0);
 #pragma unroll
   for (int s = 0; s < 9; ++s) {
@@ -523,9 +562,7 @@ __global__ __launch_bounds__(256, 1) void conv_ks_s2_dual_kernel(const KsS2Args 
   }
 
   // ---- the K parts meet: part[output][kp][tile][ct][lane], summed in the fixed order kp = 0 .. NKW - 1 ----
-  if (a.stamps != nullptr) asm volatile("s_nop 0" ::"v"(acc[0][0]), "v"(acc[PXT - 1][CT - 1]));
-  stamp(3);
-  if (a.stamps != nullptr && tid == 0) a.stamps[(size_t)blockIdx.x * 8 + 7] = __builtin_amdgcn_s_memtime() - clk_main;
+  st.main_end(acc[0][0], acc[PXT - 1][CT - 1]);
   __syncthreads();  // every wave is done reading the patch: its LDS is free
   f32x4* part = reinterpret_cast<f32x4*>(smem);
 #pragma unroll
@@ -542,16 +579,10 @@ __global__ __launch_bounds__(256, 1) void conv_ks_s2_dual_kernel(const KsS2Args 
 #pragma unroll
   for (int o = 0; o < 2; ++o)
 #pragma unroll
-    for (int g = 0; g < 2; ++g) {
-      const int ch = o * a.Cout + cb * 64 + g * 32 + kq * 8;
-      f32x4 s0 = {1.f, 1.f, 1.f, 1.f}, s1 = s0, h0 = {0.f, 0.f, 0.f, 0.f}, h1 = h0;
-      if (a.scale) { s0 = *reinterpret_cast<const f32x4*>(a.scale + ch); s1 = *reinterpret_cast<const f32x4*>(a.scale + ch + 4); }
-      if (a.shift) { h0 = *reinterpret_cast<const f32x4*>(a.shift + ch); h1 = *reinterpret_cast<const f32x4*>(a.shift + ch + 4); }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { sc[o][g][i] = s0[i]; sc[o][g][4 + i] = s1[i]; sh[o][g][i] = h0[i]; sh[o][g][4 + i] = h1[i]; }
-    }
+    for (int g = 0; g < 2; ++g)
+      ks_load_affine(a.scale, a.shift, o * a.Cout + cb * 64 + g * 32 + kq * 8, sc[o][g], sh[o][g]);
   __syncthreads();
-  stamp(4);
+  st.stamp(4);
   // wave (kp, ph) finishes the tiles ph * PXT + j with j % NKW == kp, both outputs
   constexpr int NOWN = (PXT + NKW - 1) / NKW;
 #pragma unroll
@@ -570,13 +601,7 @@ __global__ __launch_bounds__(256, 1) void conv_ks_s2_dual_kernel(const KsS2Args 
 #pragma unroll
         for (int tt = 0; tt < 2; ++tt) {
           const int ct = 2 * g + tt;
-          f32x4 sum = part[(((o * NKW + 0) * NT + tile) * CT + ct) * 64 + lane];
-#pragma unroll
-          for (int q = 1; q < NKW; ++q) {
-            const f32x4 pv = part[(((o * NKW + q) * NT + tile) * CT + ct) * 64 + lane];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) sum[i] += pv[i];
-          }
+          const f32x4 sum = ks_sum_parts<NKW>(part + ((o * NKW * NT + tile) * CT + ct) * 64 + lane, NT * CT * 64);
 #pragma unroll
           for (int i = 0; i < 4; ++i) v[4 * tt + i] = sum[i];
         }
@@ -585,18 +610,10 @@ __global__ __launch_bounds__(256, 1) void conv_ks_s2_dual_kernel(const KsS2Args 
           v[i] = v[i] * sc[o][g][i] + sh[o][g][i];
           if (o == 0 && a.relu) v[i] = fmaxf(v[i], 0.f);
         }
-        if (live) {
-          typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-          const u32x4 ov = {lss_pack_bf2(v[0], v[1]), lss_pack_bf2(v[2], v[3]), lss_pack_bf2(v[4], v[5]), lss_pack_bf2(v[6], v[7])};
-          *reinterpret_cast<u32x4*>((o == 0 ? a.y : a.y2) + opix + g * 32) = ov;
-        }
+        if (live) *reinterpret_cast<u32x4*>((o == 0 ? a.y : a.y2) + opix + g * 32) = ks_pack8(v);
       }
   }
-  if (a.stamps != nullptr) {
-    stamp(5);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    stamp(6);
-  }
+  st.drain();
 }
 
 // w1 (Cout, Cin, 3, 3) + wd (Cout, Cin) fp32 -> the stride-2 kernel's register image, bf16:
@@ -622,55 +639,37 @@ __global__ void pack_weights_ks_s2_dual_kernel(const float* __restrict__ w1, con
 }
 
 struct KsS2Plan {
-  int ok, Ho, Wo, pitch, PB, npb, nposp, ncb, lds, grid, nkw;
+  int ok, lds, grid, nkw;
+  KsS2Args a;
 };
 
 KsS2Plan ks_s2_plan(int B, int H, int W, int Cin, int Cout) {
-  KsS2Plan p = {};
-  if (B <= 0 || H < 2 || W < 4 || Cout <= 0 || Cout % 64 != 0) return p;
-  if (Cin == 128) p.nkw = 4;
-  else if (Cin == 64) p.nkw = 2;
-  else return p;
+  KsS2Plan pl = {};
+  KsS2Args& p = pl.a;
+  if (B <= 0 || H < 2 || W < 4 || Cout <= 0 || Cout % 64 != 0) return pl;
+  if (Cin == 128) pl.nkw = 4;
+  else if (Cin == 64) pl.nkw = 2;
+  else return pl;
+  p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
   p.Ho = (H - 1) / 2 + 1; p.Wo = (W - 1) / 2 + 1;
   p.pitch = 2 * p.Wo + 1;
-  p.PB = 16 * KS2_PXT * (4 / p.nkw);
-  if (p.PB > 2 * p.Wo + 1) return p;                 // a pixel block spans at most three output rows
+  p.PB = 16 * KS2_PXT * (4 / pl.nkw);
+  if (p.PB > 2 * p.Wo + 1) return pl;                // a pixel block spans at most three output rows
   const long long HWo = (long long)p.Ho * p.Wo;
   p.npb = (int)((HWo + p.PB - 1) / p.PB);
   p.ncb = Cout / 64;
   p.nposp = (KS_ROWS * p.pitch + 31) / 32 * 32;
   const int patch = (Cin / 32) * p.nposp * KS_POSB;
-  if (patch > 112 * 1024) return p;
-  const int red = 2 * p.nkw * (p.PB / 16) * KS2_CT * 1024;   // the K parts' partial tiles of both outputs
-  p.lds = patch > red ? patch : red;
-  if (p.lds > KS_LDS_MAX) return p;
+  if (patch > 112 * 1024) return pl;
+  const int red = 2 * pl.nkw * (p.PB / 16) * KS2_CT * 1024;   // the K parts' partial tiles of both outputs
+  pl.lds = patch > red ? patch : red;
+  if (pl.lds > KS_LDS_MAX) return pl;
   const long long grid = (long long)B * p.npb * p.ncb;
-  if (grid < 64 || grid > 512) return p;
-  if ((long long)B * H * W * Cin >= (1LL << 30) || (long long)B * HWo * Cout >= (1LL << 30)) return p;
-  p.grid = (int)grid;
-  p.ok = 1;
-  return p;
-}
-
-template <int NKW>
-int ks_s2_launch(const KsS2Plan& p, const KsS2Args& a, hipStream_t st) {
-  static bool attr_set[64] = {};
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
-  if (dev < 0 || !attr_set[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_ks_s2_dual_kernel<NKW>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, KS_LDS_MAX);
-    if (e != hipSuccess) return (int)e;
-    if (dev >= 0) attr_set[dev] = true;
-  }
-  hipLaunchKernelGGL((conv_ks_s2_dual_kernel<NKW>), dim3(p.grid), dim3(256), p.lds, st, a);
-  return lss_launch_status();
-}
-
-// the diagnostic stamp buffer of tools/bench_ks.py --stamps (every kernel of this file), or null
-unsigned long long* ks_stamps_from_env() {
-  const char* e = getenv("LSS_KS_STAMPS");
-  return e ? reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 16)) : nullptr;
+  if (grid < 64 || grid > 512) return pl;
+  if ((long long)B * H * W * Cin >= (1LL << 30) || (long long)B * HWo * Cout >= (1LL << 30)) return pl;
+  pl.grid = (int)grid;
+  pl.ok = 1;
+  return pl;
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -719,18 +718,10 @@ __global__ __launch_bounds__(256, 1) void conv_ks_stem_kernel(const KsStemArgs a
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = wave & 1, ph = wave >> 1;       // channel half (32 of the 64), row half of the tile
   const int n = lane & 15, kq = lane >> 4;
-  auto stamp = [&](int k) {
-    if (a.stamps != nullptr && tid == 0) a.stamps[(size_t)blockIdx.x * 8 + k] = __builtin_amdgcn_s_memrealtime();
-  };
-  stamp(0);
-  unsigned long long clk_main = 0;
+  KsStamps st = {a.stamps, tid};
+  st.stamp(0);
 
-  int t;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  }
+  const int t = lss_xcd_order(blockIdx.x, gridDim.x);
   const int cb = t % a.ncb;
   const int tg = t / a.ncb;
   const int npi = a.nty * a.ntx;
@@ -740,26 +731,10 @@ __global__ __launch_bounds__(256, 1) void conv_ks_stem_kernel(const KsStemArgs a
   const int iy0 = 2 * oy0 - 3, ix0 = 2 * ox0 - 3;  // input row / column of patch row 0 / relative column 0
 
   // ---- input patch -> LDS, columns de-interleaved: position (pr, pc) <- input (iy0 + pr, ix0 + (pc < 19 ? 2 pc : 2 (pc - 19) + 1))
-  {
-    constexpr int ppc = ST_NPOSP >> 4;
-    constexpr int q64 = 64 / ST_PW, r64 = 64 - q64 * ST_PW;
-    const int h = wave & 1;
-    const int pos0 = 32 * (wave >> 1) + (lane >> 1);
-    int pr = pos0 / ST_PW, pc = pos0 - pr * ST_PW;
-    const unsigned char* zsrc = lss_ks_zero_page + (lane & 7) * 16;
-    const unsigned short* xb = a.x + (size_t)b * a.H * a.W * Cin + (2 * h + (lane & 1)) * 8;
-    for (int i = wave; i < ppc; i += 4) {
-      const int iy = iy0 + pr, ix = ix0 + (pc < ST_NE ? 2 * pc : 2 * (pc - ST_NE) + 1);
-      const bool in = pr < ST_PR && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-      const unsigned short* src = xb + (in ? (iy * a.W + ix) * Cin : 0);
-#pragma unroll
-      for (int c = 0; c < 2; ++c)
-        ks_glds16(in ? (const void*)(src + c * 32) : (const void*)zsrc,
-                  smem + ((size_t)(c * 2 + h) * ST_NPOSP + 32 * (i >> 1)) * 32);
-      pr += q64; pc += r64;
-      if (pc >= ST_PW) { pc -= ST_PW; ++pr; }
-    }
-  }
+  ks_fill_patch<2>(smem, a.x + (size_t)b * a.H * a.W * Cin, Cin, a.H, a.W, ST_PR, ST_PW, ST_NPOSP, wave, lane,
+                   [&](int pr, int pc, int& iy, int& ix) {
+                     iy = iy0 + pr; ix = ix0 + (pc < ST_NE ? 2 * pc : 2 * (pc - ST_NE) + 1);
+                   });
 
   // ---- weights: the first ST_WPRE k-steps of this wave's two channel tiles; the window never closes ----
   bf16x8 wf[ST_KS][2];
@@ -773,7 +748,7 @@ __global__ __launch_bounds__(256, 1) void conv_ks_stem_kernel(const KsStemArgs a
 
   // lane base of row segment 0 of this wave; segment j adds 2 j pitch positions, tap (ky, kx) its wave-uniform offset
   const int ab0 = (2 * (ph * PXT) * ST_PW + n) * 32 + (kq >> 1) * ST_NPOSP * 32 + (kq & 1) * 16;
-  stamp(1);
+  st.stamp(1);
   f32x4 acc[PXT][2];
 #pragma unroll
   for (int j = 0; j < PXT; ++j) {
@@ -783,16 +758,10 @@ __global__ __launch_bounds__(256, 1) void conv_ks_stem_kernel(const KsStemArgs a
   // epilogue constants of this lane's 8 consecutive channels, requested with everything else
   const int ch = cb * 64 + g * 32 + kq * 8;
   float sc[8], sh[8];
-  {
-    f32x4 s0 = {1.f, 1.f, 1.f, 1.f}, s1 = s0, h0 = {0.f, 0.f, 0.f, 0.f}, h1 = h0;
-    if (a.scale) { s0 = *reinterpret_cast<const f32x4*>(a.scale + ch); s1 = *reinterpret_cast<const f32x4*>(a.scale + ch + 4); }
-    if (a.shift) { h0 = *reinterpret_cast<const f32x4*>(a.shift + ch); h1 = *reinterpret_cast<const f32x4*>(a.shift + ch + 4); }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { sc[i] = s0[i]; sc[4 + i] = s1[i]; sh[i] = h0[i]; sh[4 + i] = h1[i]; }
-  }
+  ks_load_affine(a.scale, a.shift, ch, sc, sh);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the patch pieces have landed
   __syncthreads();
-  stamp(2);
+  st.stamp(2);
 
   // ---- main phase: 98 k-steps x 6 row segments x 2 channel tiles, LDS reads, weight requests and MFMAs only ----
   bf16x8 fb[2][PXT];
@@ -803,7 +772,7 @@ __global__ __launch_bounds__(256, 1) void conv_ks_stem_kernel(const KsStemArgs a
 #pragma unroll
     for (int j = 0; j < PXT; ++j) fb[buf][j] = *reinterpret_cast<const bf16x8*>(cbase + j * (2 * ST_PW * 32));
   };
-  if (a.stamps != nullptr) clk_main = __builtin_amdgcn_s_memtime();
+  st.main_begin();
   load_frags(0, 0);
 #pragma unroll
   for (int s = 0; s < ST_KS; ++s) {
@@ -817,10 +786,8 @@ __global__ __launch_bounds__(256, 1) void conv_ks_stem_kernel(const KsStemArgs a
     }
     __builtin_amdgcn_sched_barrier(0);
   }
-  if (a.stamps != nullptr) asm volatile("s_nop 0" ::"v"(acc[0][0]), "v"(acc[PXT - 1][1]));  // the MFMA chain has retired
-  stamp(3);
-  if (a.stamps != nullptr && tid == 0) a.stamps[(size_t)blockIdx.x * 8 + 7] = __builtin_amdgcn_s_memtime() - clk_main;
-  stamp(4);  // (no K parts to meet)
+  st.main_end(acc[0][0], acc[PXT - 1][1]);
+  st.stamp(4);  // (no K parts to meet)
 
   // ---- epilogue: lane (kq, n) holds channels ch .. ch + 7 of pixel (oy0 + 6 ph + j, ox0 + n) ----
   const int ox = ox0 + n;
@@ -835,17 +802,10 @@ __global__ __launch_bounds__(256, 1) void conv_ks_stem_kernel(const KsStemArgs a
       v[i] = v[i] * sc[i] + sh[i];
       if (a.relu) v[i] = fmaxf(v[i], 0.f);
     }
-    if (oy < a.Ho && ox < a.Wo) {
-      typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-      const u32x4 ov = {lss_pack_bf2(v[0], v[1]), lss_pack_bf2(v[2], v[3]), lss_pack_bf2(v[4], v[5]), lss_pack_bf2(v[6], v[7])};
-      *reinterpret_cast<u32x4*>(a.y + (((size_t)b * a.Ho + oy) * a.Wo + ox) * a.Cout + ch) = ov;
-    }
+    if (oy < a.Ho && ox < a.Wo)
+      *reinterpret_cast<u32x4*>(a.y + (((size_t)b * a.Ho + oy) * a.Wo + ox) * a.Cout + ch) = ks_pack8(v);
   }
-  if (a.stamps != nullptr) {
-    stamp(5);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    stamp(6);
-  }
+  st.drain();
 }
 
 // w (Cout, 64, 7, 7) fp32 -> the stem kernel's register image, bf16: [co block of 64][k-step S = tap * 2 + chunk]
@@ -868,23 +828,26 @@ __global__ void pack_weights_ks_stem_kernel(const float* __restrict__ w, int Cou
 }
 
 struct KsStemPlan {
-  int ok, Ho, Wo, nty, ntx, ncb, grid;
+  int ok, grid;
+  KsStemArgs a;
 };
 
 KsStemPlan ks_stem_plan(int B, int H, int W, int Cin, int Cout) {
-  KsStemPlan p = {};
-  if (B <= 0 || H <= 0 || W <= 0 || Cin != 64 || Cout <= 0 || Cout % 64 != 0) return p;
+  KsStemPlan pl = {};
+  KsStemArgs& p = pl.a;
+  if (B <= 0 || H <= 0 || W <= 0 || Cin != 64 || Cout <= 0 || Cout % 64 != 0) return pl;
+  p.B = B; p.H = H; p.W = W; p.Cout = Cout;
   p.Ho = (H - 1) / 2 + 1; p.Wo = (W - 1) / 2 + 1;
-  if (p.Ho < ST_TH || p.Wo < ST_TW) return p;          // at least one whole tile
+  if (p.Ho < ST_TH || p.Wo < ST_TW) return pl;         // at least one whole tile
   p.nty = (p.Ho + ST_TH - 1) / ST_TH; p.ntx = (p.Wo + ST_TW - 1) / ST_TW;
   p.ncb = Cout / 64;
   const long long grid = (long long)B * p.nty * p.ntx * p.ncb;
   // one workgroup per CU in ONE round; below 32 workgroups the tile kernel's smaller tiles spread wider
-  if (grid < 32 || grid > 256) return p;
-  if ((long long)B * H * W * Cin >= (1LL << 30) || (long long)B * p.Ho * p.Wo * Cout >= (1LL << 30)) return p;
-  p.grid = (int)grid;
-  p.ok = 1;
-  return p;
+  if (grid < 32 || grid > 256) return pl;
+  if ((long long)B * H * W * Cin >= (1LL << 30) || (long long)B * p.Ho * p.Wo * Cout >= (1LL << 30)) return pl;
+  pl.grid = (int)grid;
+  pl.ok = 1;
+  return pl;
 }
 
 }  // namespace
@@ -892,9 +855,7 @@ KsStemPlan ks_stem_plan(int B, int H, int W, int Cin, int Cout) {
 // Is (shape) a case for the K-split one-pass kernel?  3x3 / stride 1 / pad 1, bf16, Cin in {64, 128, 256}, Cout a
 // multiple of 32, an image narrow enough for a pixel block to span five rows, and a grid of 64-512 workgroups.
 extern "C" int lss_conv2d_ks_ok(int B, int H, int W, int Cin, int Cout) {
-  if (const char* e = getenv("LSS_CONV_KS"))
-    if (atoi(e) == 0) return 0;
-  return ks_plan(B, H, W, Cin, Cout).ok;
+  return ks_enabled() && ks_plan(B, H, W, Cin, Cout).ok;
 }
 
 extern "C" size_t lss_conv2d_ks_packed_weight_bytes(int Cout, int Cin) {
@@ -905,9 +866,7 @@ extern "C" size_t lss_conv2d_ks_packed_weight_bytes(int Cout, int Cin) {
 extern "C" int lss_conv2d_pack_weights_ks(const float* w_oihw, int Cout, int Cin, void* w_packed, void* stream) {
   LSS_CHECK_PTR(w_oihw); LSS_CHECK_PTR(w_packed);
   if (lss_conv2d_ks_packed_weight_bytes(Cout, Cin) == 0) return LSS_E_SHAPE;
-  const size_t n = (size_t)Cout * Cin * 9;
-  const int grid = (int)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
-  hipLaunchKernelGGL(pack_weights_ks_kernel, dim3(grid), dim3(256), 0, lss_stream(stream), w_oihw, Cout, Cin,
+  hipLaunchKernelGGL(pack_weights_ks_kernel, dim3(ks_pack_grid((size_t)Cout * Cin * 9)), dim3(256), 0, lss_stream(stream), w_oihw, Cout, Cin,
                      reinterpret_cast<unsigned short*>(w_packed), 0);
   return lss_launch_status();
 }
@@ -917,9 +876,7 @@ extern "C" int lss_conv2d_pack_weights_ks(const float* w_oihw, int Cout, int Cin
 extern "C" int lss_conv2d_pack_weights_ks_dgrad(const float* w_oihw, int Cout, int Cin, void* w_packed, void* stream) {
   LSS_CHECK_PTR(w_oihw); LSS_CHECK_PTR(w_packed);
   if (lss_conv2d_ks_packed_weight_bytes(Cin, Cout) == 0) return LSS_E_SHAPE;
-  const size_t n = (size_t)Cout * Cin * 9;
-  const int grid = (int)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
-  hipLaunchKernelGGL(pack_weights_ks_kernel, dim3(grid), dim3(256), 0, lss_stream(stream), w_oihw, Cin, Cout,
+  hipLaunchKernelGGL(pack_weights_ks_kernel, dim3(ks_pack_grid((size_t)Cout * Cin * 9)), dim3(256), 0, lss_stream(stream), w_oihw, Cin, Cout,
                      reinterpret_cast<unsigned short*>(w_packed), 1);
   return lss_launch_status();
 }
@@ -927,33 +884,28 @@ extern "C" int lss_conv2d_pack_weights_ks_dgrad(const float* w_oihw, int Cout, i
 // launcher behind lss_conv2d_fwd when the weights are KS-packed (LSS_W_KS)
 int lss_conv_ks_launch(const void* x, const void* w_ks, const float* scale, const float* shift, const void* residual,
                        void* y, int B, int H, int W, int Cin, int Cout, int relu, int wt, hipStream_t st) {
-  const KsPlan p = ks_plan(B, H, W, Cin, Cout);
+  KsPlan p = ks_plan(B, H, W, Cin, Cout);
   if (!p.ok) return LSS_E_SHAPE;
   if (relu != 0 && relu != 1) return LSS_E_LAYOUT;
-  if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(w_ks) |
-        reinterpret_cast<uintptr_t>(residual)) & 15) != 0)
-    return LSS_E_ALIGN;
-  KsArgs a;
+  if (!ks_aligned16(x, y, w_ks, residual)) return LSS_E_ALIGN;
+  KsArgs& a = p.a;
   a.x = reinterpret_cast<const unsigned short*>(x);
   a.w = reinterpret_cast<const unsigned char*>(w_ks);
   a.scale = scale; a.shift = shift;
   a.residual = reinterpret_cast<const unsigned short*>(residual);
   a.y = reinterpret_cast<unsigned short*>(y);
-  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.relu = relu; a.wt = wt;
-  a.PB = p.PB; a.npb = p.npb; a.nposp = p.nposp; a.ncb = p.ncb;
+  a.relu = relu; a.wt = wt;
   a.stamps = ks_stamps_from_env();
-  if (p.variant == 0) return ks_launch<18, 4, 5>(p, a, st);
-  if (p.variant == 1) return ks_launch<9, 4, 10>(p, a, st);
-  return ks_launch<9, 2, 10>(p, a, st);
+  if (p.variant == 0) return ks_launch<conv_ks_kernel<18, 4, 5>>(p.grid, p.lds, a, st);
+  if (p.variant == 1) return ks_launch<conv_ks_kernel<9, 4, 10>>(p.grid, p.lds, a, st);
+  return ks_launch<conv_ks_kernel<9, 2, 10>>(p.grid, p.lds, a, st);
 }
 
 // Stride-2 mode (conv1 3x3 / 2 + the 1x1 / 2 downsample of a BasicBlock in one launch): is (shape) a case?  bf16, Cin in
 // {64, 128}, Cout a multiple of 64, an output 48-63 (Cin 64) / 24-31 (Cin 128) pixels wide - the 7-row patch fits LDS
 // and a pixel block of 96 / 48 spans at most three output rows - and a grid of 64-512 workgroups.
 extern "C" int lss_conv2d_ks_s2_dual_ok(int B, int H, int W, int Cin, int Cout) {
-  if (const char* e = getenv("LSS_CONV_KS"))
-    if (atoi(e) == 0) return 0;
-  return ks_s2_plan(B, H, W, Cin, Cout).ok;
+  return ks_enabled() && ks_s2_plan(B, H, W, Cin, Cout).ok;
 }
 
 extern "C" size_t lss_conv2d_ks_s2_dual_packed_weight_bytes(int Cout, int Cin) {
@@ -965,9 +917,7 @@ extern "C" int lss_conv2d_pack_weights_ks_s2_dual(const float* w1_oihw, const fl
                                                   void* w_packed, void* stream) {
   LSS_CHECK_PTR(w1_oihw); LSS_CHECK_PTR(wd_oi); LSS_CHECK_PTR(w_packed);
   if (lss_conv2d_ks_s2_dual_packed_weight_bytes(Cout, Cin) == 0) return LSS_E_SHAPE;
-  const size_t n = (size_t)Cout * Cin * 10;
-  const int grid = (int)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
-  hipLaunchKernelGGL(pack_weights_ks_s2_dual_kernel, dim3(grid), dim3(256), 0, lss_stream(stream), w1_oihw, wd_oi, Cout,
+  hipLaunchKernelGGL(pack_weights_ks_s2_dual_kernel, dim3(ks_pack_grid((size_t)Cout * Cin * 10)), dim3(256), 0, lss_stream(stream), w1_oihw, wd_oi, Cout,
                      Cin, reinterpret_cast<unsigned short*>(w_packed));
   return lss_launch_status();
 }
@@ -976,31 +926,26 @@ extern "C" int lss_conv2d_ks_s2_dual_fwd(const void* x, const void* w_packed, co
                                          void* y, void* y2, int B, int H, int W, int Cin, int Cout, int relu,
                                          void* stream) {
   LSS_CHECK_PTR(x); LSS_CHECK_PTR(w_packed); LSS_CHECK_PTR(y); LSS_CHECK_PTR(y2);
-  const KsS2Plan p = ks_s2_plan(B, H, W, Cin, Cout);
+  KsS2Plan p = ks_s2_plan(B, H, W, Cin, Cout);
   if (!p.ok) return LSS_E_SHAPE;
   if (relu != 0 && relu != 1) return LSS_E_LAYOUT;
-  if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(y2) |
-        reinterpret_cast<uintptr_t>(w_packed) | reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(shift)) & 15) != 0)
-    return LSS_E_ALIGN;
-  KsS2Args a;
+  if (!ks_aligned16(x, y, y2, w_packed, scale, shift)) return LSS_E_ALIGN;
+  KsS2Args& a = p.a;
   a.x = reinterpret_cast<const unsigned short*>(x);
   a.w = reinterpret_cast<const unsigned char*>(w_packed);
   a.scale = scale; a.shift = shift;
   a.y = reinterpret_cast<unsigned short*>(y);
   a.y2 = reinterpret_cast<unsigned short*>(y2);
-  a.B = B; a.H = H; a.W = W; a.Cin = Cin; a.Cout = Cout; a.relu = relu;
-  a.Ho = p.Ho; a.Wo = p.Wo; a.pitch = p.pitch;
-  a.PB = p.PB; a.npb = p.npb; a.nposp = p.nposp; a.ncb = p.ncb;
+  a.relu = relu;
   a.stamps = ks_stamps_from_env();
-  return p.nkw == 4 ? ks_s2_launch<4>(p, a, lss_stream(stream)) : ks_s2_launch<2>(p, a, lss_stream(stream));
+  return p.nkw == 4 ? ks_launch<conv_ks_s2_dual_kernel<4>>(p.grid, p.lds, a, lss_stream(stream))
+                    : ks_launch<conv_ks_s2_dual_kernel<2>>(p.grid, p.lds, a, lss_stream(stream));
 }
 
 // Stem mode (7x7 / stride 2 / pad 3, Cin 64, one launch): is (shape) a case?  bf16, Cout a multiple of 64, at least one
 // 12 x 16 tile of outputs, and a grid of 32-256 workgroups (one round; the hires workload's 442 stay on the tile kernel).
 extern "C" int lss_conv2d_ks_stem_ok(int B, int H, int W, int Cin, int Cout) {
-  if (const char* e = getenv("LSS_CONV_KS"))
-    if (atoi(e) == 0) return 0;
-  return ks_stem_plan(B, H, W, Cin, Cout).ok;
+  return ks_enabled() && ks_stem_plan(B, H, W, Cin, Cout).ok;
 }
 
 extern "C" size_t lss_conv2d_ks_stem_packed_weight_bytes(int Cout, int Cin) {
@@ -1011,9 +956,7 @@ extern "C" size_t lss_conv2d_ks_stem_packed_weight_bytes(int Cout, int Cin) {
 extern "C" int lss_conv2d_pack_weights_ks_stem(const float* w_oihw, int Cout, int Cin, void* w_packed, void* stream) {
   LSS_CHECK_PTR(w_oihw); LSS_CHECK_PTR(w_packed);
   if (lss_conv2d_ks_stem_packed_weight_bytes(Cout, Cin) == 0) return LSS_E_SHAPE;
-  const size_t n = (size_t)Cout * Cin * 49;
-  const int grid = (int)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256);
-  hipLaunchKernelGGL(pack_weights_ks_stem_kernel, dim3(grid), dim3(256), 0, lss_stream(stream), w_oihw, Cout,
+  hipLaunchKernelGGL(pack_weights_ks_stem_kernel, dim3(ks_pack_grid((size_t)Cout * Cin * 49)), dim3(256), 0, lss_stream(stream), w_oihw, Cout,
                      reinterpret_cast<unsigned short*>(w_packed));
   return lss_launch_status();
 }
@@ -1021,29 +964,16 @@ extern "C" int lss_conv2d_pack_weights_ks_stem(const float* w_oihw, int Cout, in
 extern "C" int lss_conv2d_ks_stem_fwd(const void* x, const void* w_packed, const float* scale, const float* shift,
                                       void* y, int B, int H, int W, int Cin, int Cout, int relu, void* stream) {
   LSS_CHECK_PTR(x); LSS_CHECK_PTR(w_packed); LSS_CHECK_PTR(y);
-  const KsStemPlan p = ks_stem_plan(B, H, W, Cin, Cout);
+  KsStemPlan p = ks_stem_plan(B, H, W, Cin, Cout);
   if (!p.ok) return LSS_E_SHAPE;
   if (relu != 0 && relu != 1) return LSS_E_LAYOUT;
-  if (((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(w_packed) |
-        reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(shift)) & 15) != 0)
-    return LSS_E_ALIGN;
-  KsStemArgs a;
+  if (!ks_aligned16(x, y, w_packed, scale, shift)) return LSS_E_ALIGN;
+  KsStemArgs& a = p.a;
   a.x = reinterpret_cast<const unsigned short*>(x);
   a.w = reinterpret_cast<const unsigned char*>(w_packed);
   a.scale = scale; a.shift = shift;
   a.y = reinterpret_cast<unsigned short*>(y);
-  a.B = B; a.H = H; a.W = W; a.Cout = Cout; a.relu = relu;
-  a.Ho = p.Ho; a.Wo = p.Wo; a.nty = p.nty; a.ntx = p.ntx; a.ncb = p.ncb;
+  a.relu = relu;
   a.stamps = ks_stamps_from_env();
-  static bool attr_set[64] = {};
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = -1;
-  if (dev < 0 || !attr_set[dev]) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conv_ks_stem_kernel),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, KS_LDS_MAX);
-    if (e != hipSuccess) return (int)e;
-    if (dev >= 0) attr_set[dev] = true;
-  }
-  hipLaunchKernelGGL(conv_ks_stem_kernel, dim3(p.grid), dim3(256), ST_LDS, lss_stream(stream), a);
-  return lss_launch_status();
+  return ks_launch<conv_ks_stem_kernel>(p.grid, ST_LDS, a, lss_stream(stream));
 }

@@ -435,11 +435,7 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
   // the 8 XCDs, so give XCD k the k-th contiguous eighth of the tile list (= a band of image
   // rows): neighbouring tiles then share halo rows through ONE L2 instead of every L2
   // pulling the whole input from the Infinity Cache.  Bijective for any grid size.
-  int t;
-  {
-    const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  }
+  int t = lss_xcd_order(bid, nwg);
   const int tx = t % tilesX; t /= tilesX;
   const int ty = t % tilesY;
   const int b = t / tilesY;

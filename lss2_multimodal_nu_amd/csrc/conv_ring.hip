@@ -206,9 +206,7 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
   // ---- which tile: XCD-aware order (blocks b and b + 8 share an XCD: give each XCD a contiguous range) ----
   RingTile T;
   {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    const int t = lss_xcd_order(blockIdx.x, gridDim.x);
     T.nb = t % a.nblk;
     const int quad = t / a.nblk;
     if (T22) {  // quad = tile (the launcher takes this layout only when the tiles cover the output exactly)

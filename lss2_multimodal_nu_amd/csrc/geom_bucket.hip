@@ -269,11 +269,7 @@ __global__ __launch_bounds__(256, 3) void depthnet_rows_and_voxels_kernel(FusedK
     // halves of a pixel tile read the same x lines, and so do neighbouring tiles (a 128-B line of x holds 32 pixels of
     // one channel and a tile is 16): in id order those four workgroups sat on four XCDs and each L2 fetched the lines
     // for itself - FETCH_SIZE 37 MB for 8.9 MB of trunk features (profiles/r03_hbm_traffic.json).
-    int k2 = id;
-    if (a.k2_xcd) {
-      const int xcd = id & 7, q8 = n2x >> 3, r8 = n2x & 7;
-      k2 = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (id >> 3);
-    }
+    const int k2 = a.k2_xcd ? lss_xcd_order(id, n2x) : id;
     const int tile = k2 >> 1;
     if ((k2 & 1) == 0)
       lss_depthnet::depthnet_rows_f32_body<ND>(a.x, a.w, a.bias, 0, a.D, true, a.Cin, a.HW, a.D, a.C, a.depth, a.feat,

@@ -93,12 +93,7 @@ __global__ __launch_bounds__(256, 3) void linear_mfma_kernel(LinearArgs a) {
   const int r = lane & 31, h = lane >> 5;
   // XCD-aware order: XCD k works on the k-th contiguous eighth of the tile list, column
   // tiles of one row tile adjacent, so a row tile's x rows are fetched into ONE L2
-  int t;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    t = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  }
+  const int t = lss_xcd_order(blockIdx.x, gridDim.x);
   const int n0 = (t % a.ntiles) * BN, m0 = (t / a.ntiles) * BM;
   const int wr = wave >> 1, wc = wave & 1;
   const unsigned short* xbase = a.x;

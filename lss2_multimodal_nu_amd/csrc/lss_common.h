@@ -48,6 +48,14 @@ __device__ __forceinline__ unsigned int lss_pack_bf2(float lo, float hi) {
   return (unsigned int)lss_f2bf(lo) | ((unsigned int)lss_f2bf(hi) << 16);
 }
 
+// XCD-aware block order (cdna_hip_programming.md T1): workgroups are dealt round-robin to the 8 XCDs, so block `bid` of
+// `nwg` takes list position t such that XCD k works on the k-th contiguous eighth of the list - neighbours in the list
+// share ONE L2.  Bijective for any grid size.
+__device__ __forceinline__ int lss_xcd_order(int bid, int nwg) {
+  const int xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+}
+
 __device__ __forceinline__ float lss_wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

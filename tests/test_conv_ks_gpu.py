@@ -106,3 +106,31 @@ def test_ks_input_gradient_conv_vs_autograd(ops, report, cfg):
     tag = "x".join(str(c) for c in cfg)
     assert report("k8k_dgrad_max_rel_" + tag, (out - ref).abs().max() / ref.abs().max()) <= BF16_OUT_TOL
     assert report("k8k_dgrad_rel_l2_" + tag, (out - ref).norm() / ref.norm()) <= BF16_OUT_TOL / 3
+
+
+EXACT_SHAPES = [
+    # B, H, W, Cin, Cout: the smallest each variant's plan takes with odd sizes and a ragged last block
+    (3, 23, 21, 256, 128),   # 483 pixels = 6 blocks of 80 + one of 3; an 80-pixel block spans five rows of 21
+    (2, 41, 43, 128, 128),   # 1763 pixels = 11 blocks of 160 + one of 3
+    (1, 61, 83, 64, 128),    # 5063 pixels = 15 blocks of 320 + one of 263; two K parts x two pixel halves
+]
+
+
+@pytest.mark.parametrize("cfg", EXACT_SHAPES)
+def test_ks_conv_is_exact_on_integer_operands(ops, cfg):
+    """x and the residual integers in [-3, 3], weights integers in [-2, 2], no scale / shift, no ReLU: every product and
+    partial sum is an integer below 2^24 (K <= 9 x 256, |sum| <= 13 827), so every summation order gives the same fp32
+    value and lss_f2bf rounds it to nearest even as torch does: the output EQUALS torch's CPU conv2d + residual rounded
+    with .bfloat16().  One misplaced patch column at an image edge, which the error ratios above would not notice,
+    changes an integer."""
+    B, H, W, Cin, Cout = cfg
+    assert ops.conv_ks_ok(B, H, W, Cin, Cout), "test shape must be a case for the K-split kernel"
+    gen = torch.Generator().manual_seed(sum(cfg))
+    x = torch.randint(-3, 4, (B, Cin, H, W), generator=gen).float()
+    w = torch.randint(-2, 3, (Cout, Cin, 3, 3), generator=gen).float()
+    r = torch.randint(-3, 4, (B, Cout, H, W), generator=gen).float()
+    want = (torch.nn.functional.conv2d(x, w, None, padding=1) + r).permute(0, 2, 3, 1).contiguous().bfloat16()
+    xg = x.permute(0, 2, 3, 1).contiguous().bfloat16().cuda()
+    rg = r.permute(0, 2, 3, 1).contiguous().bfloat16().cuda()
+    y = ops.conv2d_nhwc(xg, ops.pack_conv_weight_ks(w.cuda()), (3, 3), 1, 1, None, None, rg, False, None, 1, None, 1)
+    assert y.dtype == torch.bfloat16 and torch.equal(y.cpu(), want)

@@ -193,3 +193,31 @@ def test_bevencode_plan_replays_the_new_launches(ops):
     assert plan.n == 16 and kinds.count(4) == 2 and 3 not in kinds
     assert torch.equal(a, b)
     assert all(v == 0 for v in ops.timeout_counters().values())
+
+
+EXACT_SHAPES = [
+    # B, H, W, Cin, Cout: the smallest each variant's plan takes with odd sizes and a ragged last block
+    (2, 49, 51, 128, 256),   # 25 x 26 = 650 outputs = 13 blocks of 48 + one of 26; odd W: the last odd-plane column is padding
+    (2, 97, 99, 64, 128),    # 49 x 50 = 2450 outputs = 25 blocks of 96 + one of 50
+]
+
+
+@pytest.mark.parametrize("cfg", EXACT_SHAPES)
+def test_ks_s2_dual_is_exact_on_integer_operands(ops, cfg):
+    """x integers in [-3, 3], both weight sets integers in [-2, 2], no scale / shift, no ReLU: every product and partial
+    sum is an integer below 2^24 (K <= 9 x 128, |sum| <= 6 912), so every summation order gives the same fp32 value and
+    lss_f2bf rounds it to nearest even as torch does: y and y2 EQUAL torch's CPU convs rounded with .bfloat16().  One
+    misplaced column of the de-interleaved patch, which the error ratios above would not notice, changes an integer."""
+    B, H, W, Cin, Cout = cfg
+    assert ops.conv_ks_s2_dual_ok(B, H, W, Cin, Cout), "test shape must be a case for the stride-2 K-split kernel"
+    gen = torch.Generator().manual_seed(sum(cfg))
+    x = torch.randint(-3, 4, (B, Cin, H, W), generator=gen).float()
+    w1 = torch.randint(-2, 3, (Cout, Cin, 3, 3), generator=gen).float()
+    wd = torch.randint(-2, 3, (Cout, Cin, 1, 1), generator=gen).float()
+    want1 = torch.nn.functional.conv2d(x, w1, None, stride=2, padding=1).permute(0, 2, 3, 1).contiguous().bfloat16()
+    want2 = torch.nn.functional.conv2d(x, wd, None, stride=2).permute(0, 2, 3, 1).contiguous().bfloat16()
+    xg = x.permute(0, 2, 3, 1).contiguous().bfloat16().cuda()
+    y, y2 = ops.conv2d_ks_s2_dual_nhwc(xg, ops.pack_conv_weight_ks_s2_dual(w1.cuda(), wd.cuda()), None, None, relu=False)
+    assert y.dtype == torch.bfloat16 and y2.dtype == torch.bfloat16
+    assert torch.equal(y.cpu(), want1)
+    assert torch.equal(y2.cpu(), want2)

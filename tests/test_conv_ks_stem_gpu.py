@@ -208,3 +208,19 @@ def test_bevencode_plan_replays_the_stem_launch(ops, monkeypatch):
     assert plan.n == 16 and kinds[0] == 5 and kinds.count(5) == 1 and kinds.count(4) == 2 and 3 not in kinds and 1 not in kinds
     assert torch.equal(a, b) and torch.equal(a, c)
     assert all(v == 0 for v in ops.timeout_counters().values())
+
+
+def test_ks_stem_is_exact_on_integer_operands(ops):
+    """x integers in [-3, 3], weights integers in [-2, 2], no scale / shift, no ReLU: every product and partial sum is an
+    integer below 2^24 (K = 49 x 64, |sum| <= 18 816), so every summation order gives the same fp32 value and lss_f2bf
+    rounds it to nearest even as torch does: the output EQUALS torch's CPU conv2d rounded with .bfloat16().  The smallest
+    shape the plan takes: 12 x 16 outputs, one tile per image, every edge of the patch from the zero page."""
+    B, H, W, Cin, Cout = 32, 23, 31, 64, 64
+    assert ops.conv_ks_stem_ok(B, H, W, Cin, Cout), "test shape must be a case for the stem mode"
+    gen = torch.Generator().manual_seed(B + H + W + Cin + Cout)
+    x = torch.randint(-3, 4, (B, Cin, H, W), generator=gen).float()
+    w = torch.randint(-2, 3, (Cout, Cin, 7, 7), generator=gen).float()
+    want = torch.nn.functional.conv2d(x, w, None, stride=2, padding=3).permute(0, 2, 3, 1).contiguous().bfloat16()
+    xg = x.permute(0, 2, 3, 1).contiguous().bfloat16().cuda()
+    y = ops.conv2d_ks_stem_nhwc(xg, ops.pack_conv_weight_ks_stem(w.cuda()), None, None, relu=False)
+    assert y.dtype == torch.bfloat16 and torch.equal(y.cpu(), want)

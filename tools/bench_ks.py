@@ -41,20 +41,55 @@ def _stem_operands(B, H, W, Cout):
     return x, ops.pack_conv_weight_s2d(w, 3), ops.pack_conv_weight_ks_stem(w), sc, sh
 
 
+def _record(chain, launch, x):
+    """One recorded launch list of `chain` launches: launch(y) -> the next y, starting from x."""
+    rec = ops.ConvRecorder()
+    ops.set_recorder(rec)
+    y = x
+    for _ in range(chain):
+        y = launch(y)
+    ops.set_recorder(None)
+    return ops.ConvPlan(rec, x, y), x, y
+
+
+def _time_plans(plans, rounds, chain):
+    """plans: {key: (plan, x, y)}.  Three warm-up passes over all of them, then `rounds` HIP-event-timed passes in the
+    same interleaved order; returns {key: sorted us per launch}."""
+    res = {}
+    for _ in range(3):
+        for plan, x, y in plans.values():
+            plan.run(x, y)
+    torch.cuda.synchronize()
+    for _ in range(rounds):
+        for key, (plan, x, y) in plans.items():
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            plan.run(x, y)
+            e.record()
+            torch.cuda.synchronize()
+            res.setdefault(key, []).append(s.elapsed_time(e) * 1e3 / chain)
+    return {k: sorted(v) for k, v in res.items()}
+
+
+def _stamped(launch):
+    """The stamp buffer of one launch() after five warm-up ones."""
+    for _ in range(5):
+        launch()
+    buf = torch.zeros(1024 * 8, dtype=torch.int64, device="cuda")
+    os.environ["LSS_KS_STAMPS"] = "%x" % buf.data_ptr()
+    torch.cuda.synchronize()
+    launch()
+    torch.cuda.synchronize()
+    del os.environ["LSS_KS_STAMPS"]
+    return buf
+
+
 def stamps_stem():
     """Stem mode: no reduce phase (slot 4 = slot 3); 98 k-steps x 12 = 1 176 MFMAs per wave.  L2 -> CU bytes per
     workgroup, from the layout: patch 1 088 positions x 128 B = 136 KiB + weights 392 KiB requested by two waves each."""
     name, B, H, W, Cout = STEM
     x, _, wk, sc, sh = _stem_operands(B, H, W, Cout)
-    for _ in range(5):
-        ops.conv2d_ks_stem_nhwc(x, wk, sc, sh)
-    buf = torch.zeros(1024 * 8, dtype=torch.int64, device="cuda")
-    os.environ["LSS_KS_STAMPS"] = "%x" % buf.data_ptr()
-    torch.cuda.synchronize()
-    ops.conv2d_ks_stem_nhwc(x, wk, sc, sh)
-    torch.cuda.synchronize()
-    del os.environ["LSS_KS_STAMPS"]
-    _print_stamps(name, buf, 1176.0)
+    _print_stamps(name, _stamped(lambda: ops.conv2d_ks_stem_nhwc(x, wk, sc, sh)), 1176.0)
 
 
 def bench_stem(rounds, chain):
@@ -62,28 +97,10 @@ def bench_stem(rounds, chain):
     same input inside one recorded list."""
     name, B, H, W, Cout = STEM
     x, ws2d, wk, sc, sh = _stem_operands(B, H, W, Cout)
-    plans, res = [], {}
-    for tag in ("tile", "ks"):
-        rec = ops.ConvRecorder()
-        ops.set_recorder(rec)
-        for _ in range(chain):
-            y = ops.conv2d_s2_nhwc(x, ws2d, 7, 3, sc, sh, None, True) if tag == "tile" else \
-                ops.conv2d_ks_stem_nhwc(x, wk, sc, sh)
-        ops.set_recorder(None)
-        plans.append((tag, ops.ConvPlan(rec, x, y), y))
-    for _ in range(3):
-        for tag, plan, y in plans:
-            plan.run(x, y)
-    torch.cuda.synchronize()
-    for _ in range(rounds):
-        for tag, plan, y in plans:
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            plan.run(x, y)
-            e.record()
-            torch.cuda.synchronize()
-            res.setdefault(tag, []).append(s.elapsed_time(e) * 1e3 / chain)
-    t, k = sorted(res["tile"]), sorted(res["ks"])
+    res = _time_plans({
+        "tile": _record(chain, lambda _: ops.conv2d_s2_nhwc(x, ws2d, 7, 3, sc, sh, None, True), x),
+        "ks": _record(chain, lambda _: ops.conv2d_ks_stem_nhwc(x, wk, sc, sh), x)}, rounds, chain)
+    t, k = res["tile"], res["ks"]
     print("%-22s tile %5.2f us (min %6.2f)   ks %6.2f us (min %6.2f)   per launch incl. its boundary"
           % (name, t[len(t) // 2], t[0], k[len(k) // 2], k[0]))
 
@@ -105,51 +122,26 @@ def _print_stamps(name, buf, n_mfma):
 def stamps_s2():
     for name, B, H, W, Cin, Cout in S2_LAYERS:
         x, _, wk, sc, sh = _s2_operands(B, H, W, Cin, Cout)
-        for _ in range(5):
-            ops.conv2d_ks_s2_dual_nhwc(x, wk, sc, sh)
-        buf = torch.zeros(1024 * 8, dtype=torch.int64, device="cuda")
-        os.environ["LSS_KS_STAMPS"] = "%x" % buf.data_ptr()
-        torch.cuda.synchronize()
-        ops.conv2d_ks_s2_dual_nhwc(x, wk, sc, sh)
-        torch.cuda.synchronize()
-        del os.environ["LSS_KS_STAMPS"]
-        _print_stamps(name, buf, 120.0)
+        _print_stamps(name, _stamped(lambda: ops.conv2d_ks_s2_dual_nhwc(x, wk, sc, sh)), 120.0)
 
 
 def bench_s2(rounds, chain):
     """Per-launch time of the stride-2 entries inside one recorded list: `chain` launches over the same input (the
     output is half the size, so no dependent chain; the launches still serialise on the stream)."""
-    plans, res = [], {}
+    plans = {}
     for name, B, H, W, Cin, Cout in S2_LAYERS:
         x, wcat, wk, sc, sh = _s2_operands(B, H, W, Cin, Cout)
-        for tag in ("dual", "ks"):
-            rec = ops.ConvRecorder()
-            ops.set_recorder(rec)
-            for _ in range(chain):
-                y, _ = ops.conv2d_s2_dual_nhwc(x, wcat, sc, sh, Cout) if tag == "dual" else \
-                    ops.conv2d_ks_s2_dual_nhwc(x, wk, sc, sh)
-            ops.set_recorder(None)
-            plans.append((name, tag, ops.ConvPlan(rec, x, y), x, y))
-    for _ in range(3):
-        for name, tag, plan, x, y in plans:
-            plan.run(x, y)
-    torch.cuda.synchronize()
-    for _ in range(rounds):
-        for name, tag, plan, x, y in plans:
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            plan.run(x, y)
-            e.record()
-            torch.cuda.synchronize()
-            res.setdefault((name, tag), []).append(s.elapsed_time(e) * 1e3 / chain)
+        # (_record calls its launch at once: the closures never see the next layer's operands)
+        plans[(name, "dual")] = _record(chain, lambda _: ops.conv2d_s2_dual_nhwc(x, wcat, sc, sh, Cout)[0], x)
+        plans[(name, "ks")] = _record(chain, lambda _: ops.conv2d_ks_s2_dual_nhwc(x, wk, sc, sh)[0], x)
+    res = _time_plans(plans, rounds, chain)
     for name, *_ in S2_LAYERS:
-        t, k = sorted(res[(name, "dual")]), sorted(res[(name, "ks")])
+        t, k = res[(name, "dual")], res[(name, "ks")]
         print("%-22s dual %5.2f us (min %6.2f)   ks %6.2f us (min %6.2f)   per launch incl. its boundary"
               % (name, t[len(t) // 2], t[0], k[len(k) // 2], k[0]))
 
 
 def stamps():
-    import numpy as np
     torch.manual_seed(0)
     print("%-22s %4s | %s" % ("K-split kernel (B=4)", "WGs", "start-spread  issue  landed  main  reduce  epilogue  drain | first->last us (p50 / max)"))
     for name, B, H, W, C in LAYERS:
@@ -158,24 +150,7 @@ def stamps():
         w = torch.randn(C, C, 3, 3, device="cuda") * (C * 9) ** -0.5
         sc, sh = torch.rand(C, device="cuda") + 0.5, torch.randn(C, device="cuda") * 0.1
         wk = ops.pack_conv_weight_ks(w)
-        for _ in range(5):
-            ops.conv2d_nhwc(x, wk, (3, 3), 1, 1, sc, sh, r, True, None, 1, None, 1)
-        buf = torch.zeros(1024 * 8, dtype=torch.int64, device="cuda")
-        os.environ["LSS_KS_STAMPS"] = "%x" % buf.data_ptr()
-        torch.cuda.synchronize()
-        ops.conv2d_nhwc(x, wk, (3, 3), 1, 1, sc, sh, r, True, None, 1, None, 1)
-        torch.cuda.synchronize()
-        del os.environ["LSS_KS_STAMPS"]
-        t = buf.view(-1, 8).cpu().numpy().astype(np.float64) * 0.01
-        t = t[t[:, 0] != 0]
-        t0 = t[:, 0].min()
-        f = lambda v: "%5.2f/%5.2f" % (np.median(v), v.max())  # noqa: E731
-        print("%-22s %4d | %s  %s  %s  %s  %s  %s  %s | %s" % (
-            name, len(t), f(t[:, 0] - t0), f(t[:, 1] - t[:, 0]), f(t[:, 2] - t[:, 1]), f(t[:, 3] - t[:, 2]),
-            f(t[:, 4] - t[:, 3]), f(t[:, 5] - t[:, 4]), f(t[:, 6] - t[:, 5]), f(t[:, 6] - t[:, 0])))
-        clk = t[:, 7] * 100.0  # slot 7: s_memtime ticks over the main phase
-        print("%-22s        main phase: %.0f s_memtime ticks (median) = %.1f per MFMA of a wave; ticks per us of s_memrealtime %.0f"
-              % ("", np.median(clk), np.median(clk) / 180.0, np.median(clk / np.maximum(t[:, 3] - t[:, 2], 1e-3))))
+        _print_stamps(name, _stamped(lambda: ops.conv2d_nhwc(x, wk, (3, 3), 1, 1, sc, sh, r, True, None, 1, None, 1)), 180.0)
     stamps_s2()
     stamps_stem()
 
@@ -189,35 +164,19 @@ def main():
     if a.stamps:
         return stamps()
     torch.manual_seed(0)
-    res = {}
-    plans = []
+    plans = {}
     for name, B, H, W, C in LAYERS:
         x = torch.randn(B, H, W, C, device="cuda").bfloat16()
         r = torch.randn(B, H, W, C, device="cuda").bfloat16()
         w = torch.randn(C, C, 3, 3, device="cuda") * (C * 9) ** -0.5
         sc, sh = torch.rand(C, device="cuda") + 0.5, torch.randn(C, device="cuda") * 0.1
         for tag, wp in (("tile", ops.pack_conv_weight(w, 1)), ("ks", ops.pack_conv_weight_ks(w))):
-            rec = ops.ConvRecorder()
-            ops.set_recorder(rec)
-            y = x
-            for _ in range(a.chain):   # a dependent chain, like the network: each launch reads the previous one's output
-                y = ops.conv2d_nhwc(y, wp, (3, 3), 1, 1, sc, sh, r, True, None, 1, None, 1)
-            ops.set_recorder(None)
-            plans.append((name, tag, ops.ConvPlan(rec, x, y), x, y, 2.0 * B * H * W * C * C * 9))
-    for _ in range(3):
-        for name, tag, plan, x, y, fl in plans:
-            plan.run(x, y)
-    torch.cuda.synchronize()
-    for _ in range(a.rounds):
-        for name, tag, plan, x, y, fl in plans:
-            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s.record()
-            plan.run(x, y)
-            e.record()
-            torch.cuda.synchronize()
-            res.setdefault((name, tag), []).append(s.elapsed_time(e) * 1e3 / a.chain)
+            # a dependent chain, like the network: each launch reads the previous one's output
+            plans[(name, tag)] = _record(
+                a.chain, lambda y: ops.conv2d_nhwc(y, wp, (3, 3), 1, 1, sc, sh, r, True, None, 1, None, 1), x)
+    res = _time_plans(plans, a.rounds, a.chain)
     for name, B, H, W, C in LAYERS:
-        t, k = sorted(res[(name, "tile")]), sorted(res[(name, "ks")])
+        t, k = res[(name, "tile")], res[(name, "ks")]
         print("%-22s tile %6.2f us (min %6.2f)   ks %6.2f us (min %6.2f)   per launch incl. its boundary"
               % (name, t[len(t) // 2], t[0], k[len(k) // 2], k[0]))
     bench_s2(a.rounds, a.chain)
