@@ -317,7 +317,8 @@ int lss_layernorm_fwd(const void* x, int x_dt, const float* gamma, const float* 
  *     y = act( scale[co] * conv(in, w)[.., co] + shift[co] + residual )
  * where `in` is either x itself, or (fused gather) the channel concat
  *     [ x2 , bilinear_align_corners_upsample(x, up) ]          (ref Up.forward)
- *   x        (B, H, W, Cx)  NHWC, dtype `dt`
+ *   x        (B, H, W, Cx)  NHWC, dtype `dt`; Cx % 8 == 0 (fp32), Cx % 32 == 0 (bf16), and Cx, C2 % 64 == 0 for the
+ *            bf16 fused gather; LSS_E_SHAPE otherwise
  *   x2       (B, H*up, W*up, C2) NHWC or NULL (C2 = 0)
  *   w        packed weights from lss_conv2d_pack_weights
  *   scale, shift (Cout) fp32 or NULL (=1 / =0): folded eval-mode BatchNorm or bias

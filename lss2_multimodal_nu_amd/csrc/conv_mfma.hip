@@ -240,9 +240,10 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(ConvArgs a) {
           av[s] = make_uint4(0, 0, 0, 0);
           b0[s] = make_uint4(0, 0, 0, 0);
           b1[s] = make_uint4(0, 0, 0, 0);
-          if (in_ok) av[s] = load_in_piece<T, FUSED>(a, b, iy, ix, c + s * PIECE);
-          if (c0_ok) b0[s] = *reinterpret_cast<const uint4*>(w0 + c + s * PIECE);
-          if (c1_ok) b1[s] = *reinterpret_cast<const uint4*>(w1 + c + s * PIECE);
+          const bool k_ok = c + s * PIECE < a.Cin;  // bf16 rows of Cin % 64 == 32 channels end inside the last block
+          if (in_ok && k_ok) av[s] = load_in_piece<T, FUSED>(a, b, iy, ix, c + s * PIECE);
+          if (c0_ok && k_ok) b0[s] = *reinterpret_cast<const uint4*>(w0 + c + s * PIECE);
+          if (c1_ok && k_ok) b1[s] = *reinterpret_cast<const uint4*>(w1 + c + s * PIECE);
         }
         if (sizeof(T) == 2) {
 #pragma unroll
@@ -1250,8 +1251,11 @@ extern "C" int lss_conv2d_fwd(const void* x, const void* x2, const void* w_packe
     return lss_conv_ring_launch(x, x2, w_packed, scale, shift, y, nullptr, nullptr, nullptr, 0, B, H, W, Cx, C2, up, Cout,
                                 relu & 1, wt_ring ? 1 : 0, lss_stream(stream));
   }
-  const int kblock = dt == LSS_DT_BF16 ? 64 : 8;
-  // K blocks never straddle the x2 | upsample(x) boundary
+  // K blocks never straddle the x2 | upsample(x) boundary.  A plain bf16 input may end in half a K block
+  // (Cin % 64 == 32): the GEMM kernel of the 1x1 layers stages 32-channel slabs, and the direct kernel leaves the
+  // missing half of its last block at zero
+  const bool fused = (up > 1) || (C2 > 0);
+  const int kblock = dt == LSS_DT_BF16 ? (fused ? 64 : 32) : 8;
   if (Cx % kblock != 0 || C2 % kblock != 0) return LSS_E_SHAPE;
   ConvArgs a;
   a.stamps = conv_stamps_from_env();
@@ -1277,7 +1281,6 @@ extern "C" int lss_conv2d_fwd(const void* x, const void* x2, const void* w_packe
   a.head_w = nullptr; a.head_b = nullptr; a.head_out = nullptr; a.head_n = 0;
   a.ry = a.Hin > 1 ? (float)(H - 1) / (float)(a.Hin - 1) : 0.f;
   a.rx = a.Win > 1 ? (float)(W - 1) / (float)(a.Win - 1) : 0.f;
-  const bool fused = (up > 1) || (C2 > 0);
   dim3 grid(lss_cdiv(M, 128), lss_cdiv(Cout, 64));
   if (grid.y > 65535) return LSS_E_SHAPE;
   hipStream_t st = lss_stream(stream);
