@@ -309,6 +309,46 @@ int lss_layernorm_fwd(const void* x, int x_dt, const float* gamma, const float* 
                       long long rows, int C, float eps, void* y, int y_dt, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * K11  training gradients of the BEV transformer's linears and LayerNorms (csrc/linear_grad.hip).
+ * replaces: the autograd nodes (AddmmBackward, NativeLayerNormBackward) that `loss.backward()`,
+ *           train_vovnet_transformer.py:210, runs for the nn.Linear / nn.LayerNorm defined and used in
+ *           src/transformer_modules.py:77-84 (sampling_offsets, attention_weights, value_proj, output_proj),
+ *           :170-215 (linear1, linear2, norm1, norm2 and the encoder layer's forward).
+ *
+ * lss_linear_wgrad: weight and bias gradient of y = x W^T + b,
+ *        dw[n, k] = sum_t dy[t, n] x[t, k]        db[n] = sum_t dy[t, n]
+ *   x (T, K) bf16, dy (T, N) bf16, token-major and contiguous, read once per 64 x 64 output tile as they lie (the token
+ *   dimension is transposed in the kernel's LDS reads); fp32 accumulation on the bf16 MFMA.  dw (N, K) fp32, db (N)
+ *   fp32, fully written; either may be NULL (x may be NULL when dw is), not both.  The token range is split over
+ *   workgroups; the fp32 partial tiles go to `workspace` (>= lss_linear_wgrad_workspace_bytes(T, N, K) bytes =
+ *   splits * (N K + N) floats, contents need not be zero) and are added in split order.  The split count is a function
+ *   of (T, N, K) alone, there are no float atomics: two calls give the same bits.  Rows at and beyond T are never read.
+ *   A non-finite dy[t, n] reaches dw[n, :] and db[n] only.
+ *   lss_linear_wgrad_ok: 1 for N % 64 == 0, K % 64 == 0, 64 <= N, K <= 1024, 1 <= T <= 2^22; else LSS_E_SHAPE.
+ *   Also LSS_E_NULL, LSS_E_ALIGN (16 B for x, dy, workspace; 4 B for dw, db), LSS_E_WORKSPACE; nothing is written when
+ *   a check fails.
+ *
+ * lss_layernorm_bwd: backward of lss_layernorm_fwd.  x (rows, C) in x_dt, dy (rows, C) in dy_dt, gamma (C) fp32 ->
+ *   dx (rows, C) in dx_dt, dgamma (C), dbeta (C) fp32, all fully written (dtypes LSS_DT_F32 | LSS_DT_BF16).  Mean and
+ *   1 / sigma are recomputed from x with the forward kernel's arithmetic:
+ *        xhat = (x - mean) / sigma,  a = dy gamma,  dx = (a - mean(a) - xhat mean(a xhat)) / sigma,
+ *        dgamma = sum_rows dy xhat,  dbeta = sum_rows dy.
+ *   Each workgroup writes one partial (2, C) vector of its row range to `workspace`
+ *   (>= lss_layernorm_bwd_workspace_bytes(rows) bytes); a second stage adds them in order: no float atomics.
+ *   lss_layernorm_bwd_ok: 1 for C == 256, 1 <= rows < 2^31; else LSS_E_SHAPE.  Also LSS_E_NULL (every pointer is
+ *   required), LSS_E_LAYOUT (dtype), LSS_E_ALIGN (16 B; 4 B for dgamma, dbeta), LSS_E_WORKSPACE; nothing is written
+ *   when a check fails. */
+int lss_linear_wgrad_ok(int T, int N, int K);
+size_t lss_linear_wgrad_workspace_bytes(int T, int N, int K);
+int lss_linear_wgrad(const void* x, const void* dy, int T, int N, int K, void* workspace, size_t workspace_bytes,
+                     float* dw, float* db, void* stream);
+int lss_layernorm_bwd_ok(long long rows, int C);
+size_t lss_layernorm_bwd_workspace_bytes(long long rows);
+int lss_layernorm_bwd(const void* x, int x_dt, const void* dy, int dy_dt, const float* gamma, long long rows, int C,
+                      float eps, void* workspace, size_t workspace_bytes, void* dx, int dx_dt, float* dgamma,
+                      float* dbeta, void* stream);
+
+/* ---------------------------------------------------------------------------
  * K8  BevEncode convolutions: implicit-GEMM on MFMA, NHWC activations.
  * replaces: the conv2d / batch_norm / relu / add / interpolate / cat ATen ops of
  *           src/modules.py:22-27, 118-130 (and torchvision BasicBlock.forward).

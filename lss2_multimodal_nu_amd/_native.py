@@ -40,6 +40,13 @@ SIGNATURES = {
     "lss_pointwise_conv_bwd_workspace_bytes": (_sz, [_i] * 4),
     "lss_pointwise_conv_bwd": (_i, [_vp, _i, ctypes.c_longlong, _vp, _i, _vp] + [_i] * 4 + [_vp, _sz] + [_vp] * 4),
     "lss_layernorm_fwd": (_i, [_vp, _i, _vp, _vp, ctypes.c_longlong, _i, ctypes.c_float, _vp, _i, _vp]),
+    "lss_linear_wgrad_ok": (_i, [_i] * 3),
+    "lss_linear_wgrad_workspace_bytes": (_sz, [_i] * 3),
+    "lss_linear_wgrad": (_i, [_vp, _vp, _i, _i, _i, _vp, _sz, _vp, _vp, _vp]),
+    "lss_layernorm_bwd_ok": (_i, [ctypes.c_longlong, _i]),
+    "lss_layernorm_bwd_workspace_bytes": (_sz, [ctypes.c_longlong]),
+    "lss_layernorm_bwd": (_i, [_vp, _i, _vp, _i, _vp, ctypes.c_longlong, _i, ctypes.c_float, _vp, _sz, _vp, _i, _vp, _vp,
+                               _vp]),
     "lss_linear_res_ln_fwd": (_i, [_vp] * 4 + [ctypes.c_longlong, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
     "lss_ffn_fused_fwd": (_i, [_vp] * 5 + [ctypes.c_longlong, _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
     "lss_lift_splat_fwd": (_i, [_vp] * 3 + [_i] * 9 + [_vp, _i, _vp]),

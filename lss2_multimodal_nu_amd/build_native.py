@@ -29,6 +29,7 @@ SOURCES = {
     "bev_transformer.hip": [],
     "deform_grad.hip": [],
     "pointwise_grad.hip": [],
+    "linear_grad.hip": ["-fno-slp-vectorize"],  # no v_pk_*_f32 next to MFMAs, as conv_ring.hip
     "linear_mfma.hip": [],
     "ffn_fused.hip": [],
     "conv_grad.hip": [],

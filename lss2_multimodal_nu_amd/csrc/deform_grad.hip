@@ -313,6 +313,17 @@ __global__ __launch_bounds__(256) void deform_convert_kernel(const unsigned long
   reinterpret_cast<f32x4*>(d_value)[i] = o;
 }
 
+// Zero fill as a KERNEL, not hipMemsetAsync: inside a captured graph the memset nodes of this entry (two identical ones
+// per call from B = 2 on) did not survive a relaunch - sample 1's d_value came out wrong from the second replay on,
+// while graphs of kernel nodes alone replay bit-equal.  n16 16-byte words.
+__global__ __launch_bounds__(256) void deform_zero_kernel(uint4* __restrict__ p, size_t n16) {
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256)
+    p[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+__global__ void deform_zero_words_kernel(unsigned int* __restrict__ p, int n) {
+  for (int i = threadIdx.x; i < n; i += blockDim.x) p[i] = 0u;
+}
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 inline int ceil_log2(long long n) {
@@ -351,19 +362,23 @@ extern "C" int lss_deform_attn_bwd(const float* value, const float* offsets_logi
   unsigned int* maxbits = flags + HW * 8;
   const int lgN = ceil_log2(HW);
   const long long n4 = HW * TC / 4;
+  const size_t n16 = (size_t)HW * (TC * 8 + 8 * 4) / 16;
 
   hipLaunchKernelGGL(deform_grad_ol_kernel, dim3(lss_cdiv(rows, 8)), dim3(256), 0, st, value, offsets_logits,
                      ref_pts, ref_bstride, d_out, B, H, W, d_offsets_logits);
   int rc = lss_launch_status();
   if (rc) return rc;
-  if (hipMemsetAsync(maxbits, 0, (size_t)B * 4, st) != hipSuccess) return lss_launch_status();
+  hipLaunchKernelGGL(deform_zero_words_kernel, dim3(1), dim3(256), 0, st, maxbits, B);
+  if ((rc = lss_launch_status())) return rc;
   hipLaunchKernelGGL(deform_absmax_kernel, dim3((unsigned)std::min<long long>(lss_cdiv(n4, 256), 256), B), dim3(256),
                      0, st, d_out, n4, maxbits);
   if ((rc = lss_launch_status())) return rc;
   const int tiles = lss_cdiv(H, TS) * lss_cdiv(W, TS);
   // samples one after another through one sample's sums (the workspace stays B-independent)
   for (int b = 0; b < B; ++b) {
-    if (hipMemsetAsync(sums, 0, (size_t)HW * (TC * 8 + 8 * 4), st) != hipSuccess) return lss_launch_status();
+    hipLaunchKernelGGL(deform_zero_kernel, dim3((unsigned)std::min<size_t>((n16 + 255) / 256, 4096)), dim3(256), 0, st,
+                       reinterpret_cast<uint4*>(sums), n16);  // the sums and the flag words behind them
+    if ((rc = lss_launch_status())) return rc;
     hipLaunchKernelGGL(deform_scatter_kernel, dim3(tiles, 8 * (32 / CS)), dim3(256), 0, st, offsets_logits, ref_pts,
                        ref_bstride, d_out, b, H, W, maxbits, lgN, sums, flags);
     if ((rc = lss_launch_status())) return rc;

@@ -1,0 +1,424 @@
+// K11: the training gradients of the BEV transformer's linears and LayerNorms that no existing kernel covers
+// (replaces the AddmmBackward / NativeLayerNormBackward nodes that `loss.backward()`, ref train_vovnet_transformer.py:210,
+// runs for the nn.Linear / nn.LayerNorm of ref src/transformer_modules.py:77-84, 170-215).  The input gradient of a
+// linear is the forward GEMM on the transposed weight (linear_mfma.hip) and needs nothing here.
+//
+// lss_linear_wgrad      dw[n, k] = sum_t dy[t, n] x[t, k],  db[n] = sum_t dy[t, n]     (y = x W^T + b, bf16 operands)
+//   The contraction index is the TOKEN index, the slow dimension of both operands.  As in K9w (conv_wgrad.hip) both
+//   tensors are read token-major as they lie and transposed on the way into the matrix core by `ds_read_b64_tr_b16`.
+//   Workgroup = one 64 (n) x 64 (k) output tile over one range of tokens; 4 waves.  A stage is 128 tokens: 16 KiB of dy
+//   columns n0 .. n0+63 and 16 KiB of x columns k0 .. k0+63.  Wave w owns tokens 32 w .. 32 w + 31 of every stage:
+//   8 + 8 transposed reads feed the 4 x 4 tiles of v_mfma_f32_16x16x32_bf16 (64 accumulator registers, 0.5 KiB of LDS
+//   per MFMA as in K9w).  The four waves' accumulators are added in wave order through LDS at the end, and the tile goes
+//   to the workspace as partial[split][N][K]; linear_wgrad_reduce_kernel adds the splits in split order.
+//   Pipeline: plain double buffer.  The global loads of stage s + 1 are issued into registers before the MFMAs of stage
+//   s, stored to the other LDS buffer after them, ONE workgroup barrier per stage.  No flag words, nothing to time out.
+//   LDS image (both operands, K9w's): token-major, 128 B per token = four 32-B channel tiles, the tile index
+//   XOR-swizzled by f(t) = bit1(t) | bit3(t) << 1, so the 8 tokens a 32-lane half reads fall in 8 different 8-bank
+//   groups.  LDS = 2 buffers x 2 operands x 16 KiB = 64 KiB (two workgroups per CU); the end-of-kernel reduction reuses it.
+//   Tail: tokens at and beyond T are zero-SELECTED in the staging registers (never loaded, never multiplied by zero
+//   outside the MFMA): they add exact zeros.  All 256 threads run every transposed read (EXEC all ones); the read
+//   addresses are multiples of 8 B.
+//   db: the workgroups of k tile 0 add up the dy pieces they stage (from the staging registers, fp32), 32 partial sums
+//   per column, added in a fixed order through LDS at the end: db costs no second pass over dy.
+//   Split rule (a function of (T, N, K) alone): stages = ceil(T / 128), tiles = (N / 64)(K / 64),
+//   want = clamp(512 / tiles, 1, stages), per = ceil(stages / want), splits = ceil(stages / per).  No float atomics.
+//
+// lss_layernorm_bwd     backward of lss_layernorm_fwd (C = 256), one wave per row, 4 channels per lane
+//   Recomputes mean and 1 / sigma with layernorm_kernel's own two-pass arithmetic (the forward saves only its input):
+//     xhat = (x - mean) / sigma,   a = g gamma,   dx = (a - mean(a) - xhat mean(a xhat)) / sigma
+//     dgamma = sum_rows g xhat,    dbeta = sum_rows g
+//   A workgroup walks a row range (wave w: rows r0 + w, r0 + w + 4, ..), its four waves' (2, 256) sums are added in wave
+//   order and written as one partial vector; layernorm_bwd_reduce_kernel adds the workgroups' partials in order.
+//   Row ranges: groups = min(ceil(rows / 4), 1024), rows per group = ceil(rows / groups).
+#include <algorithm>
+
+#include "lss_common.h"
+
+namespace {
+
+constexpr int LG_TOK = 128;           // tokens per stage
+constexpr int LG_BLK = 32 * 128;      // 4096 B: 32 tokens x 64 channels
+constexpr int LG_OPER = 4 * LG_BLK;   // one operand of a stage
+constexpr int LG_BUF = 2 * LG_OPER;   // dy then x
+constexpr int LG_MAXWG = 512;         // two workgroups per CU
+constexpr int LN_C = 256;
+constexpr int LN_MAXGROUPS = 1024;
+
+struct LinWgradArgs {
+  const unsigned short* x;   // (T, K) bf16
+  const unsigned short* dy;  // (T, N) bf16
+  float* part;               // [splits][N][K]
+  float* dbp;                // [splits][N]
+  int T, N, K;
+  int ntk;      // k tiles of the grid (1 when only db is asked for)
+  int nstage;   // ceil(T / 128)
+  int per;      // stages per split
+  int want_dw, want_db;
+};
+
+typedef __attribute__((ext_vector_type(4))) short lg_s16x4;
+typedef __attribute__((ext_vector_type(8))) short lg_s16x8;
+typedef __attribute__((ext_vector_type(8))) __bf16 lg_bf16x8;
+typedef __attribute__((ext_vector_type(4))) float lg_f32x4;
+
+__device__ __forceinline__ int lg_swz(int pos) { return ((pos >> 1) & 1) | (((pos >> 3) & 1) << 1); }
+
+// 4 tokens x 16 channels, transposed: this lane's channel at the 4 tokens
+__device__ __forceinline__ lg_s16x4 lg_tr(const unsigned char* p) {
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) lg_s16x4*)p);
+}
+__device__ __forceinline__ lg_bf16x8 lg_frag(const unsigned char* lo, const unsigned char* hi) {
+  const lg_s16x4 a = lg_tr(lo), b = lg_tr(hi);
+  const lg_s16x8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
+  return __builtin_bit_cast(lg_bf16x8, v);
+}
+
+__global__ __launch_bounds__(256) void linear_wgrad_kernel(const LinWgradArgs a) {
+  __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * LG_BUF];
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int ntn = a.N >> 6;
+  int bid = blockIdx.x;
+  const int kt = bid % a.ntk; bid /= a.ntk;
+  const int nt = bid % ntn;
+  const int split = bid / ntn;
+  const int n0 = nt * 64, k0 = kt * 64;
+  const int st0 = split * a.per;
+  const int nst = min(a.per, a.nstage - st0);  // >= 1 by construction of the grid
+  const bool do_dw = a.want_dw != 0;           // workgroup-uniform, as is do_db
+  const bool do_db = a.want_db != 0 && kt == 0;
+
+  // staging: thread = token p32 of each of the stage's four 32-token blocks, 16-B piece c of its 128-B row
+  const int p32 = tid >> 3, c = tid & 7;
+  const int soff = p32 * 128 + (((c >> 1) ^ lg_swz(p32)) << 5) + (c & 1) * 16;
+  uint4 rd[4], rx[4];
+  auto fetch = [&](int st) {
+    const long long tb = (long long)(st0 + st) * LG_TOK + p32;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const long long t = tb + 32 * j;
+      const bool ok = t < a.T;
+      rd[j] = make_uint4(0u, 0u, 0u, 0u);
+      rx[j] = make_uint4(0u, 0u, 0u, 0u);
+      if (ok) rd[j] = *reinterpret_cast<const uint4*>(a.dy + (size_t)t * a.N + n0 + 8 * c);
+      if (ok && do_dw) rx[j] = *reinterpret_cast<const uint4*>(a.x + (size_t)t * a.K + k0 + 8 * c);
+    }
+  };
+  float dbacc[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) dbacc[e] = 0.f;
+  auto put = [&](int buf) {
+    unsigned char* b = smem + buf * LG_BUF + soff;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      *reinterpret_cast<uint4*>(b + j * LG_BLK) = rd[j];
+      if (do_dw) *reinterpret_cast<uint4*>(b + LG_OPER + j * LG_BLK) = rx[j];
+    }
+    if (do_db) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const unsigned int w4[4] = {rd[j].x, rd[j].y, rd[j].z, rd[j].w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          dbacc[2 * e] += lss_bf2f((unsigned short)(w4[e] & 0xffffu));
+          dbacc[2 * e + 1] += lss_bf2f((unsigned short)(w4[e] >> 16));
+        }
+      }
+    }
+  };
+
+  // transposed reads: lane (g, q, p) supplies token 8 g + 4 h + q, channels 16 ct + 4 p .. + 3 and receives channel
+  // 16 ct + (lane & 15) at tokens 8 g + 4 h .. + 3 - the 16x16x32 operand's k = 8 g .. 8 g + 7
+  const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+  int roff[2][4];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int pa = 8 * g + 4 * h + q;
+#pragma unroll
+    for (int ct = 0; ct < 4; ++ct) roff[h][ct] = pa * 128 + ((ct ^ lg_swz(pa)) << 5) + p * 8;
+  }
+  lg_f32x4 acc[4][4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[i][j] = (lg_f32x4){0.f, 0.f, 0.f, 0.f};
+
+  fetch(0);
+  put(0);
+  __syncthreads();
+  for (int s = 0; s < nst; ++s) {
+    const bool more = s + 1 < nst;
+    if (more) fetch(s + 1);
+    if (do_dw) {
+      const unsigned char* db_ = smem + (s & 1) * LG_BUF + wave * LG_BLK;
+      const unsigned char* xb = db_ + LG_OPER;
+      lg_bf16x8 fa[4], fb[4];
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) fa[ct] = lg_frag(db_ + roff[0][ct], db_ + roff[1][ct]);
+#pragma unroll
+      for (int ct = 0; ct < 4; ++ct) fb[ct] = lg_frag(xb + roff[0][ct], xb + roff[1][ct]);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
+    }
+    // the other buffer was last read in iteration s - 1, which every wave has left (the barrier below)
+    if (more) put((s + 1) & 1);
+    __syncthreads();
+  }
+
+  // the four waves' tiles, added in wave order: red[wave][row n][column k ^ swizzle] fp32 over the staging buffers
+  float* red = reinterpret_cast<float*>(smem);
+  if (do_dw) {
+    const int n = lane & 15;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int row = i * 16 + 4 * g + r, col = (j * 16 + n) ^ (g << 4);  // ((row >> 2) & 3) == g
+          red[wave * 4096 + row * 64 + col] = acc[i][j][r];
+        }
+    __syncthreads();
+    float* out = a.part + (size_t)split * a.N * a.K + (size_t)n0 * a.K + k0;
+#pragma unroll
+    for (int m = 0; m < 16; ++m) {
+      const int e = tid + 256 * m, row = e >> 6, col = e & 63;
+      const int pe = row * 64 + (col ^ (((row >> 2) & 3) << 4));
+      out[(size_t)row * a.K + col] = ((red[pe] + red[4096 + pe]) + red[8192 + pe]) + red[12288 + pe];
+    }
+    __syncthreads();
+  }
+  if (do_db) {
+#pragma unroll
+    for (int e = 0; e < 8; ++e) red[p32 * 64 + c * 8 + e] = dbacc[e];
+    __syncthreads();
+    if (tid < 64) {
+      float s = 0.f;
+      for (int i = 0; i < 32; ++i) s += red[i * 64 + tid];
+      a.dbp[(size_t)split * a.N + n0 + tid] = s;
+    }
+  }
+}
+
+// x[i] = the S partials of element i added in split order (four interleaved chains, fixed final tree)
+__device__ __forceinline__ float lg_sum_splits(const float* __restrict__ p, int S, size_t stride) {
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
+  int k = 0;
+  for (; k + 4 <= S; k += 4) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s[i] += p[(size_t)(k + i) * stride];
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+    if (k + i < S) s[i] += p[(size_t)(k + i) * stride];
+  return (s[0] + s[1]) + (s[2] + s[3]);
+}
+
+__global__ __launch_bounds__(256) void linear_wgrad_reduce_kernel(const float* __restrict__ part,
+                                                                  const float* __restrict__ dbp, int S, int NK, int N,
+                                                                  float* __restrict__ dw, float* __restrict__ db) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (dw != nullptr && i < NK) dw[i] = lg_sum_splits(part + i, S, (size_t)NK);
+  if (db != nullptr && i < N) db[i] = lg_sum_splits(dbp + i, S, (size_t)N);
+}
+
+struct LinSplit {
+  int nstage, per, S;
+};
+
+inline LinSplit lin_split(int T, int N, int K) {
+  LinSplit sp;
+  sp.nstage = lss_cdiv(T, LG_TOK);
+  const int tiles = (N / 64) * (K / 64);
+  const int want = std::max(1, std::min(sp.nstage, LG_MAXWG / tiles));
+  sp.per = lss_cdiv(sp.nstage, want);
+  sp.S = lss_cdiv(sp.nstage, sp.per);
+  return sp;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+template <typename T>
+__device__ __forceinline__ f32x4 ln_load4(const T* p);
+template <>
+__device__ __forceinline__ f32x4 ln_load4<float>(const float* p) {
+  return *reinterpret_cast<const f32x4*>(p);
+}
+template <>
+__device__ __forceinline__ f32x4 ln_load4<unsigned short>(const unsigned short* p) {
+  const uint2 v = *reinterpret_cast<const uint2*>(p);
+  return (f32x4){lss_bf2f((unsigned short)(v.x & 0xffff)), lss_bf2f((unsigned short)(v.x >> 16)),
+                 lss_bf2f((unsigned short)(v.y & 0xffff)), lss_bf2f((unsigned short)(v.y >> 16))};
+}
+__device__ __forceinline__ void ln_store4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
+__device__ __forceinline__ void ln_store4(unsigned short* p, f32x4 v) {
+  uint2 o;
+  o.x = lss_pack_bf2(v[0], v[1]);
+  o.y = lss_pack_bf2(v[2], v[3]);
+  *reinterpret_cast<uint2*>(p) = o;
+}
+
+template <typename TX, typename TG, typename TO>
+__global__ __launch_bounds__(256) void layernorm_bwd_kernel(const TX* __restrict__ x, const TG* __restrict__ dy,
+                                                            const float* __restrict__ gamma, long long rows,
+                                                            long long rpg, float eps, TO* __restrict__ dx,
+                                                            float* __restrict__ part) {
+  __shared__ float red[4][2 * LN_C];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long r0 = (long long)blockIdx.x * rpg, r1 = min(rows, r0 + rpg);
+  const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + 4 * lane);
+  f32x4 dg = (f32x4){0.f, 0.f, 0.f, 0.f}, dbt = (f32x4){0.f, 0.f, 0.f, 0.f};
+  for (long long row = r0 + wave; row < r1; row += 4) {  // whole waves: the shuffles below see all 64 lanes
+    const f32x4 v = ln_load4<TX>(x + row * LN_C + 4 * lane);
+    const f32x4 gr = ln_load4<TG>(dy + row * LN_C + 4 * lane);
+    // mean and 1 / sigma exactly as layernorm_kernel computes them
+    const float mean = lss_wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.f / LN_C);
+    const f32x4 d = (f32x4){v[0] - mean, v[1] - mean, v[2] - mean, v[3] - mean};
+    const float var = lss_wave_sum(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3]) * (1.f / LN_C);
+    const float inv = rsqrtf(var + eps);
+    const f32x4 xh = (f32x4){d[0] * inv, d[1] * inv, d[2] * inv, d[3] * inv};
+    const f32x4 ag = (f32x4){gr[0] * gm[0], gr[1] * gm[1], gr[2] * gm[2], gr[3] * gm[3]};
+    const float m1 = lss_wave_sum(ag[0] + ag[1] + ag[2] + ag[3]) * (1.f / LN_C);
+    const float m2 = lss_wave_sum(ag[0] * xh[0] + ag[1] * xh[1] + ag[2] * xh[2] + ag[3] * xh[3]) * (1.f / LN_C);
+    ln_store4(dx + row * LN_C + 4 * lane,
+              (f32x4){(ag[0] - m1 - xh[0] * m2) * inv, (ag[1] - m1 - xh[1] * m2) * inv,
+                      (ag[2] - m1 - xh[2] * m2) * inv, (ag[3] - m1 - xh[3] * m2) * inv});
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      dg[i] += gr[i] * xh[i];
+      dbt[i] += gr[i];
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    red[wave][4 * lane + i] = dg[i];
+    red[wave][LN_C + 4 * lane + i] = dbt[i];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int m = 0; m < 2; ++m) {
+    const int e = tid + 256 * m;
+    part[(size_t)blockIdx.x * (2 * LN_C) + e] = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
+  }
+}
+
+// out[0 .. 255] = dgamma, out[256 .. 511] = dbeta: the groups' partials in group order
+__global__ __launch_bounds__(256) void layernorm_bwd_reduce_kernel(const float* __restrict__ part, int G,
+                                                                   float* __restrict__ dgamma,
+                                                                   float* __restrict__ dbeta) {
+  const int e = blockIdx.x * 256 + threadIdx.x;  // grid of 2
+  const float s = lg_sum_splits(part + e, G, (size_t)(2 * LN_C));
+  if (e < LN_C) dgamma[e] = s;
+  else dbeta[e - LN_C] = s;
+}
+
+struct LnSplit {
+  long long rpg;
+  int G;
+};
+
+inline LnSplit ln_split(long long rows) {
+  LnSplit sp;
+  const long long want = std::min<long long>((rows + 3) / 4, LN_MAXGROUPS);
+  sp.rpg = (rows + want - 1) / want;
+  sp.G = (int)((rows + sp.rpg - 1) / sp.rpg);
+  return sp;
+}
+
+inline bool lg_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+}  // namespace
+
+extern "C" int lss_linear_wgrad_ok(int T, int N, int K) {
+  if (T < 1 || T > (1 << 22)) return 0;
+  if (N < 64 || N > 1024 || K < 64 || K > 1024 || N % 64 != 0 || K % 64 != 0) return 0;
+  return 1;
+}
+
+extern "C" size_t lss_linear_wgrad_workspace_bytes(int T, int N, int K) {
+  if (!lss_linear_wgrad_ok(T, N, K)) return 0;
+  const LinSplit sp = lin_split(T, N, K);
+  return (size_t)sp.S * ((size_t)N * K + N) * sizeof(float);
+}
+
+extern "C" int lss_linear_wgrad(const void* x, const void* dy, int T, int N, int K, void* workspace,
+                                size_t workspace_bytes, float* dw, float* db, void* stream) {
+  LSS_CHECK_PTR(dy);
+  LSS_CHECK_PTR(workspace);
+  if (dw != nullptr) LSS_CHECK_PTR(x);
+  if (dw == nullptr && db == nullptr) return LSS_E_NULL;
+  if (!lss_linear_wgrad_ok(T, N, K)) return LSS_E_SHAPE;
+  if (!lg_aligned(x, 16) || !lg_aligned(dy, 16) || !lg_aligned(workspace, 16) || !lg_aligned(dw, 4) ||
+      !lg_aligned(db, 4))
+    return LSS_E_ALIGN;
+  if (workspace_bytes < lss_linear_wgrad_workspace_bytes(T, N, K)) return LSS_E_WORKSPACE;
+  const LinSplit sp = lin_split(T, N, K);
+  LinWgradArgs a;
+  a.x = static_cast<const unsigned short*>(x);
+  a.dy = static_cast<const unsigned short*>(dy);
+  a.part = static_cast<float*>(workspace);
+  a.dbp = a.part + (size_t)sp.S * N * K;
+  a.T = T; a.N = N; a.K = K;
+  a.ntk = dw != nullptr ? K / 64 : 1;
+  a.nstage = sp.nstage;
+  a.per = sp.per;
+  a.want_dw = dw != nullptr;
+  a.want_db = db != nullptr;
+  hipStream_t st = lss_stream(stream);
+  hipLaunchKernelGGL(linear_wgrad_kernel, dim3(a.ntk * (N / 64) * sp.S), dim3(256), 0, st, a);
+  int rc = lss_launch_status();
+  if (rc != 0) return rc;
+  const int n = std::max(dw != nullptr ? N * K : 0, N);
+  hipLaunchKernelGGL(linear_wgrad_reduce_kernel, dim3(lss_cdiv(n, 256)), dim3(256), 0, st, a.part, a.dbp, sp.S, N * K,
+                     N, dw, db);
+  return lss_launch_status();
+}
+
+extern "C" int lss_layernorm_bwd_ok(long long rows, int C) {
+  return rows >= 1 && rows < (1LL << 31) && C == LN_C;
+}
+
+extern "C" size_t lss_layernorm_bwd_workspace_bytes(long long rows) {
+  if (!lss_layernorm_bwd_ok(rows, LN_C)) return 0;
+  return (size_t)ln_split(rows).G * 2 * LN_C * sizeof(float);
+}
+
+extern "C" int lss_layernorm_bwd(const void* x, int x_dt, const void* dy, int dy_dt, const float* gamma,
+                                 long long rows, int C, float eps, void* workspace, size_t workspace_bytes, void* dx,
+                                 int dx_dt, float* dgamma, float* dbeta, void* stream) {
+  LSS_CHECK_PTR(x); LSS_CHECK_PTR(dy); LSS_CHECK_PTR(gamma); LSS_CHECK_PTR(workspace);
+  LSS_CHECK_PTR(dx); LSS_CHECK_PTR(dgamma); LSS_CHECK_PTR(dbeta);
+  if (!lss_layernorm_bwd_ok(rows, C)) return LSS_E_SHAPE;
+  for (int dt : {x_dt, dy_dt, dx_dt})
+    if (dt != LSS_DT_F32 && dt != LSS_DT_BF16) return LSS_E_LAYOUT;
+  if (!lg_aligned(x, 16) || !lg_aligned(dy, 16) || !lg_aligned(gamma, 16) || !lg_aligned(dx, 16) ||
+      !lg_aligned(workspace, 16) || !lg_aligned(dgamma, 4) || !lg_aligned(dbeta, 4))
+    return LSS_E_ALIGN;
+  if (workspace_bytes < lss_layernorm_bwd_workspace_bytes(rows)) return LSS_E_WORKSPACE;
+  const LnSplit sp = ln_split(rows);
+  float* part = static_cast<float*>(workspace);
+  hipStream_t st = lss_stream(stream);
+  const int code = (x_dt == LSS_DT_BF16 ? 4 : 0) | (dy_dt == LSS_DT_BF16 ? 2 : 0) | (dx_dt == LSS_DT_BF16 ? 1 : 0);
+#define LSS_LNB(TX, TG, TO)                                                                                     \
+  hipLaunchKernelGGL((layernorm_bwd_kernel<TX, TG, TO>), dim3(sp.G), dim3(256), 0, st, static_cast<const TX*>(x), \
+                     static_cast<const TG*>(dy), gamma, rows, sp.rpg, eps, static_cast<TO*>(dx), part)
+  typedef unsigned short bf;
+  switch (code) {
+    case 0: LSS_LNB(float, float, float); break;
+    case 1: LSS_LNB(float, float, bf); break;
+    case 2: LSS_LNB(float, bf, float); break;
+    case 3: LSS_LNB(float, bf, bf); break;
+    case 4: LSS_LNB(bf, float, float); break;
+    case 5: LSS_LNB(bf, float, bf); break;
+    case 6: LSS_LNB(bf, bf, float); break;
+    default: LSS_LNB(bf, bf, bf); break;
+  }
+#undef LSS_LNB
+  int rc = lss_launch_status();
+  if (rc != 0) return rc;
+  hipLaunchKernelGGL(layernorm_bwd_reduce_kernel, dim3(2), dim3(256), 0, st, part, sp.G, dgamma, dbeta);
+  return lss_launch_status();
+}

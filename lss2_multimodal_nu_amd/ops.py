@@ -893,6 +893,74 @@ def conv3x3_wgrad(x, dy):
     return dw
 
 
+def linear_wgrad_ok(T, Nout, K):
+    """True when `linear_wgrad` accepts the shape (Nout % 64 == 0, K % 64 == 0, 64 <= Nout, K <= 1024, 1 <= T <= 2^22)."""
+    return bool(N.lib().lss_linear_wgrad_ok(int(T), int(Nout), int(K)))
+
+
+def linear_wgrad(x, dy, want_dw=True, want_db=True):
+    """K11: weight and bias gradient of y = x W^T + b (lss_linear_wgrad).  x (T, K), dy (T, Nout) contiguous bf16 token
+    rows -> (dw (Nout, K) fp32 | None, db (Nout) fp32 | None), bit-reproducible.  The workspace is cached per shape
+    and device."""
+    for t, nm in ((x, "x"), (dy, "dy")):
+        if t.dim() != 2 or t.dtype != torch.bfloat16 or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous 2-d bf16 tensor, got %s %s" % (nm, t.dtype, tuple(t.shape)))
+    T, K = x.shape
+    if dy.shape[0] != T:
+        raise ValueError("dy %s does not match x %s" % (tuple(dy.shape), tuple(x.shape)))
+    Nout = dy.shape[1]
+    if not (want_dw or want_db):
+        raise ValueError("linear_wgrad: nothing asked for")
+    if not linear_wgrad_ok(T, Nout, K):
+        raise ValueError("linear_wgrad needs N %% 64 == 0, K %% 64 == 0, 64 <= N, K <= 1024, 1 <= T <= 2^22 "
+                         "(got T=%d, N=%d, K=%d)" % (T, Nout, K))
+    if not (x.is_cuda and dy.is_cuda):
+        raise ValueError("x and dy must be GPU tensors")
+    nbytes = N.lib().lss_linear_wgrad_workspace_bytes(T, Nout, K)
+    key = ("linear", T, Nout, K, str(x.device))
+    ws = _wgrad_ws.get(key)
+    if ws is None:
+        ws = _wgrad_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    dw = torch.empty(Nout, K, dtype=torch.float32, device=x.device) if want_dw else None
+    db = torch.empty(Nout, dtype=torch.float32, device=x.device) if want_db else None
+    with _timed("linear_wgrad"):
+        N.check(N.lib().lss_linear_wgrad(N.ptr(x), N.ptr(dy), T, Nout, K, N.ptr(ws), nbytes, N.ptr(dw), N.ptr(db),
+                                         N.stream()), "lss_linear_wgrad")
+    return dw, db
+
+
+def layernorm_bwd(x, dy, gamma, eps, dx_dtype):
+    """K11: backward of `layernorm` (lss_layernorm_bwd).  x, dy contiguous fp32 | bf16 rows of 256, gamma (256) fp32 ->
+    (dx like x in dx_dtype, dgamma (256), dbeta (256) fp32).  Mean and 1 / sigma are recomputed from x."""
+    code = {torch.float32: DT_F32, torch.bfloat16: DT_BF16}
+    for t, nm in ((x, "x"), (dy, "dy")):
+        if not t.is_contiguous() or t.dtype not in code:
+            raise ValueError("%s must be contiguous fp32/bf16" % nm)
+    if dx_dtype not in code:
+        raise ValueError("dx_dtype must be fp32 or bf16")
+    C = x.shape[-1]
+    if tuple(dy.shape) != tuple(x.shape) or x.numel() == 0:
+        raise ValueError("dy %s does not match x %s" % (tuple(dy.shape), tuple(x.shape)))
+    _f32c(gamma, "gamma", (C,))
+    rows = x.numel() // C
+    if not N.lib().lss_layernorm_bwd_ok(rows, C):
+        raise ValueError("layernorm_bwd needs rows of 256 (got %s)" % (tuple(x.shape),))
+    if not (x.is_cuda and dy.is_cuda):
+        raise ValueError("x and dy must be GPU tensors")
+    nbytes = N.lib().lss_layernorm_bwd_workspace_bytes(rows)
+    key = ("layernorm", rows, str(x.device))
+    ws = _wgrad_ws.get(key)
+    if ws is None:
+        ws = _wgrad_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    dx = torch.empty(x.shape, dtype=dx_dtype, device=x.device)
+    dgb = torch.empty(2, C, dtype=torch.float32, device=x.device)
+    with _timed("layernorm_bwd"):
+        N.check(N.lib().lss_layernorm_bwd(N.ptr(x), code[x.dtype], N.ptr(dy), code[dy.dtype], N.ptr(gamma), rows, C,
+                                          float(eps), N.ptr(ws), nbytes, N.ptr(dx), code[dx_dtype], N.ptr(dgb[0]),
+                                          N.ptr(dgb[1]), N.stream()), "lss_layernorm_bwd")
+    return dx, dgb[0], dgb[1]
+
+
 def pack_conv_weight_s2_dgrad(w_oihw, pad):
     """OIHW fp32 of a stride-2 K x K conv -> (KT*KT, 4*Cin, Cout) bf16: the weight of the stride-1 conv that maps dY to
     the four phase planes of dX (lss_conv2d_pack_weights_s2_dgrad).  Returns (packed, KT)."""

@@ -6,10 +6,17 @@ Constructor arguments, `forward()` signatures and `state_dict` keys follow the
 reference.  torch.nn modules are PARAMETER CONTAINERS: in inference the
 arithmetic runs in csrc/ (token-major NHWC activations: the linears are 1x1
 MFMA convs, sampling + softmax + weighting is one gather kernel, residual +
-LayerNorm one row kernel).  Training / autograd runs the same parameters through
-torch ops; on the GPU the deformable-attention sampling core is one native
-autograd node (`_DeformAttnFn`: HIP forward and backward), elsewhere all heads
-are sampled in ONE batched `grid_sample`.
+LayerNorm one row kernel).  Training / autograd: under bf16 autocast on the GPU
+(`_transformer_native_ok`) the encoder layer's five linears and both LayerNorms
+are native autograd nodes too (`_LinearFn`: the MFMA GEMM forward, the same GEMM
+on the transposed weight for the input gradient, csrc/linear_grad.hip for the
+weight and bias gradient; `_LayerNormFn`: the row kernel and its backward), next
+to the deformable-attention sampling core (`_DeformAttnFn`: HIP forward and
+backward); GELU, dropout and the residual adds stay torch elementwise ops.
+Everything else (fp32, fp16 autocast, CPU, d_model != 256,
+LSS_TRANSFORMER_NATIVE=0) runs the parameters through torch ops, all heads
+sampled in ONE batched `grid_sample` where the sampling node does not apply.
+`TRANSFORMER_CALLS` counts the encoder-layer training calls per route.
 """
 import math
 import os
@@ -19,7 +26,12 @@ from torch import nn
 from torch.nn import functional as F
 
 from . import ops
-from .modules import _PRECISIONS, _needs_autograd, _to_nhwc, default_precision
+from .modules import _PRECISIONS, _native_training, _needs_autograd, _to_nhwc, default_precision
+
+# training calls of TransformerEncoderLayer.forward by route (as model_vovnet_transformer.LIFT_CALLS)
+TRANSFORMER_CALLS = {"native": 0, "composition": 0}
+# LSS_TRANSFORMER_NATIVE unset: see DESIGN.md 4b for the measurement that decides this
+_TRANSFORMER_NATIVE_DEFAULT = "1"
 
 
 class _PackedLinear:
@@ -116,6 +128,91 @@ def _deform_native_ok(attn, query, value, reference_points):
             and attn.d_model == 256 and attn.n_heads == 8 and attn.n_points == 8
             and not reference_points.requires_grad
             and os.environ.get("LSS_DEFORM_NATIVE", "1") != "0")
+
+
+class _LinearFn(torch.autograd.Function):
+    """y = x W^T + b over token rows as one native node (ref: the nn.Linear of src/transformer_modules.py:77-84,
+    170-171 under bf16 autocast).  x (..., K) is flattened to contiguous rows and rounded to bf16 - the rounding
+    autocast applies; forward = the 1x1 MFMA conv with the bias as shift; backward: dx = the same kernel on the
+    transposed pack, dw / db = ops.linear_wgrad, the incoming gradient rounded to bf16 once.  Saves the bf16 x and a
+    reference to the weight.  Returns bf16 (fp32 with out_f32); gradients come back in the dtypes of the inputs."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda")
+    def forward(ctx, x, weight, bias, out_f32=False):
+        Nout, K = weight.shape
+        xb = x.detach().reshape(-1, K).to(torch.bfloat16).contiguous()
+        T = xb.shape[0]
+        w = ops.pack_conv_weight(weight.detach().float().reshape(Nout, K, 1, 1).contiguous(), ops.DT_BF16)
+        y = ops.conv2d_nhwc(xb.view(1, T, 1, K), w, (1, 1), 1, 0, None, bias.detach().float().contiguous(), None,
+                            ops.ACT_NONE, dt=ops.DT_BF16, out_f32=out_f32, tag="linear")
+        ctx.save_for_backward(xb, weight)
+        ctx.meta = (tuple(x.shape), x.dtype, bias.dtype)
+        return y.view(tuple(x.shape[:-1]) + (Nout,))
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, dy):
+        xb, weight = ctx.saved_tensors
+        shape, x_dtype, b_dtype = ctx.meta
+        Nout, K = weight.shape
+        T = xb.shape[0]
+        dyb = dy.reshape(T, Nout).to(torch.bfloat16).contiguous()
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            wd = ops.pack_conv_weight_dgrad(weight.detach().float().reshape(Nout, K, 1, 1).contiguous(), ops.DT_BF16)
+            dx = ops.conv2d_nhwc(dyb.view(1, T, 1, Nout), wd, (1, 1), 1, 0, dt=ops.DT_BF16, tag="linear_dgrad")
+            dx = dx.view(shape).to(x_dtype)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            dw, db = ops.linear_wgrad(xb, dyb, ctx.needs_input_grad[1], ctx.needs_input_grad[2])
+            dw = None if dw is None else dw.to(weight.dtype)
+            db = None if db is None else db.to(b_dtype)
+        return dx, dw, db, None
+
+
+class _LayerNormFn(torch.autograd.Function):
+    """nn.LayerNorm(256) over rows as one native node (ref: src/transformer_modules.py:204, 208): forward =
+    ops.layernorm -> fp32 (what autocast's fp32-listed layer_norm returns), backward = ops.layernorm_bwd, which
+    recomputes mean and 1 / sigma.  Saves x and gamma."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda")
+    def forward(ctx, x, gamma, beta, eps):
+        xc = x.detach().contiguous()
+        ctx.save_for_backward(xc, gamma)
+        ctx.eps = eps
+        ctx.dtypes = (gamma.dtype, beta.dtype)
+        return ops.layernorm(xc, gamma.detach().float().contiguous(), beta.detach().float().contiguous(), eps,
+                             torch.float32)
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, dy):
+        xc, gamma = ctx.saved_tensors
+        dyc = dy.contiguous()
+        if dyc.dtype not in (torch.float32, torch.bfloat16):
+            dyc = dyc.float()
+        dx, dg, dbt = ops.layernorm_bwd(xc, dyc, gamma.detach().float().contiguous(), ctx.eps, xc.dtype)
+        return dx, dg.to(ctx.dtypes[0]), dbt.to(ctx.dtypes[1]), None
+
+
+def _transformer_native_ok(layer, src, pos, reference_points):
+    """Does this TransformerEncoderLayer training call take the native linear / LayerNorm nodes?  (GPU tensors, bf16
+    autocast - `modules._native_training()` -, d_model 256, d_ff a multiple of 64 up to 1024, a square token grid whose
+    token count `lss_linear_wgrad_ok` accepts, the deformable-attention node's own conditions, and the switch
+    LSS_TRANSFORMER_NATIVE.)"""
+    if os.environ.get("LSS_TRANSFORMER_NATIVE", _TRANSFORMER_NATIVE_DEFAULT) == "0":
+        return False
+    if not (src.is_cuda and pos.is_cuda and src.dim() == 3 and _native_training()):
+        return False
+    B, N, C = src.shape
+    d_ff, d_model = layer.linear1.weight.shape
+    H = int(math.sqrt(N))
+    if C != 256 or d_model != 256 or d_ff % 64 != 0 or d_ff > 1024 or H * H != N:
+        return False
+    if src.dtype not in (torch.float32, torch.bfloat16) or not ops.linear_wgrad_ok(B * N, 256, 256):
+        return False
+    return _deform_native_ok(layer.self_attn, src, src, reference_points)
 
 
 class DeformableAttention(nn.Module):
@@ -235,10 +332,32 @@ class TransformerEncoderLayer(nn.Module):
 
     def forward(self, src, pos, reference_points):
         """src (B, N, C); pos (B, C, H, W); reference_points (B, N, 2)."""
+        if _transformer_native_ok(self, src, pos, reference_points):
+            TRANSFORMER_CALLS["native"] += 1
+            return self._forward_native(src, pos, reference_points)
+        TRANSFORMER_CALLS["composition"] += 1
         q = src + pos.flatten(2).permute(0, 2, 1)
         src = self.norm1(src + self.dropout1(self.self_attn(q, src, reference_points)))
         ff = self.linear2(self.dropout(self.activation(self.linear1(src))))
         return self.norm2(src + self.dropout2(ff))
+
+    def _forward_native(self, src, pos, reference_points):
+        """`forward` on the native nodes (bf16 autocast): the same operations at the same rounding points, except that
+        [offsets | logits] and the projected value reach the sampling node in fp32 without a bf16 stop on the way."""
+        a = self.self_attn
+        H = W = int(math.sqrt(src.shape[1]))
+        q = src + pos.flatten(2).permute(0, 2, 1)
+        # sampling_offsets and attention_weights as ONE GEMM: the 192-wide [offsets | logits] the sampling node takes
+        w_ol = torch.cat([a.sampling_offsets.weight, a.attention_weights.weight], 0)
+        b_ol = torch.cat([a.sampling_offsets.bias, a.attention_weights.bias], 0)
+        ol = _LinearFn.apply(q, w_ol, b_ol, True)
+        val = _LinearFn.apply(src, a.value_proj.weight, a.value_proj.bias, True)
+        att = _DeformAttnFn.apply(val, ol, reference_points, H, W)
+        att = _LinearFn.apply(att, a.output_proj.weight, a.output_proj.bias)
+        x1 = _LayerNormFn.apply(src + self.dropout1(att), self.norm1.weight, self.norm1.bias, self.norm1.eps)
+        ff = _LinearFn.apply(x1, self.linear1.weight, self.linear1.bias)
+        ff = _LinearFn.apply(self.dropout(self.activation(ff)), self.linear2.weight, self.linear2.bias)
+        return _LayerNormFn.apply(x1 + self.dropout2(ff), self.norm2.weight, self.norm2.bias, self.norm2.eps)
 
 
 class LightweightBEVTransformer(nn.Module):
