@@ -700,7 +700,9 @@ typedef struct lss_conv_launch {
                      4 = lss_conv2d_ks_s2_dual_fwd (Cout: channels of EACH output), 5 = lss_conv2d_ks_stem_fwd */
   int32_t split;  /* kind 3 only */
 } lss_conv_launch_t;
-/* Enqueue `n` conv launches in order on `stream`; returns the first non-zero code. */
+/* Enqueue `n` conv launches in order on `stream`; returns the first non-zero code.  The descriptor is also the eager
+ * route: the Python conv wrappers run every single conv as a list of one, so a recorded launch and its replay are
+ * the same call on the same bytes. */
 int lss_conv2d_sequence(const lss_conv_launch_t* launches, int n, void* stream);
 
 /* Position-wise feed-forward block of the BEV transformer layer in one launch (the hidden activation never

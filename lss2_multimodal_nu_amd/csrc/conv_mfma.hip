@@ -1178,6 +1178,48 @@ void launch_conv_lds(const ConvArgs& a, hipStream_t st) {
   }
 }
 
+// LSS_CONV_WT=0: write-back epilogue stores.  Read on every call, like every switch here: tests flip them in-process
+inline bool conv_wt_from_env() {
+  const char* e = getenv("LSS_CONV_WT");
+  return e == nullptr || atoi(e) != 0;
+}
+
+// The one fill of ConvArgs: geometry, activation word (`act` = ACT_* | LSS_OUT_F32), write-through, align_corners
+// ratios.  An entry checks its own arguments, calls this, then sets what only it has.  rc: 0 or LSS_E_SHAPE (no
+// output pixel, or 2^31 and more of them).
+struct ConvFill {
+  int rc;
+  ConvArgs a;
+};
+ConvFill conv_args_fill(const void* x, const void* x2, const void* w, const float* scale, const float* shift,
+                        const void* residual, void* y, float* stats, int B, int H, int W, int Cx, int C2, int up,
+                        int Cout, int KH, int KW, int stride, int pad, int act) {
+  ConvFill f = {};  // zero: one output (y2, split), no fused head (head_*), no LDS source staging (src_lds)
+  f.rc = LSS_E_SHAPE;
+  ConvArgs& a = f.a;
+  a.stamps = conv_stamps_from_env();
+  a.x = x; a.x2 = x2; a.w = w; a.scale = scale; a.shift = shift; a.residual = residual;
+  a.y = y; a.stats = stats;
+  a.B = B; a.H = H; a.W = W; a.Cx = Cx; a.C2 = C2; a.up = up;
+  a.Hin = H * up; a.Win = W * up; a.Cin = Cx + C2;
+  a.Cout = Cout; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad;
+  a.Ho = (a.Hin + 2 * pad - KH) / stride + 1;
+  a.Wo = (a.Win + 2 * pad - KW) / stride + 1;
+  if (a.Ho <= 0 || a.Wo <= 0) return f;
+  const long long M = (long long)B * a.Ho * a.Wo;
+  if (M >= (1LL << 31)) return f;
+  a.M = (int)M;
+  a.relu = act & 3;
+  a.out_f32 = (act & LSS_OUT_F32) != 0;
+  a.wt = conv_wt_from_env() && (unsigned long long)a.M * a.Cout * 2 < (1ULL << 31);
+  a.relu_n = a.Cout;
+  // read by the fused-gather (MODE 1) code only; 1 where up == 1
+  a.ry = a.Hin > 1 ? (float)(H - 1) / (float)(a.Hin - 1) : 0.f;
+  a.rx = a.Win > 1 ? (float)(W - 1) / (float)(a.Win - 1) : 0.f;
+  f.rc = 0;
+  return f;
+}
+
 }  // namespace
 
 extern "C" size_t lss_conv2d_s2d_packed_weight_bytes(int Cout, int Cin, int K, int pad) {
@@ -1247,9 +1289,8 @@ extern "C" int lss_conv2d_fwd(const void* x, const void* x2, const void* w_packe
     if (dt != LSS_DT_BF16 || KH != 3 || KW != 3 || stride != 1 || pad != 1 || residual != nullptr || stats != nullptr ||
         (relu & ~(LSS_W_RING | 1)) != 0)
       return LSS_E_SHAPE;
-    const bool wt_ring = (getenv("LSS_CONV_WT") == nullptr || atoi(getenv("LSS_CONV_WT")) != 0);
     return lss_conv_ring_launch(x, x2, w_packed, scale, shift, y, nullptr, nullptr, nullptr, 0, B, H, W, Cx, C2, up, Cout,
-                                relu & 1, wt_ring ? 1 : 0, lss_stream(stream));
+                                relu & 1, conv_wt_from_env() ? 1 : 0, lss_stream(stream));
   }
   // K blocks never straddle the x2 | upsample(x) boundary.  A plain bf16 input may end in half a K block
   // (Cin % 64 == 32): the GEMM kernel of the 1x1 layers stages 32-channel slabs, and the direct kernel leaves the
@@ -1257,30 +1298,13 @@ extern "C" int lss_conv2d_fwd(const void* x, const void* x2, const void* w_packe
   const bool fused = (up > 1) || (C2 > 0);
   const int kblock = dt == LSS_DT_BF16 ? (fused ? 64 : 32) : 8;
   if (Cx % kblock != 0 || C2 % kblock != 0) return LSS_E_SHAPE;
-  ConvArgs a;
-  a.stamps = conv_stamps_from_env();
-  a.src_lds = 0;
-  a.x = x; a.x2 = x2; a.w = w_packed; a.scale = scale; a.shift = shift; a.residual = residual;
-  a.y = y; a.stats = stats;
-  a.B = B; a.H = H; a.W = W; a.Cx = Cx; a.C2 = C2; a.up = up;
-  a.Hin = H * up; a.Win = W * up; a.Cin = Cx + C2;
-  a.Cout = Cout; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad;
-  a.Ho = (a.Hin + 2 * pad - KH) / stride + 1;
-  a.Wo = (a.Win + 2 * pad - KW) / stride + 1;
-  if (a.Ho <= 0 || a.Wo <= 0) return LSS_E_SHAPE;
-  const long long M = (long long)B * a.Ho * a.Wo;
-  if (M >= (1LL << 31)) return LSS_E_SHAPE;
-  a.M = (int)M;
-  a.relu = relu & 3;
-  a.out_f32 = (relu & LSS_OUT_F32) != 0;
-  a.wt = (getenv("LSS_CONV_WT") == nullptr || atoi(getenv("LSS_CONV_WT")) != 0) &&
-         (unsigned long long)a.M * a.Cout * 2 < (1ULL << 31);
-  a.y2 = nullptr; a.split = 0; a.relu_n = a.Cout;
+  const ConvFill f = conv_args_fill(x, x2, w_packed, scale, shift, residual, y, stats, B, H, W, Cx, C2, up, Cout, KH, KW,
+                                    stride, pad, relu);
+  if (f.rc != 0) return f.rc;
+  const ConvArgs& a = f.a;
+  const long long M = a.M;
   const bool head_major = (relu & LSS_OUT_HEAD_MAJOR32) != 0;
   if (a.relu == 3 || (relu & ~(3 | LSS_OUT_F32 | LSS_OUT_HEAD_MAJOR32)) != 0) return LSS_E_LAYOUT;
-  a.head_w = nullptr; a.head_b = nullptr; a.head_out = nullptr; a.head_n = 0;
-  a.ry = a.Hin > 1 ? (float)(H - 1) / (float)(a.Hin - 1) : 0.f;
-  a.rx = a.Win > 1 ? (float)(W - 1) / (float)(a.Win - 1) : 0.f;
   dim3 grid(lss_cdiv(M, 128), lss_cdiv(Cout, 64));
   if (grid.y > 65535) return LSS_E_SHAPE;
   hipStream_t st = lss_stream(stream);
@@ -1327,29 +1351,14 @@ static int conv2d_s2_impl(const void* x, const void* w_s2d, const float* scale, 
   LSS_CHECK_POS(B); LSS_CHECK_POS(H); LSS_CHECK_POS(W); LSS_CHECK_POS(Cx); LSS_CHECK_POS(Cout);
   if (!((K == 3 && pad == 1) || (K == 7 && pad == 3) || (K == 1 && pad == 0))) return LSS_E_SHAPE;
   if (Cx % 64 != 0) return LSS_E_SHAPE;
-  ConvArgs a;
-  a.stamps = conv_stamps_from_env();
-  a.src_lds = 0;
-  a.x = x; a.x2 = nullptr; a.w = w_s2d; a.scale = scale; a.shift = shift; a.residual = residual;
-  a.y = y; a.stats = stats;
-  a.B = B; a.H = H; a.W = W; a.Cx = Cx; a.C2 = 0; a.up = 1;
-  // K = 1: only parity phase (0,0) is ever read, so the K loop runs over that phase alone
+  ConvFill f = conv_args_fill(x, nullptr, w_s2d, scale, shift, residual, y, stats, B, H, W, Cx, 0, 1, Cout, K, K, 2, pad,
+                              relu & 3);
+  if (f.rc != 0) return f.rc;
+  ConvArgs& a = f.a;
+  // the K loop runs over the four parity phases; K = 1 reads phase (0,0) only, so it runs over that phase alone
   // and the weights are the plain [1][Cout][Cx] pack
-  a.Hin = H; a.Win = W; a.Cin = K == 1 ? Cx : 4 * Cx;
-  a.Cout = Cout; a.KH = K; a.KW = K; a.stride = 2; a.pad = pad;
-  a.Ho = (H + 2 * pad - K) / 2 + 1;
-  a.Wo = (W + 2 * pad - K) / 2 + 1;
-  if (a.Ho <= 0 || a.Wo <= 0) return LSS_E_SHAPE;
-  const long long M = (long long)B * a.Ho * a.Wo;
-  if (M >= (1LL << 31)) return LSS_E_SHAPE;
-  a.M = (int)M;
-  a.relu = relu & 3;
-  a.out_f32 = 0;
-  a.wt = (getenv("LSS_CONV_WT") == nullptr || atoi(getenv("LSS_CONV_WT")) != 0) &&
-         (unsigned long long)a.M * a.Cout * 2 < (1ULL << 31);
+  a.Cin = K == 1 ? Cx : 4 * Cx;
   a.y2 = y2; a.split = split; a.relu_n = y2 ? relu_n : a.Cout;
-  a.head_w = nullptr; a.head_b = nullptr; a.head_out = nullptr; a.head_n = 0;
-  a.ry = a.rx = 0.f;
   hipStream_t st = lss_stream(stream);
   if (K == 7) launch_conv_lds<2, 4, 4, 2>(a, st);
   else if (K == 3) launch_conv_lds<2, 2, 2, 1>(a, st);
@@ -1400,26 +1409,11 @@ extern "C" int lss_conv2d_head_fwd(const void* x, const void* x2, const void* w_
   if ((Cout != 128 && Cout != 64) || C2 < 0 || Cx % 64 != 0 || C2 % 64 != 0 || head_n > 64) return LSS_E_SHAPE;
   if (Cout == 64 && (up != 1 || C2 != 0)) return LSS_E_SHAPE;  // the 64-wide tile has no fused-gather form
   if (C2 > 0 && x2 == nullptr) return LSS_E_NULL;
-  ConvArgs a;
-  a.stamps = conv_stamps_from_env();
-  a.src_lds = 0;
-  a.x = x; a.x2 = x2; a.w = w_packed; a.scale = scale; a.shift = shift; a.residual = nullptr;
-  a.y = nullptr; a.stats = nullptr;
-  a.B = B; a.H = H; a.W = W; a.Cx = Cx; a.C2 = C2; a.up = up;
-  a.Hin = H * up; a.Win = W * up; a.Cin = Cx + C2;
-  a.Cout = Cout; a.KH = 3; a.KW = 3; a.stride = 1; a.pad = 1;
-  a.Ho = a.Hin; a.Wo = a.Win;
-  const long long M = (long long)B * a.Ho * a.Wo;
-  if (M >= (1LL << 31)) return LSS_E_SHAPE;
-  a.M = (int)M;
-  a.relu = relu & 3;
-  a.out_f32 = 0;
-  a.wt = (getenv("LSS_CONV_WT") == nullptr || atoi(getenv("LSS_CONV_WT")) != 0) &&
-         (unsigned long long)a.M * a.Cout * 2 < (1ULL << 31);
-  a.y2 = nullptr; a.split = 0; a.relu_n = a.Cout;
+  ConvFill f = conv_args_fill(x, x2, w_packed, scale, shift, nullptr, nullptr, nullptr, B, H, W, Cx, C2, up, Cout, 3, 3, 1,
+                              1, relu & 3);
+  if (f.rc != 0) return f.rc;
+  ConvArgs& a = f.a;
   a.head_w = head_w; a.head_b = head_b; a.head_out = out; a.head_n = head_n;
-  a.ry = a.Hin > 1 ? (float)(H - 1) / (float)(a.Hin - 1) : 0.f;
-  a.rx = a.Win > 1 ? (float)(W - 1) / (float)(a.Win - 1) : 0.f;
   const bool fused = (up > 1) || (C2 > 0);
   const int tilesX = lss_cdiv(a.Wo, 16), tilesY = lss_cdiv(a.Ho, Cout == 64 ? 16 : 8);
   dim3 g(tilesX * tilesY * B, 1);

@@ -559,18 +559,25 @@ class _FoldedConv:
         self.pad_in = pad_in
         self.key = None
         self.w = self.scale = self.shift = None
-        self.w_ring, self.ring_key = None, None
-        self.w_ks, self.ks_key = None, None
-        self.w_stem, self.stem_key = None, None
+        self._images = {}  # layout name -> (key it was packed for, weight image)
 
-    def stem(self, dt):
-        """The 7x7 weights in the layout of the K-split kernel's stem mode, cached under the key of the s2d pack (which
-        the fallback keeps); `get(dt)` must have been called for the current key."""
-        if self.stem_key != self.key:
+    def _w32(self):
+        """The conv's weight as contiguous OIHW fp32, with the `pad_in` zero input channels in place."""
+        w32 = self.conv.weight.detach().float().contiguous()
+        if self.pad_in is not None:
+            at, n = self.pad_in
+            w32 = torch.cat([w32[:, :at], w32.new_zeros(w32.shape[0], n, *w32.shape[2:]), w32[:, at:]], 1).contiguous()
+        return w32
+
+    def image(self, layout, pack_fn):
+        """The same weights in another kernel's layout ("ring": csrc/conv_ring.hip; "ks", "stem": csrc/conv_ks.hip),
+        packed with `pack_fn` on first use and whenever a source tensor changes; `get(dt)` must have been called for
+        the current key (the image is cached under it, next to the pack `get` made, which the fallbacks keep)."""
+        hit = self._images.get(layout)
+        if hit is None or hit[0] != self.key:
             with torch.no_grad():
-                self.w_stem = ops.pack_conv_weight_ks_stem(self.conv.weight.detach().float().contiguous())
-            self.stem_key = self.key
-        return self.w_stem
+                hit = self._images[layout] = (self.key, pack_fn(self._w32()))
+        return hit[1]
 
     def stem_case(self, x, dt, residual=None, x2=None, up=1):
         """Does this call go to the stem mode of the K-split one-pass kernel?  7x7 / stride 2 / pad 3, bf16, nothing fused,
@@ -583,15 +590,6 @@ class _FoldedConv:
         B, H, W, Cx = x.shape
         return ops.conv_ks_stem_ok(B, H, W, Cx, c.out_channels)
 
-    def ks(self, dt):
-        """The same weights in the K-split one-pass kernel's layout (csrc/conv_ks.hip), packed on first use and
-        whenever a source tensor changes; `get(dt)` must have been called for the current key."""
-        if self.ks_key != self.key:
-            with torch.no_grad():
-                self.w_ks = ops.pack_conv_weight_ks(self.conv.weight.detach().float().contiguous())
-            self.ks_key = self.key
-        return self.w_ks
-
     def ks_case(self, x, dt, x2=None, up=1):
         """Does this call go to the K-split one-pass kernel?  3x3 / stride 1 / pad 1, bf16, no fused gather, and a shape
         `lss_conv2d_ks_ok` accepts (layer1-3 of BevEncode at the benchmark sizes)."""
@@ -601,20 +599,6 @@ class _FoldedConv:
             return False
         B, H, W, Cx = x.shape
         return ops.conv_ks_ok(B, H, W, Cx, c.out_channels)
-
-    def ring(self, dt):
-        """The same weights in the ring kernel's layout (csrc/conv_ring.hip), packed on first use and whenever a
-        source tensor changes; `get(dt)` must have been called for the current key."""
-        if self.ring_key != self.key:
-            with torch.no_grad():
-                w32 = self.conv.weight.detach().float().contiguous()
-                if self.pad_in is not None:
-                    at, n = self.pad_in
-                    w32 = torch.cat([w32[:, :at], w32.new_zeros(w32.shape[0], n, *w32.shape[2:]), w32[:, at:]],
-                                    1).contiguous()
-                self.w_ring = ops.pack_conv_weight_ring(w32)
-            self.ring_key = self.key
-        return self.w_ring
 
     def ring_case(self, x, dt, residual=None, x2=None, up=1, head_n=0):
         """Does this call go to the loader / consumer ring kernel?  3x3 / stride 1 / pad 1, bf16, no residual, and a
@@ -648,11 +632,7 @@ class _FoldedConv:
         key = self._key(dt)
         if key != self.key:
             with torch.no_grad():
-                w32 = self.conv.weight.detach().float().contiguous()
-                if self.pad_in is not None:
-                    at, n = self.pad_in
-                    w32 = torch.cat([w32[:, :at], w32.new_zeros(w32.shape[0], n, *w32.shape[2:]), w32[:, at:]],
-                                    1).contiguous()
+                w32 = self._w32()
                 # (the 1x1/2 conv reads parity phase (0,0) only: plain pack)
                 if not self.pack:
                     self.w = None
@@ -677,13 +657,13 @@ class _FoldedConv:
         w, scale, shift = self.get(dt)
         c = self.conv
         if relu in (False, True) and self.stem_case(x, dt, residual, x2, up):   # one pass, K = 49 Cin (csrc/conv_ks.hip)
-            return ops.conv2d_ks_stem_nhwc(x, self.stem(dt), scale, shift, relu=relu)
+            return ops.conv2d_ks_stem_nhwc(x, self.image("stem", ops.pack_conv_weight_ks_stem), scale, shift, relu=relu)
         if self._s2d(dt) and x2 is None and up == 1:
             return ops.conv2d_s2_nhwc(x, w, c.kernel_size[0], c.padding[0], scale, shift, residual, relu)
         if relu in (False, True) and self.ks_case(x, dt, x2, up):
-            w = self.ks(dt)
+            w = self.image("ks", ops.pack_conv_weight_ks)
         elif relu in (False, True) and self.ring_case(x, dt, residual, x2, up):
-            w = self.ring(dt)
+            w = self.image("ring", ops.pack_conv_weight_ring)
         return ops.conv2d_nhwc(x, w, c.kernel_size, c.stride[0], c.padding[0], scale, shift, residual, relu,
                                x2=x2, up=up, dt=dt)
 
@@ -1064,7 +1044,7 @@ class BevEncode(nn.Module):
             w, scale, shift = self._up2a.get(dt)
             head = self.up2[4]
             if self._up2a.ring_case(x, dt, up=2, head_n=head.out_channels):
-                w = self._up2a.ring(dt)
+                w = self._up2a.image("ring", ops.pack_conv_weight_ring)
             hw = head.weight.detach().float().reshape(head.out_channels, -1).contiguous()
             return ops.conv3x3_head_nchw(x, w, scale, shift, hw, head.bias.detach().float().contiguous(), up=2)
         x = self._up2a.run(x, dt, relu=True, up=2)

@@ -110,16 +110,16 @@ def guard_every():
 
 
 class ConvRecorder:
-    """Collects the conv launches of one eager pass (pointers + shapes) together with the
+    """Collects the conv launches of one eager pass (the descriptors `_conv_launch` ran) together with the
     tensors that must outlive them; `ConvPlan` replays the list with ONE native call."""
 
     def __init__(self):
-        self.launches = []
+        self.launches = []  # (kind, N.ConvLaunch)
         self.keep = []
 
-    def add(self, kind, keep, **f):
-        self.launches.append((kind, f))
-        self.keep.extend(t for t in keep if t is not None)
+    def add(self, launch, keep):
+        self.launches.append((launch.kind, launch))
+        self.keep.extend(keep)
 
 
 _recorder = None
@@ -138,11 +138,9 @@ class ConvPlan:
         self.keep = rec.keep
         self.in_slots, self.out_slots = [], []
         pin, pout = x_in.data_ptr(), out.data_ptr()
-        for i, (kind, f) in enumerate(rec.launches):
+        for i, (_, launch) in enumerate(rec.launches):
+            self.arr[i] = launch  # a copy: `run` patches the plan's own descriptors
             c = self.arr[i]
-            c.kind = kind
-            for k, v in f.items():
-                setattr(c, k, v.data_ptr() if isinstance(v, torch.Tensor) else (v if v is not None else None))
             for name in ("x", "x2", "residual"):
                 if getattr(c, name) == pin:
                     self.in_slots.append((i, name))
@@ -159,7 +157,6 @@ class ConvPlan:
         for i, name in self.out_slots:
             setattr(self.arr[i], name, pout)
         if _timer is not None and _timer.last_conv and self.n > 1:
-            import ctypes
             N.check(N.lib().lss_conv2d_sequence(self.arr, self.n - 1, N.stream()), "lss_conv2d_sequence")
             last = ctypes.byref(self.arr, (self.n - 1) * ctypes.sizeof(self.arr[0]))  # &arr[n - 1]
             with _timed("conv_plan_last", coarse=True):
@@ -811,6 +808,34 @@ def pack_conv_weight_ring_dgrad(w_oihw):
     return RingWeight(out, Cin, Cout)
 
 
+# kind of a lss_conv_launch_t -> the entry lss_conv2d_sequence hands it to (named in error messages)
+_CONV_ENTRIES = ("lss_conv2d_fwd", "lss_conv2d_s2_fwd", "lss_conv2d_head_fwd", "lss_conv2d_s2_dual_fwd",
+                 "lss_conv2d_ks_s2_dual_fwd", "lss_conv2d_ks_stem_fwd")
+
+
+def _conv_launch(kind, tag, tensors, dt=DT_BF16, **fields):
+    """The one route from a conv wrapper to its kernel: one lss_conv_launch_t of `kind` from the pointer fields
+    `tensors` (name -> GPU tensor or None) and the integer `fields`, handed to the recorder when one is set and run
+    through lss_conv2d_sequence - the call a ConvPlan replays it with."""
+    for name, t in tensors.items():
+        if t is not None:
+            if not t.is_cuda:
+                raise N.LssNativeError("%s: expected a GPU tensor, got %s" % (name, t.device))
+            fields[name] = t.data_ptr()
+    c = N.ConvLaunch(kind=kind, dt=dt, **fields)
+    if _recorder is not None:
+        _recorder.add(c, [t for t in tensors.values() if t is not None])
+    with _timed(tag):
+        N.check(N.lib().lss_conv2d_sequence(ctypes.byref(c), 1, N.stream()), _CONV_ENTRIES[kind])
+
+
+def _check_per_channel(n, **operands):
+    """The optional per-channel fp32 operands of a conv epilogue: scale / shift (n = Cout), stats (n = 2 Cout)."""
+    for name, t in operands.items():
+        if t is not None:
+            _f32c(t, name, (n,))
+
+
 def conv2d_nhwc(x, w_packed, ksize, stride, pad, scale=None, shift=None, residual=None, relu=False,
                 x2=None, up=1, stats=None, dt=DT_BF16, tag="conv2d_fwd", out_f32=False, head_major=False):
     """K8.  x (B,H,W,Cx) NHWC in `dt`; x2 (B,H*up,W*up,C2) optional skip tensor
@@ -838,22 +863,14 @@ def conv2d_nhwc(x, w_packed, ksize, stride, pad, scale=None, shift=None, residua
     Ho = (H * up + 2 * pad - KH) // stride + 1
     Wo = (W * up + 2 * pad - KW) // stride + 1
     y = torch.empty(B, Ho, Wo, Cout, dtype=torch.float32 if out_f32 else tdt, device=x.device)
-    for name, t in (("scale", scale), ("shift", shift)):
-        if t is not None:
-            _f32c(t, name, (Cout,))
+    _check_per_channel(Cout, scale=scale, shift=shift)
+    _check_per_channel(2 * Cout, stats=stats)
     if residual is not None and (residual.dtype != tdt or tuple(residual.shape) != (B, Ho, Wo, Cout)
                                  or not residual.is_contiguous()):
         raise ValueError("residual must match the output")
-    if stats is not None:
-        _f32c(stats, "stats", (2 * Cout,))
-    if _recorder is not None:
-        _recorder.add(0, (x, x2, w_packed, scale, shift, residual, y, stats), x=x, x2=x2, w=w_packed, scale=scale,
-                      shift=shift, residual=residual, y=y, stats=stats, B=B, H=H, W=W, Cx=Cx, C2=C2, up=up, Cout=Cout,
-                      KH=KH, KW=KW, stride=stride, pad=pad, relu=act, dt=dt)
-    with _timed(tag):
-        N.check(N.lib().lss_conv2d_fwd(N.ptr(x), N.ptr(x2), N.ptr(w_packed), N.ptr(scale), N.ptr(shift),
-                                       N.ptr(residual), N.ptr(y), N.ptr(stats), B, H, W, Cx, C2, up, Cout,
-                                       KH, KW, stride, pad, act, dt, N.stream()), "lss_conv2d_fwd")
+    _conv_launch(0, tag, {"x": x, "x2": x2, "w": w_packed, "scale": scale, "shift": shift, "residual": residual, "y": y,
+                          "stats": stats},
+                 B=B, H=H, W=W, Cx=Cx, C2=C2, up=up, Cout=Cout, KH=KH, KW=KW, stride=stride, pad=pad, relu=act, dt=dt)
     return y.view(B, Cout // 32, Ho * Wo, 32) if head_major else y
 
 
@@ -1534,22 +1551,14 @@ def conv2d_s2_nhwc(x, w_s2d, K, pad, scale=None, shift=None, residual=None, relu
         raise ValueError("conv2d_s2_nhwc operands must be contiguous bf16 with s2d-packed weights")
     Ho, Wo = (H + 2 * pad - K) // 2 + 1, (W + 2 * pad - K) // 2 + 1
     y = torch.empty(B, Ho, Wo, Cout, dtype=torch.bfloat16, device=x.device)
-    for name, t in (("scale", scale), ("shift", shift)):
-        if t is not None:
-            _f32c(t, name, (Cout,))
+    _check_per_channel(Cout, scale=scale, shift=shift)
+    _check_per_channel(2 * Cout, stats=stats)
     if residual is not None and (residual.dtype != torch.bfloat16 or tuple(residual.shape) != tuple(y.shape)
                                  or not residual.is_contiguous()):
         raise ValueError("residual must match the output")
-    if stats is not None:
-        _f32c(stats, "stats", (2 * Cout,))
-    if _recorder is not None:
-        _recorder.add(1, (x, w_s2d, scale, shift, residual, y, stats), x=x, w=w_s2d, scale=scale, shift=shift,
-                      residual=residual, y=y, stats=stats, B=B, H=H, W=W, Cx=Cx, Cout=Cout, KH=K, KW=K, stride=2,
-                      pad=pad, relu=1 if relu else 0, dt=DT_BF16)
-    with _timed(tag):
-        N.check(N.lib().lss_conv2d_s2_fwd(N.ptr(x), N.ptr(w_s2d), N.ptr(scale), N.ptr(shift), N.ptr(residual),
-                                          N.ptr(y), N.ptr(stats), B, H, W, Cx, Cout, K, pad, 1 if relu else 0,
-                                          N.stream()), "lss_conv2d_s2_fwd")
+    _conv_launch(1, tag, {"x": x, "w": w_s2d, "scale": scale, "shift": shift, "residual": residual, "y": y,
+                          "stats": stats},
+                 B=B, H=H, W=W, Cx=Cx, Cout=Cout, KH=K, KW=K, stride=2, pad=pad, relu=1 if relu else 0)
     return y
 
 
@@ -1565,14 +1574,8 @@ def conv2d_s2_dual_nhwc(x, w_s2d, scale, shift, split, relu=True, tag="conv2d_fw
     Ho, Wo = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
     y = torch.empty(B, Ho, Wo, split, dtype=torch.bfloat16, device=x.device)
     y2 = torch.empty(B, Ho, Wo, Cout - split, dtype=torch.bfloat16, device=x.device)
-    if _recorder is not None:
-        _recorder.add(3, (x, w_s2d, scale, shift, y, y2), x=x, w=w_s2d, scale=scale, shift=shift, y=y, y2=y2, B=B, H=H,
-                      W=W, Cx=Cx, Cout=Cout, KH=3, KW=3, stride=2, pad=1, relu=1 if relu else 0, dt=DT_BF16,
-                      split=split)
-    with _timed(tag):
-        N.check(N.lib().lss_conv2d_s2_dual_fwd(N.ptr(x), N.ptr(w_s2d), N.ptr(scale), N.ptr(shift), N.ptr(y), N.ptr(y2),
-                                               B, H, W, Cx, Cout, split, 3, 1, 1 if relu else 0, N.stream()),
-                "lss_conv2d_s2_dual_fwd")
+    _conv_launch(3, tag, {"x": x, "w": w_s2d, "scale": scale, "shift": shift, "y": y, "y2": y2},
+                 B=B, H=H, W=W, Cx=Cx, Cout=Cout, KH=3, KW=3, stride=2, pad=1, relu=1 if relu else 0, split=split)
     return y, y2
 
 
@@ -1606,19 +1609,12 @@ def conv2d_ks_s2_dual_nhwc(x, w_ks, scale=None, shift=None, relu=True, tag="conv
             or w_ks.data.numel() != w_ks.Cout * Cx * 10:
         raise ValueError("conv2d_ks_s2_dual_nhwc operands must be contiguous bf16 with stride-2 KS-packed weights")
     Cout = w_ks.Cout
-    for name, t in (("scale", scale), ("shift", shift)):
-        if t is not None:
-            _f32c(t, name, (2 * Cout,))
+    _check_per_channel(2 * Cout, scale=scale, shift=shift)
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     y = torch.empty(B, Ho, Wo, Cout, dtype=torch.bfloat16, device=x.device)
     y2 = torch.empty(B, Ho, Wo, Cout, dtype=torch.bfloat16, device=x.device)
-    if _recorder is not None:
-        _recorder.add(4, (x, w_ks.data, scale, shift, y, y2), x=x, w=w_ks.data, scale=scale, shift=shift, y=y, y2=y2,
-                      B=B, H=H, W=W, Cx=Cx, Cout=Cout, KH=3, KW=3, stride=2, pad=1, relu=1 if relu else 0, dt=DT_BF16)
-    with _timed(tag):
-        N.check(N.lib().lss_conv2d_ks_s2_dual_fwd(N.ptr(x), N.ptr(w_ks.data), N.ptr(scale), N.ptr(shift), N.ptr(y),
-                                                  N.ptr(y2), B, H, W, Cx, Cout, 1 if relu else 0, N.stream()),
-                "lss_conv2d_ks_s2_dual_fwd")
+    _conv_launch(4, tag, {"x": x, "w": w_ks.data, "scale": scale, "shift": shift, "y": y, "y2": y2},
+                 B=B, H=H, W=W, Cx=Cx, Cout=Cout, KH=3, KW=3, stride=2, pad=1, relu=1 if relu else 0)
     return y, y2
 
 
@@ -1649,18 +1645,11 @@ def conv2d_ks_stem_nhwc(x, w_ks, scale=None, shift=None, relu=True, tag="conv2d_
             or w_ks.data.numel() != w_ks.Cout * Cx * 49:
         raise ValueError("conv2d_ks_stem_nhwc operands must be contiguous bf16 with stem KS-packed weights")
     Cout = w_ks.Cout
-    for name, t in (("scale", scale), ("shift", shift)):
-        if t is not None:
-            _f32c(t, name, (Cout,))
+    _check_per_channel(Cout, scale=scale, shift=shift)
     Ho, Wo = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     y = torch.empty(B, Ho, Wo, Cout, dtype=torch.bfloat16, device=x.device)
-    if _recorder is not None:
-        _recorder.add(5, (x, w_ks.data, scale, shift, y), x=x, w=w_ks.data, scale=scale, shift=shift, y=y,
-                      B=B, H=H, W=W, Cx=Cx, Cout=Cout, KH=7, KW=7, stride=2, pad=3, relu=1 if relu else 0, dt=DT_BF16)
-    with _timed(tag):
-        N.check(N.lib().lss_conv2d_ks_stem_fwd(N.ptr(x), N.ptr(w_ks.data), N.ptr(scale), N.ptr(shift), N.ptr(y),
-                                               B, H, W, Cx, Cout, 1 if relu else 0, N.stream()),
-                "lss_conv2d_ks_stem_fwd")
+    _conv_launch(5, tag, {"x": x, "w": w_ks.data, "scale": scale, "shift": shift, "y": y},
+                 B=B, H=H, W=W, Cx=Cx, Cout=Cout, KH=7, KW=7, stride=2, pad=3, relu=1 if relu else 0)
     return y
 
 
@@ -1685,16 +1674,10 @@ def conv3x3_head_nchw(x, w_packed, scale, shift, head_w, head_b, x2=None, up=1, 
     _f32c(scale, "scale", (Cout,))
     _f32c(shift, "shift", (Cout,))
     out = torch.empty(B, n, H * up, W * up, dtype=torch.float32, device=x.device)
-    if _recorder is not None:
-        _recorder.add(2, (x, x2, w_packed, scale, shift, head_w, head_b, out), x=x, x2=x2, w=w_packed, scale=scale,
-                      shift=shift, head_w=head_w, head_b=head_b, head_out=out, B=B, H=H, W=W, Cx=Cx, C2=C2, up=up,
-                      Cout=Cout, KH=3, KW=3, stride=1, pad=1, relu=(1 if relu else 0) | (W_RING if ring else 0),
-                      dt=DT_BF16, head_n=n)
-    with _timed(tag):
-        N.check(N.lib().lss_conv2d_head_fwd(N.ptr(x), N.ptr(x2), N.ptr(w_packed), N.ptr(scale), N.ptr(shift),
-                                            N.ptr(head_w), N.ptr(head_b), N.ptr(out), B, H, W, Cx, C2, up, Cout, n,
-                                            (1 if relu else 0) | (W_RING if ring else 0), N.stream()),
-                "lss_conv2d_head_fwd")
+    _conv_launch(2, tag, {"x": x, "x2": x2, "w": w_packed, "scale": scale, "shift": shift, "head_w": head_w,
+                          "head_b": head_b, "head_out": out},
+                 B=B, H=H, W=W, Cx=Cx, C2=C2, up=up, Cout=Cout, KH=3, KW=3, stride=1, pad=1,
+                 relu=(1 if relu else 0) | (W_RING if ring else 0), head_n=n)
     return out
 
 
