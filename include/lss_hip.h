@@ -349,6 +349,49 @@ int lss_layernorm_bwd(const void* x, int x_dt, const void* dy, int dy_dt, const 
                       float* dbeta, void* stream);
 
 /* ---------------------------------------------------------------------------
+ * K12  the pointwise remainder of the BEV transformer's training step (csrc/transformer_pointwise.hip): four streaming
+ * kernels, 16-B accesses, capped grids, no atomics.
+ * replaces: src/transformer_modules.py:207-208, 211-213 (dropout1 + residual add + norm1; GELU + dropout on the hidden;
+ *           dropout2 + residual add + norm2) and the autograd nodes `loss.backward()` runs for them.
+ *
+ * The dropout mask is never stored: both directions recompute it (csrc/dropout_philox.h is the definition).
+ *   seed   int64[2] ON THE DEVICE = {key, stream}, read as unsigned, 8-B aligned; NULL = no dropout.
+ *   mask   element e (linear index of the contiguous tensor) belongs to Philox4x32-10 call q = e >> 3 with key
+ *          (lo32 key, hi32 key) and counter (q, 0, lo32 stream, hi32 stream); w = out[(e & 7) >> 1],
+ *          piece = (e & 1) ? w >> 16 : w & 0xffff; keep <=> piece >= thr.  m = keep ? scale : 0.
+ *   thr    round(p * 65536) in 0 .. 65535 (0 = identity; anything else is LSS_E_SHAPE); the caller passes
+ *          scale = 1 / (1 - thr / 65536).  m is applied as a multiply: a non-finite value under a dropped element
+ *          stays non-finite, as with torch's mask multiply.
+ *
+ * lss_gelu_dropout_fwd: y = bf16(gelu(h) m), h, y bf16 [n]; exact-erf GELU in fp32 (erf by A&S 7.1.26, 1.5e-7).
+ * lss_gelu_dropout_bwd: dh = bf16(dy m (Phi(h) + h phi(h))) in fp32; finite for every finite bf16 h.
+ *   lss_gelu_dropout_ok: 1 for n % 8 == 0, 8 <= n <= 2^32; else LSS_E_SHAPE.  The output must not be an input
+ *   (LSS_E_LAYOUT).  16-B alignment (LSS_E_ALIGN).
+ * lss_add_dropout_ln_fwd: s = res + a m (one fp32 multiply, one add), y = LayerNorm(s) with the arithmetic of
+ *   lss_layernorm_fwd.  res in res_dt, a in a_dt (LSS_DT_F32 | LSS_DT_BF16), s and y fp32, all (rows, C);
+ *   e = row * 256 + c.
+ * lss_add_dropout_ln_bwd: lss_layernorm_bwd on s - the same formula, the same partials in `workspace`
+ *   (>= lss_add_dropout_ln_bwd_workspace_bytes(rows) bytes), the same fixed-order second stage - with ds fp32 (the
+ *   gradient of res) and a second output da = ds m in da_dt.
+ *   lss_add_dropout_ln_ok: 1 for C == 256, 1 <= rows <= 2^22; else LSS_E_SHAPE.  Also LSS_E_NULL (every pointer but
+ *   seed is required), LSS_E_LAYOUT (dtype), LSS_E_ALIGN (16 B; 8 B for seed; 4 B for dgamma, dbeta), LSS_E_WORKSPACE.
+ * All checks run before any HIP call; nothing is written when one fails. */
+int lss_gelu_dropout_ok(long long n);
+int lss_gelu_dropout_fwd(const void* h, long long n, int thr, float scale, const long long* seed, void* y,
+                         void* stream);
+int lss_gelu_dropout_bwd(const void* h, const void* dy, long long n, int thr, float scale, const long long* seed,
+                         void* dh, void* stream);
+int lss_add_dropout_ln_ok(long long rows, int C);
+size_t lss_add_dropout_ln_bwd_workspace_bytes(long long rows);
+int lss_add_dropout_ln_fwd(const void* res, int res_dt, const void* a, int a_dt, long long rows, int C, int thr,
+                           float scale, const long long* seed, const float* gamma, const float* beta, float eps,
+                           float* s, float* y, void* stream);
+int lss_add_dropout_ln_bwd(const float* s, const void* dy, int dy_dt, const float* gamma, long long rows, int C,
+                           float eps, int thr, float scale, const long long* seed, void* workspace,
+                           size_t workspace_bytes, float* ds, void* da, int da_dt, float* dgamma, float* dbeta,
+                           void* stream);
+
+/* ---------------------------------------------------------------------------
  * K8  BevEncode convolutions: implicit-GEMM on MFMA, NHWC activations.
  * replaces: the conv2d / batch_norm / relu / add / interpolate / cat ATen ops of
  *           src/modules.py:22-27, 118-130 (and torchvision BasicBlock.forward).

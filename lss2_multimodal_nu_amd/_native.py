@@ -47,6 +47,15 @@ SIGNATURES = {
     "lss_layernorm_bwd_workspace_bytes": (_sz, [ctypes.c_longlong]),
     "lss_layernorm_bwd": (_i, [_vp, _i, _vp, _i, _vp, ctypes.c_longlong, _i, ctypes.c_float, _vp, _sz, _vp, _i, _vp, _vp,
                                _vp]),
+    "lss_gelu_dropout_ok": (_i, [ctypes.c_longlong]),
+    "lss_gelu_dropout_fwd": (_i, [_vp, ctypes.c_longlong, _i, ctypes.c_float, _vp, _vp, _vp]),
+    "lss_gelu_dropout_bwd": (_i, [_vp, _vp, ctypes.c_longlong, _i, ctypes.c_float, _vp, _vp, _vp]),
+    "lss_add_dropout_ln_ok": (_i, [ctypes.c_longlong, _i]),
+    "lss_add_dropout_ln_bwd_workspace_bytes": (_sz, [ctypes.c_longlong]),
+    "lss_add_dropout_ln_fwd": (_i, [_vp, _i, _vp, _i, ctypes.c_longlong, _i, _i, ctypes.c_float, _vp, _vp, _vp,
+                                    ctypes.c_float, _vp, _vp, _vp]),
+    "lss_add_dropout_ln_bwd": (_i, [_vp, _vp, _i, _vp, ctypes.c_longlong, _i, ctypes.c_float, _i, ctypes.c_float, _vp,
+                                    _vp, _sz, _vp, _vp, _i, _vp, _vp, _vp]),
     "lss_linear_res_ln_fwd": (_i, [_vp] * 4 + [ctypes.c_longlong, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
     "lss_ffn_fused_fwd": (_i, [_vp] * 5 + [ctypes.c_longlong, _i, _i, _vp, _vp, _vp, ctypes.c_float, _vp, _vp]),
     "lss_lift_splat_fwd": (_i, [_vp] * 3 + [_i] * 9 + [_vp, _i, _vp]),

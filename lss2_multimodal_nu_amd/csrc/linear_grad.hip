@@ -33,6 +33,7 @@
 //   Row ranges: groups = min(ceil(rows / 4), 1024), rows per group = ceil(rows / groups).
 #include <algorithm>
 
+#include "layernorm_bwd_row.h"  // the LayerNorm backward's row arithmetic, lg_sum_splits, ln_split, lg_aligned
 #include "lss_common.h"
 
 namespace {
@@ -42,8 +43,6 @@ constexpr int LG_BLK = 32 * 128;      // 4096 B: 32 tokens x 64 channels
 constexpr int LG_OPER = 4 * LG_BLK;   // one operand of a stage
 constexpr int LG_BUF = 2 * LG_OPER;   // dy then x
 constexpr int LG_MAXWG = 512;         // two workgroups per CU
-constexpr int LN_C = 256;
-constexpr int LN_MAXGROUPS = 1024;
 
 struct LinWgradArgs {
   const unsigned short* x;   // (T, K) bf16
@@ -204,20 +203,6 @@ __global__ __launch_bounds__(256) void linear_wgrad_kernel(const LinWgradArgs a)
   }
 }
 
-// x[i] = the S partials of element i added in split order (four interleaved chains, fixed final tree)
-__device__ __forceinline__ float lg_sum_splits(const float* __restrict__ p, int S, size_t stride) {
-  float s[4] = {0.f, 0.f, 0.f, 0.f};
-  int k = 0;
-  for (; k + 4 <= S; k += 4) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) s[i] += p[(size_t)(k + i) * stride];
-  }
-#pragma unroll
-  for (int i = 0; i < 3; ++i)
-    if (k + i < S) s[i] += p[(size_t)(k + i) * stride];
-  return (s[0] + s[1]) + (s[2] + s[3]);
-}
-
 __global__ __launch_bounds__(256) void linear_wgrad_reduce_kernel(const float* __restrict__ part,
                                                                   const float* __restrict__ dbp, int S, int NK, int N,
                                                                   float* __restrict__ dw, float* __restrict__ db) {
@@ -241,26 +226,6 @@ inline LinSplit lin_split(int T, int N, int K) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ f32x4 ln_load4(const T* p);
-template <>
-__device__ __forceinline__ f32x4 ln_load4<float>(const float* p) {
-  return *reinterpret_cast<const f32x4*>(p);
-}
-template <>
-__device__ __forceinline__ f32x4 ln_load4<unsigned short>(const unsigned short* p) {
-  const uint2 v = *reinterpret_cast<const uint2*>(p);
-  return (f32x4){lss_bf2f((unsigned short)(v.x & 0xffff)), lss_bf2f((unsigned short)(v.x >> 16)),
-                 lss_bf2f((unsigned short)(v.y & 0xffff)), lss_bf2f((unsigned short)(v.y >> 16))};
-}
-__device__ __forceinline__ void ln_store4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-__device__ __forceinline__ void ln_store4(unsigned short* p, f32x4 v) {
-  uint2 o;
-  o.x = lss_pack_bf2(v[0], v[1]);
-  o.y = lss_pack_bf2(v[2], v[3]);
-  *reinterpret_cast<uint2*>(p) = o;
-}
-
 template <typename TX, typename TG, typename TO>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const TX* __restrict__ x, const TG* __restrict__ dy,
                                                             const float* __restrict__ gamma, long long rows,
@@ -271,64 +236,13 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const TX* __restrict
   const long long r0 = (long long)blockIdx.x * rpg, r1 = min(rows, r0 + rpg);
   const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + 4 * lane);
   f32x4 dg = (f32x4){0.f, 0.f, 0.f, 0.f}, dbt = (f32x4){0.f, 0.f, 0.f, 0.f};
-  for (long long row = r0 + wave; row < r1; row += 4) {  // whole waves: the shuffles below see all 64 lanes
+  for (long long row = r0 + wave; row < r1; row += 4) {  // whole waves: the shuffles of ln_bwd_row see all 64 lanes
     const f32x4 v = ln_load4<TX>(x + row * LN_C + 4 * lane);
     const f32x4 gr = ln_load4<TG>(dy + row * LN_C + 4 * lane);
-    // mean and 1 / sigma exactly as layernorm_kernel computes them
-    const float mean = lss_wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.f / LN_C);
-    const f32x4 d = (f32x4){v[0] - mean, v[1] - mean, v[2] - mean, v[3] - mean};
-    const float var = lss_wave_sum(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3]) * (1.f / LN_C);
-    const float inv = rsqrtf(var + eps);
-    const f32x4 xh = (f32x4){d[0] * inv, d[1] * inv, d[2] * inv, d[3] * inv};
-    const f32x4 ag = (f32x4){gr[0] * gm[0], gr[1] * gm[1], gr[2] * gm[2], gr[3] * gm[3]};
-    const float m1 = lss_wave_sum(ag[0] + ag[1] + ag[2] + ag[3]) * (1.f / LN_C);
-    const float m2 = lss_wave_sum(ag[0] * xh[0] + ag[1] * xh[1] + ag[2] * xh[2] + ag[3] * xh[3]) * (1.f / LN_C);
-    ln_store4(dx + row * LN_C + 4 * lane,
-              (f32x4){(ag[0] - m1 - xh[0] * m2) * inv, (ag[1] - m1 - xh[1] * m2) * inv,
-                      (ag[2] - m1 - xh[2] * m2) * inv, (ag[3] - m1 - xh[3] * m2) * inv});
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      dg[i] += gr[i] * xh[i];
-      dbt[i] += gr[i];
-    }
+    ln_store4(dx + row * LN_C + 4 * lane, ln_bwd_row(v, gr, gm, eps, dg, dbt));
   }
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    red[wave][4 * lane + i] = dg[i];
-    red[wave][LN_C + 4 * lane + i] = dbt[i];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int m = 0; m < 2; ++m) {
-    const int e = tid + 256 * m;
-    part[(size_t)blockIdx.x * (2 * LN_C) + e] = ((red[0][e] + red[1][e]) + red[2][e]) + red[3][e];
-  }
+  ln_bwd_write_partial(red, dg, dbt, part);
 }
-
-// out[0 .. 255] = dgamma, out[256 .. 511] = dbeta: the groups' partials in group order
-__global__ __launch_bounds__(256) void layernorm_bwd_reduce_kernel(const float* __restrict__ part, int G,
-                                                                   float* __restrict__ dgamma,
-                                                                   float* __restrict__ dbeta) {
-  const int e = blockIdx.x * 256 + threadIdx.x;  // grid of 2
-  const float s = lg_sum_splits(part + e, G, (size_t)(2 * LN_C));
-  if (e < LN_C) dgamma[e] = s;
-  else dbeta[e - LN_C] = s;
-}
-
-struct LnSplit {
-  long long rpg;
-  int G;
-};
-
-inline LnSplit ln_split(long long rows) {
-  LnSplit sp;
-  const long long want = std::min<long long>((rows + 3) / 4, LN_MAXGROUPS);
-  sp.rpg = (rows + want - 1) / want;
-  sp.G = (int)((rows + sp.rpg - 1) / sp.rpg);
-  return sp;
-}
-
-inline bool lg_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 }  // namespace
 

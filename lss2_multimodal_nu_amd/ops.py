@@ -978,6 +978,140 @@ def layernorm_bwd(x, dy, gamma, eps, dx_dtype):
     return dx, dgb[0], dgb[1]
 
 
+def dropout_seed(device):
+    """The 16-byte seed {key, stream} of one dropout site of the K12 kernels: ONE draw of two full-range int64 on the
+    device from torch's generator of that device.  No host sync; reproducible after `torch.manual_seed`; a captured
+    graph draws a fresh seed at every replay."""
+    return torch.randint(-2 ** 63, 2 ** 63 - 1, (2,), dtype=torch.int64, device=device)
+
+
+def dropout_threshold(p):
+    """p -> (thr, scale) of the K12 mask (keep <=> 16-bit piece >= thr; thr = round(p * 65536), realised probability
+    thr / 65536, scale = 1 / (1 - thr / 65536) as fp32), or None when p has no threshold in 0 .. 65535 (p < 0, p so
+    close to 1 that everything would be dropped): such a p belongs to the torch composition."""
+    p = float(p)
+    if not 0.0 <= p < 1.0:
+        return None
+    thr = int(round(p * 65536.0))
+    if thr > 65535:
+        return None
+    return thr, 1.0 / (1.0 - thr / 65536.0)
+
+
+def _mask_args(p, seed, device):
+    """(thr, scale) of a K12 call; seed None = no dropout."""
+    if seed is None:
+        return 0, 1.0
+    ts = dropout_threshold(p)
+    if ts is None:
+        raise ValueError("dropout p = %r has no 16-bit threshold" % (p,))
+    if seed.dtype != torch.int64 or tuple(seed.shape) != (2,) or not seed.is_contiguous() or seed.device != device:
+        raise ValueError("seed must be a contiguous int64 tensor of shape (2,) on the inputs' device")
+    return ts
+
+
+def _gelu_dropout_check(h, dy=None):
+    for t, nm in ((h, "h"), (dy, "dy")):
+        if t is not None and (t.dtype != torch.bfloat16 or not t.is_contiguous()):
+            raise ValueError("%s must be a contiguous bf16 tensor, got %s" % (nm, t.dtype))
+    if dy is not None and tuple(dy.shape) != tuple(h.shape):
+        raise ValueError("dy %s does not match h %s" % (tuple(dy.shape), tuple(h.shape)))
+    if not N.lib().lss_gelu_dropout_ok(h.numel()):
+        raise ValueError("gelu_dropout needs a multiple of 8 elements, 8 <= n <= 2^32 (got %d)" % h.numel())
+    if not (h.is_cuda and (dy is None or dy.is_cuda)):
+        raise ValueError("h and dy must be GPU tensors")
+
+
+def gelu_dropout(h, p=0.0, seed=None):
+    """K12: dropout(gelu(h)) on the bf16 hidden in one pass (lss_gelu_dropout_fwd), exact-erf GELU in fp32.  The mask
+    comes from `seed` (`dropout_seed`) and is never stored; seed None = no dropout."""
+    thr, scale = _mask_args(p, seed, h.device)
+    _gelu_dropout_check(h)
+    y = torch.empty_like(h)
+    with _timed("gelu_dropout"):
+        N.check(N.lib().lss_gelu_dropout_fwd(N.ptr(h), h.numel(), thr, scale, N.ptr(seed), N.ptr(y), N.stream()),
+                "lss_gelu_dropout_fwd")
+    return y
+
+
+def gelu_dropout_bwd(h, dy, p=0.0, seed=None):
+    """K12: backward of `gelu_dropout` (lss_gelu_dropout_bwd): dh = dy * mask * gelu'(h), the mask recomputed."""
+    thr, scale = _mask_args(p, seed, h.device)
+    _gelu_dropout_check(h, dy)
+    dh = torch.empty_like(h)
+    with _timed("gelu_dropout_bwd"):
+        N.check(N.lib().lss_gelu_dropout_bwd(N.ptr(h), N.ptr(dy), h.numel(), thr, scale, N.ptr(seed), N.ptr(dh), N.stream()),
+                "lss_gelu_dropout_bwd")
+    return dh
+
+
+_PW_DT = {torch.float32: DT_F32, torch.bfloat16: DT_BF16}
+
+
+def _add_dropout_ln_rows(x, name):
+    if x.dim() < 1 or x.numel() == 0 or not N.lib().lss_add_dropout_ln_ok(x.numel() // x.shape[-1], x.shape[-1]):
+        raise ValueError("%s needs rows of 256, 1 <= rows <= 2^22 (got %s)" % (name, tuple(x.shape)))
+    return x.numel() // x.shape[-1]
+
+
+def add_dropout_layernorm(res, a, gamma, beta, eps, p=0.0, seed=None):
+    """K12: s = res + dropout(a), y = LayerNorm(s) in one pass (lss_add_dropout_ln_fwd).  res, a contiguous fp32 | bf16
+    rows of 256 of one shape -> (s, y), both fp32.  seed None = no dropout."""
+    for t, nm in ((res, "res"), (a, "a")):
+        if not t.is_contiguous() or t.dtype not in _PW_DT:
+            raise ValueError("%s must be contiguous fp32/bf16" % nm)
+    if tuple(a.shape) != tuple(res.shape):
+        raise ValueError("a %s does not match res %s" % (tuple(a.shape), tuple(res.shape)))
+    rows = _add_dropout_ln_rows(res, "add_dropout_layernorm")
+    C = res.shape[-1]
+    _f32c(gamma, "gamma", (C,))
+    _f32c(beta, "beta", (C,))
+    thr, scale = _mask_args(p, seed, res.device)
+    if not (res.is_cuda and a.is_cuda):
+        raise ValueError("res and a must be GPU tensors")
+    s = torch.empty(res.shape, dtype=torch.float32, device=res.device)
+    y = torch.empty_like(s)
+    with _timed("add_dropout_layernorm"):
+        N.check(N.lib().lss_add_dropout_ln_fwd(N.ptr(res), _PW_DT[res.dtype], N.ptr(a), _PW_DT[a.dtype], rows, C, thr,
+                                               scale, N.ptr(seed), N.ptr(gamma), N.ptr(beta), float(eps), N.ptr(s), N.ptr(y),
+                                               N.stream()), "lss_add_dropout_ln_fwd")
+    return s, y
+
+
+def add_dropout_layernorm_bwd(s, dy, gamma, eps, da_dtype, p=0.0, seed=None):
+    """K12: backward of `add_dropout_layernorm` (lss_add_dropout_ln_bwd).  s (the saved fp32 sum), dy fp32 | bf16 ->
+    (ds fp32 = the gradient of res, da = ds * mask in da_dtype, dgamma, dbeta fp32).  The workspace is cached per row
+    count and device, as `layernorm_bwd`'s."""
+    if not s.is_contiguous() or s.dtype != torch.float32:
+        raise ValueError("s must be contiguous fp32")
+    if not dy.is_contiguous() or dy.dtype not in _PW_DT:
+        raise ValueError("dy must be contiguous fp32/bf16")
+    if da_dtype not in _PW_DT:
+        raise ValueError("da_dtype must be fp32 or bf16")
+    if tuple(dy.shape) != tuple(s.shape):
+        raise ValueError("dy %s does not match s %s" % (tuple(dy.shape), tuple(s.shape)))
+    rows = _add_dropout_ln_rows(s, "add_dropout_layernorm_bwd")
+    C = s.shape[-1]
+    _f32c(gamma, "gamma", (C,))
+    thr, scale = _mask_args(p, seed, s.device)
+    if not (s.is_cuda and dy.is_cuda):
+        raise ValueError("s and dy must be GPU tensors")
+    nbytes = N.lib().lss_add_dropout_ln_bwd_workspace_bytes(rows)
+    key = ("add_dropout_ln", rows, str(s.device))
+    ws = _wgrad_ws.get(key)
+    if ws is None:
+        ws = _wgrad_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=s.device)
+    ds = torch.empty_like(s)
+    da = torch.empty(s.shape, dtype=da_dtype, device=s.device)
+    dgb = torch.empty(2, C, dtype=torch.float32, device=s.device)
+    with _timed("add_dropout_layernorm_bwd"):
+        N.check(N.lib().lss_add_dropout_ln_bwd(N.ptr(s), N.ptr(dy), _PW_DT[dy.dtype], N.ptr(gamma), rows, C, float(eps),
+                                               thr, scale, N.ptr(seed), N.ptr(ws), nbytes, N.ptr(ds), N.ptr(da),
+                                               _PW_DT[da_dtype], N.ptr(dgb[0]), N.ptr(dgb[1]), N.stream()),
+                "lss_add_dropout_ln_bwd")
+    return ds, da, dgb[0], dgb[1]
+
+
 def pack_conv_weight_s2_dgrad(w_oihw, pad):
     """OIHW fp32 of a stride-2 K x K conv -> (KT*KT, 4*Cin, Cout) bf16: the weight of the stride-1 conv that maps dY to
     the four phase planes of dX (lss_conv2d_pack_weights_s2_dgrad).  Returns (packed, KT)."""

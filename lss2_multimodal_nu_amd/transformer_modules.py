@@ -12,7 +12,10 @@ are native autograd nodes too (`_LinearFn`: the MFMA GEMM forward, the same GEMM
 on the transposed weight for the input gradient, csrc/linear_grad.hip for the
 weight and bias gradient; `_LayerNormFn`: the row kernel and its backward), next
 to the deformable-attention sampling core (`_DeformAttnFn`: HIP forward and
-backward); GELU, dropout and the residual adds stay torch elementwise ops.
+backward); GELU + dropout on the hidden and dropout + residual add + LayerNorm
+are native nodes as well (`_GeluDropoutFn`, `_AddDropoutLayerNormFn`:
+csrc/transformer_pointwise.hip, masks recomputed from a 16-byte device seed;
+LSS_TRANSFORMER_POINTWISE=0 leaves them to torch elementwise ops).
 Everything else (fp32, fp16 autocast, CPU, d_model != 256,
 LSS_TRANSFORMER_NATIVE=0) runs the parameters through torch ops, all heads
 sampled in ONE batched `grid_sample` where the sampling node does not apply.
@@ -29,9 +32,12 @@ from . import ops
 from .modules import _PRECISIONS, _native_training, _needs_autograd, _to_nhwc, default_precision
 
 # training calls of TransformerEncoderLayer.forward by route (as model_vovnet_transformer.LIFT_CALLS)
-TRANSFORMER_CALLS = {"native": 0, "composition": 0}
+# "pointwise": the native calls whose GELU / dropout / residual-add sites ran on the K12 nodes as well
+TRANSFORMER_CALLS = {"native": 0, "composition": 0, "pointwise": 0}
 # LSS_TRANSFORMER_NATIVE unset: see DESIGN.md 4b for the measurement that decides this
 _TRANSFORMER_NATIVE_DEFAULT = "1"
+# LSS_TRANSFORMER_POINTWISE unset: DESIGN.md 4b, same rule
+_TRANSFORMER_POINTWISE_DEFAULT = "1"
 
 
 class _PackedLinear:
@@ -196,6 +202,71 @@ class _LayerNormFn(torch.autograd.Function):
         return dx, dg.to(ctx.dtypes[0]), dbt.to(ctx.dtypes[1]), None
 
 
+def _rows_f32_bf16(t):
+    """A node input as the contiguous fp32 | bf16 rows the K12 row kernels take."""
+    t = t.detach().contiguous()
+    return t if t.dtype in (torch.float32, torch.bfloat16) else t.float()
+
+
+class _GeluDropoutFn(torch.autograd.Function):
+    """dropout(gelu(h)) on the bf16 hidden as one native node (ref: src/transformer_modules.py:211, activation and
+    dropout): ops.gelu_dropout / ops.gelu_dropout_bwd.  The mask is recomputed from the 16-byte device seed in both
+    directions; saves h and the seed (None = no dropout)."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda")
+    def forward(ctx, h, p, seed):
+        hc = h.detach().to(torch.bfloat16).contiguous()
+        ctx.save_for_backward(hc, seed)
+        ctx.p, ctx.dtype = p, h.dtype
+        return ops.gelu_dropout(hc, p, seed)
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, dy):
+        hc, seed = ctx.saved_tensors
+        dh = ops.gelu_dropout_bwd(hc, dy.to(torch.bfloat16).contiguous(), ctx.p, seed)
+        return dh.to(ctx.dtype), None, None
+
+
+class _AddDropoutLayerNormFn(torch.autograd.Function):
+    """LayerNorm(res + dropout(a)) as one native node (ref: src/transformer_modules.py:207-208, 212-213):
+    ops.add_dropout_layernorm -> fp32, ops.add_dropout_layernorm_bwd.  The sum s is formed in fp32 and never rounded;
+    saves s, gamma and the seed (None = no dropout).  Gradients come back in the inputs' dtypes."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda")
+    def forward(ctx, res, a, gamma, beta, eps, p, seed):
+        s, y = ops.add_dropout_layernorm(_rows_f32_bf16(res), _rows_f32_bf16(a), gamma.detach().float().contiguous(),
+                                         beta.detach().float().contiguous(), eps, p, seed)
+        ctx.save_for_backward(s, gamma, seed)
+        ctx.eps, ctx.p = eps, p
+        ctx.dtypes = (res.dtype, a.dtype, gamma.dtype, beta.dtype)
+        return y
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, dy):
+        s, gamma, seed = ctx.saved_tensors
+        res_dt, a_dt, g_dt, b_dt = ctx.dtypes
+        ds, da, dg, dbt = ops.add_dropout_layernorm_bwd(
+            s, _rows_f32_bf16(dy), gamma.detach().float().contiguous(), ctx.eps,
+            a_dt if a_dt == torch.bfloat16 else torch.float32, ctx.p, seed)
+        return ds.to(res_dt), da.to(a_dt), dg.to(g_dt), dbt.to(b_dt), None, None, None
+
+
+def _pointwise_native_ok(layer):
+    """Do the GELU-dropout and add-dropout-LayerNorm sites of a native training call take the K12 nodes?  (The switch
+    LSS_TRANSFORMER_POINTWISE, an exact-erf nn.GELU, and three dropout probabilities with a 16-bit threshold.)"""
+    if os.environ.get("LSS_TRANSFORMER_POINTWISE", _TRANSFORMER_POINTWISE_DEFAULT) == "0":
+        return False
+    act = layer.activation
+    if type(act) is not nn.GELU or getattr(act, "approximate", "none") != "none":
+        return False
+    return all(type(d) is nn.Dropout and ops.dropout_threshold(d.p) is not None
+               for d in (layer.dropout, layer.dropout1, layer.dropout2))
+
+
 def _transformer_native_ok(layer, src, pos, reference_points):
     """Does this TransformerEncoderLayer training call take the native linear / LayerNorm nodes?  (GPU tensors, bf16
     autocast - `modules._native_training()` -, d_model 256, d_ff a multiple of 64 up to 1024, a square token grid whose
@@ -354,10 +425,26 @@ class TransformerEncoderLayer(nn.Module):
         val = _LinearFn.apply(src, a.value_proj.weight, a.value_proj.bias, True)
         att = _DeformAttnFn.apply(val, ol, reference_points, H, W)
         att = _LinearFn.apply(att, a.output_proj.weight, a.output_proj.bias)
+        if _pointwise_native_ok(self):
+            TRANSFORMER_CALLS["pointwise"] += 1
+            return self._pointwise_tail(src, att)
         x1 = _LayerNormFn.apply(src + self.dropout1(att), self.norm1.weight, self.norm1.bias, self.norm1.eps)
         ff = _LinearFn.apply(x1, self.linear1.weight, self.linear1.bias)
         ff = _LinearFn.apply(self.dropout(self.activation(ff)), self.linear2.weight, self.linear2.bias)
         return _LayerNormFn.apply(x1 + self.dropout2(ff), self.norm2.weight, self.norm2.bias, self.norm2.eps)
+
+    def _pointwise_tail(self, src, att):
+        """`_forward_native` from the output projection on, with the three pointwise sites on the K12 nodes: fewer
+        rounding points than the torch ops (no bf16 stop between GELU and dropout, or between dropout and the fp32
+        residual sum).  One 16-byte seed per site, drawn on the device; none outside training or at p = 0."""
+        def seed(drop):
+            return ops.dropout_seed(src.device) if self.training and drop.p > 0 else None
+        n1, n2 = self.norm1, self.norm2
+        x1 = _AddDropoutLayerNormFn.apply(src, att, n1.weight, n1.bias, n1.eps, self.dropout1.p, seed(self.dropout1))
+        ff = _LinearFn.apply(x1, self.linear1.weight, self.linear1.bias)
+        ff = _GeluDropoutFn.apply(ff, self.dropout.p, seed(self.dropout))
+        ff = _LinearFn.apply(ff, self.linear2.weight, self.linear2.bias)
+        return _AddDropoutLayerNormFn.apply(x1, ff, n2.weight, n2.bias, n2.eps, self.dropout2.p, seed(self.dropout2))
 
 
 class LightweightBEVTransformer(nn.Module):
