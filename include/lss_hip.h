@@ -229,7 +229,8 @@ int lss_add_pos_fwd(const void* x, const float* pos, int B, int T, int C, int dt
  *                  [128,192) = attention_weights(q) as (head, point)
  *   token_bias     (H*W, 192) fp32 or NULL: added to every sample's offsets_logits row of the
  *                  same token.  With token_bias = pos @ [W_off; W_attn]^T the two linears can
- *                  run on src instead of q = src + pos (linearity), so q is never formed
+ *                  run on src instead of q = src + pos (linearity), so q is never formed.
+ *                  16-B aligned like value, offsets_logits and out (LSS_E_ALIGN otherwise)
  *   ref_x (W), ref_y (H) fp32 = torch.linspace(0, 1, n)  (:243-244)
  *   out            (B, H*W, C) in `dt`, ready for output_proj
  * Sampling is bilinear with zero padding at align_corners=False pixel coordinates, both

@@ -263,6 +263,7 @@ extern "C" int lss_deform_attn_fwd(const void* value, int value_layout, const fl
   if (n_heads != 8 || n_points != 8 || C != TC) return LSS_E_SHAPE;  // the reference's configuration
   if (value_layout != LSS_VALUE_NHWC && value_layout != LSS_VALUE_HEAD_MAJOR) return LSS_E_LAYOUT;
   if (!aligned16(value) || !aligned16(offsets_logits) || !aligned16(out)) return LSS_E_ALIGN;
+  if (token_bias && !aligned16(token_bias)) return LSS_E_ALIGN;  // read with 16-B loads; null = no bias
   const long long rows = (long long)B * H * W;
   if (rows >= (1LL << 31)) return LSS_E_SHAPE;
   const long long HW = (long long)H * W;
