@@ -22,11 +22,14 @@
 //     ds_read_b128 = 16 pixels x 32 channels) and issues two v_mfma_f32_16x16x32_bf16 against the two channel tiles:
 //     0.5 KiB of LDS reads per MFMA - the ratio of the ring kernel (section 4c) - no barrier, no flag, no DMA inside;
 //   * the K parts meet through LDS once (fp32, fixed order kp = 0, 1, 2, 3: deterministic), each wave finishing a
-//     quarter of the pixel tiles: folded BatchNorm scale / shift, residual, ReLU, one 16-B store per lane - the rows of
+//     quarter of the pixel tiles - its own part of those stays in registers, only the foreign parts cross LDS (below:
+//     ks_slot_tile) -: folded BatchNorm scale / shift, residual, ReLU, one 16-B store per lane - the rows of
 //     channel tile t are the channels {8 q + 4 t + i}, so lane (q, n) ends with 8 CONSECUTIVE channels of pixel n and
 //     the four q lanes of a pixel write 64 contiguous bytes (no LDS staging of the output tile).
 // No inter-workgroup communication, no bounded waits: nothing here can hang.
 #include <stdlib.h>
+
+#include <type_traits>
 
 #include "lss_common.h"
 
@@ -130,10 +133,60 @@ __device__ __forceinline__ u32x4 ks_pack8(const float (&v)[8]) {
   return (u32x4){lss_pack_bf2(v[0], v[1]), lss_pack_bf2(v[2], v[3]), lss_pack_bf2(v[4], v[5]), lss_pack_bf2(v[6], v[7])};
 }
 
-// the K parts of one (tile, channel tile, lane) cell meet: p0 is part kp = 0, part kp lies kstride further; summed in
-// the fixed order kp = 0 .. NKW - 1
+// The K parts meet through LDS - the FOREIGN ones only.  Wave (kp, ph) finishes the tiles j = kp, kp + NKW, .. of its
+// pixel part; it keeps its own accumulators of those tiles in registers and writes to LDS only the tiles another wave
+// finishes (the part[] layout is the one of the full exchange, a wave's own cells are simply never written or read).
+// So that "the tiles a wave finishes" are the same REGISTERS in every wave, each wave walks the pixel tiles of its part
+// rotated by its kp: accumulator slot i holds tile (i + kp) mod PXT.  The finished tiles are then the slots 0, NKW,
+// 2 NKW, .. (slot k NKW is tile kp + k NKW; where that is >= PXT the rotation has wrapped to a tile another wave
+// finishes and the slot is sent like the others) - no register is chosen at run time, one copy of the code serves all
+// waves, and what depends on kp is addresses.
+__device__ __forceinline__ int ks_slot_tile(int slot, int kp, int pxt) {
+  const int t = slot + kp;
+  return t >= pxt ? t - pxt : t;
+}
+
+// per-lane patch offsets of a wave's pixel tiles by slot: pixel n of tile t of the pixel part is pixel pl0 + 16 t of the
+// block (pl0 = first pixel of the part + n), x_first + that many pixels into image rows of W pixels; a patch row is
+// rowpitch positions.  Pixels past the block's end (npx pixels) read its last one.
+template <int PXT>
+__device__ __forceinline__ void ks_slot_offsets(int (&ab)[PXT], int kp, int pl0, int x_first, int npx, int W,
+                                                int rowpitch, int laneoff) {
+  const int plast = npx - 1;
+  const int yl = (x_first + plast) / W, xl = x_first + plast - yl * W;   // wave-uniform
+  const int y0 = (x_first + pl0) / W, x0 = x_first + pl0 - y0 * W;       // tile 0: where the rotation wraps to
+  int t = ks_slot_tile(0, kp, PXT);                                      // slot 0 (kp can be PXT: three tiles, four K parts)
+  int pl = pl0 + t * 16;
+  int y = (x_first + pl) / W, x = x_first + pl - y * W;
+#pragma unroll
+  for (int i = 0; i < PXT; ++i) {
+    const bool live = pl < npx;
+    ab[i] = ((live ? y : yl) * rowpitch + (live ? x : xl)) * 32 + laneoff;
+    pl += 16; x += 16;
+    if (x >= W) { x -= W; ++y; }
+    if (++t == PXT) { t = 0; pl = pl0; x = x0; y = y0; }   // wave-uniform
+  }
+}
+
+// the K parts of one (tile, channel tile, lane) cell meet: own is the finishing wave's part, g[] the NKW - 1 foreign
+// parts in the order of their kp; POS = the place of the own part among them.  Summed in the fixed order kp = 0 ..
+// NKW - 1 with the own part at its own position: the fp32 adds of a sum over all NKW parts read from LDS.
+template <int NKW, int POS>
+__device__ __forceinline__ f32x4 ks_sum_parts(const f32x4& own, const f32x4 (&g)[NKW - 1]) {
+  f32x4 sum = POS == 0 ? own : g[0];
+#pragma unroll
+  for (int q = 1; q < NKW; ++q) {
+    const f32x4 pv = q == POS ? own : g[q > POS ? q - 1 : q];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) sum[i] += pv[i];
+  }
+  return sum;
+}
+
+// all NKW parts of a cell from LDS (p0 is part kp = 0, part kp lies kstride further), summed in the same fixed order:
+// the full exchange, kept where keeping the own part in registers did not pay (stride-2 mode with four K parts)
 template <int NKW>
-__device__ __forceinline__ f32x4 ks_sum_parts(const f32x4* p0, int kstride) {
+__device__ __forceinline__ f32x4 ks_sum_lds(const f32x4* p0, int kstride) {
   f32x4 sum = p0[0];
 #pragma unroll
   for (int k = 1; k < NKW; ++k) {
@@ -142,6 +195,43 @@ __device__ __forceinline__ f32x4 ks_sum_parts(const f32x4* p0, int kstride) {
     for (int i = 0; i < 4; ++i) sum[i] += pv[i];
   }
   return sum;
+}
+
+// f(POS) for the wave's kp, a wave-uniform branch around the adds alone.  kp = 0 and kp = 1 share POS = 0: they differ
+// in the order of the operands of the FIRST add only, and a + b is b + a bit for bit - so two K parts need no branch.
+template <int NKW, class F>
+__device__ __forceinline__ void ks_for_pos(int kp, F&& f) {
+  if constexpr (NKW == 2) f(std::integral_constant<int, 0>{});
+  else if (kp < 2) f(std::integral_constant<int, 0>{});
+  else if (kp == 2) f(std::integral_constant<int, 2>{});
+  else f(std::integral_constant<int, 3>{});
+}
+
+// the epilogue of 8 consecutive channels: fma(v, scale, shift) (+ the residual pair words rv) -> ReLU -> bf16; one
+// function for the stride-1 and the stride-2 kernels, and the contraction WRITTEN OUT so that the bits do not hang on
+// what the optimiser fuses.  RES = false: no add at all - adding 0.f would turn -0.f into 0.f.  split0: channel 0 of
+// the eight rounds its product before the shift is added.  That is what conv1's output (y) of the stride-2 kernel has
+// computed since the kernel exists - its `v * sc + sh` was compiled to FMAs except for the first element of every group
+// of eight, which the SLP vectoriser paired with a K-part add (v_mul, then v_pk_add) - and outputs do not move here.
+// A change that is allowed to move bits should delete split0 and fuse every channel.
+template <bool RES>
+__device__ __forceinline__ u32x4 ks_finish8(float (&v)[8], const float (&sc)[8], const float (&sh)[8], const uint4& rv,
+                                            bool relu, bool split0) {
+  const unsigned int ru[4] = {rv.x, rv.y, rv.z, rv.w};
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    float r;
+    if (split0 && i == 0) {
+#pragma clang fp contract(off)
+      const float p = v[i] * sc[i];
+      r = p + sh[i];
+    } else {
+      r = __builtin_fmaf(v[i], sc[i], sh[i]);
+    }
+    if constexpr (RES) r += lss_bf2f((unsigned short)((i & 1) ? ru[i >> 1] >> 16 : ru[i >> 1] & 0xffff));
+    v[i] = relu ? fmaxf(r, 0.f) : r;
+  }
+  return ks_pack8(v);
 }
 
 struct KsArgs {
@@ -163,6 +253,7 @@ struct KsArgs {
 template <int KSW, int NKW, int PXT>
 __global__ __launch_bounds__(256, 1) void conv_ks_kernel(const KsArgs a) {
   static_assert(KSW % 9 == 0 && (NKW == 4 || NKW == 2), "a wave's K part is whole chunks of nine taps");
+  static_assert(PXT >= NKW - 1, "ks_slot_tile: slot + kp < 2 PXT");
   constexpr int NPW = 4 / NKW;          // pixel parts
   constexpr int CPW = KSW / 9;          // 32-channel chunks per wave
   constexpr int NT = PXT * NPW;         // pixel tiles of the workgroup
@@ -207,24 +298,13 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(const KsArgs a) {
 #pragma unroll
   for (int s = 0; s < WPRE; ++s) load_w(s);
 
-  // ---- per-lane patch offsets of the wave's pixel tiles (pixel n of tile j; tap (ky, kx) adds (ky WP + kx) 64) ----
-  // and the residual pieces of the tiles this wave will finish (requested now: long landed when the epilogue wants them)
+  // ---- per-lane patch offsets of the wave's pixel tiles (pixel n of the tile in slot i; tap (ky, kx) adds (ky WP + kx)
+  // 64) ---- and the residual pieces of the tiles this wave will finish (requested now: long landed when the epilogue
+  // wants them)
   const int npx = min(a.PB, HW - p0);
   int ab[PXT];
-  {
-    const int x_first = p0 - y_first * a.W;
-    const int plast = npx - 1;                                   // pixels past the block's end read its last one
-    const int yl = (x_first + plast) / a.W, xl = x_first + plast - yl * a.W;   // wave-uniform
-    int pl = ph * PXT * 16 + n;
-    int y = (x_first + pl) / a.W, x = x_first + pl - y * a.W;     // relative to y_first
-#pragma unroll
-    for (int j = 0; j < PXT; ++j) {
-      const bool live = pl < npx;
-      ab[j] = ((live ? y : yl) * WP + (live ? x : xl)) * 32 + (kq >> 1) * a.nposp * 32 + (kq & 1) * 16;
-      pl += 16; x += 16;
-      if (x >= a.W) { x -= a.W; ++y; }
-    }
-  }
+  ks_slot_offsets<PXT>(ab, kp, ph * PXT * 16 + n, p0 - y_first * a.W, npx, a.W, WP,
+                       (kq >> 1) * a.nposp * 32 + (kq & 1) * 16);
   st.stamp(1);  // every request (weights, patch pieces) has been issued
   constexpr int NOWN = (PXT + NKW - 1) / NKW;   // tiles a wave finishes: j = kp, kp + NKW, ...
   const int ch = cb * 32 + kq * 8;             // this lane's 8 consecutive output channels
@@ -237,6 +317,11 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(const KsArgs a) {
     if (a.residual != nullptr && j < PXT && pl < npx)
       rres[k] = *reinterpret_cast<const uint4*>(a.residual + ((size_t)b * HW + p0 + pl) * a.Cout + ch);
   }
+  // epilogue constants of this lane's 8 consecutive channels, requested with everything else: 16 registers through
+  // the main phase.  Requested after it - between the two barriers of the exchange, where they used to be - their
+  // latency WAS the tail: whatever the exchange did not cover, the epilogue waited for (profiles/r15_ks_tail_ab.txt).
+  float sc[8], sh[8];
+  ks_load_affine(a.scale, a.shift, ch, sc, sh);
   f32x4 acc[PXT][2];
 #pragma unroll
   for (int j = 0; j < PXT; ++j) {
@@ -282,49 +367,54 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(const KsArgs a) {
   }
 
   // ---- the K parts meet: part[kp][tile][ct][lane] (16 B each), summed in the fixed order kp = 0 .. NKW - 1 ----
+  // (a wave writes only the slots another wave finishes; the barrier in front stays: the exchange reuses the patch's LDS)
   st.main_end(acc[0][0], acc[PXT - 1][1]);
   __syncthreads();  // every wave is done reading the patch: its LDS is free
   f32x4* part = reinterpret_cast<f32x4*>(smem);
 #pragma unroll
-  for (int j = 0; j < PXT; ++j) {
-    const int tile = ph * PXT + j;
+  for (int i = 0; i < PXT; ++i) {
+    if (i % NKW == 0 && kp + i < PXT) continue;  // wave-uniform: this wave finishes the slot itself, from its registers
+    const int tile = ph * PXT + ks_slot_tile(i, kp, PXT);
 #pragma unroll
-    for (int ct = 0; ct < 2; ++ct) part[((kp * NT + tile) * 2 + ct) * 64 + lane] = acc[j][ct];
+    for (int ct = 0; ct < 2; ++ct) part[((kp * NT + tile) * 2 + ct) * 64 + lane] = acc[i][ct];
   }
-  // epilogue constants of this lane's 8 consecutive channels, requested before the barrier
-  float sc[8], sh[8];
-  ks_load_affine(a.scale, a.shift, ch, sc, sh);
   __syncthreads();
   st.stamp(4);
-  // wave (kp, ph) finishes the tiles ph * PXT + j with j % NKW == kp
+  // wave (kp, ph) finishes the tiles ph * PXT + j, j = kp + k NKW < PXT: slot k NKW.  Every foreign part of every such
+  // tile is requested before the first add (a slot that wrapped reads the last tile's cells and stores nothing).
   const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(
       a.y, 0, a.wt ? (int)((size_t)a.B * HW * a.Cout * 2) : 0, 0x00020000);
+  f32x4 fp[NOWN][2][NKW - 1];
+#pragma unroll
+  for (int k = 0; k < NOWN; ++k) {
+    const int tile = ph * PXT + min(kp + k * NKW, PXT - 1);
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+      for (int m = 0; m < NKW - 1; ++m)
+        fp[k][ct][m] = part[(((m < kp ? m : m + 1) * NT + tile) * 2 + ct) * 64 + lane];
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  f32x4 sum[NOWN][2];
+  ks_for_pos<NKW>(kp, [&](auto pos) __attribute__((always_inline)) {
+#pragma unroll
+    for (int k = 0; k < NOWN; ++k)
+#pragma unroll
+      for (int ct = 0; ct < 2; ++ct) sum[k][ct] = ks_sum_parts<NKW, decltype(pos)::value>(acc[k * NKW][ct], fp[k][ct]);
+  });
 #pragma unroll
   for (int k = 0; k < NOWN; ++k) {
     const int j = kp + k * NKW;
-    if (j >= PXT) break;  // wave-uniform
-    const int tile = ph * PXT + j;
-    const int pl = tile * 16 + n;
-    const bool live = pl < npx;
+    const int pl = (ph * PXT + j) * 16 + n;
+    const bool live = j < PXT && pl < npx;               // dead tiles and pixels compute on a clamped address, no store
     const size_t o = ((size_t)b * HW + p0 + (live ? pl : 0)) * a.Cout + ch;
-    const uint4 rv = rres[k];
     float v[8];
 #pragma unroll
-    for (int ct = 0; ct < 2; ++ct) {
-      const f32x4 sum = ks_sum_parts<NKW>(part + (tile * 2 + ct) * 64 + lane, NT * 2 * 64);
+    for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) v[4 * ct + i] = sum[i];
-    }
-    const unsigned int ru[4] = {rv.x, rv.y, rv.z, rv.w};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float lo = v[2 * k] * sc[2 * k] + sh[2 * k] + lss_bf2f((unsigned short)(ru[k] & 0xffff));
-      float hi = v[2 * k + 1] * sc[2 * k + 1] + sh[2 * k + 1] + lss_bf2f((unsigned short)(ru[k] >> 16));
-      if (a.relu) { lo = fmaxf(lo, 0.f); hi = fmaxf(hi, 0.f); }
-      v[2 * k] = lo; v[2 * k + 1] = hi;
-    }
+      for (int i = 0; i < 4; ++i) v[4 * ct + i] = sum[k][ct][i];
+    const u32x4 ov = ks_finish8<true>(v, sc, sh, rres[k], a.relu != 0, false);
     if (live) {
-      const u32x4 ov = ks_pack8(v);
       if (a.wt) __builtin_amdgcn_raw_buffer_store_b128(ov, yrsrc, (int)(o * 2), 0, 16);  // write-through
       else *reinterpret_cast<u32x4*>(a.y + o) = ov;
     }
@@ -444,7 +534,8 @@ KsPlan ks_plan(int B, int H, int W, int Cin, int Cout) {
 //     4 A fragments in registers, 12 + 12 accumulators;
 //   * the 1x1 rides on the centre tap: at k-step 4 the wave holds the B fragments it needs and issues 12 more MFMAs
 //     against the downsample's A fragments into the second accumulator set - no LDS read of its own;
-//   * both accumulator sets meet through LDS in the fixed order kp = 0 .. NKW - 1 (96 KiB of partial tiles) and leave
+//   * both accumulator sets meet through LDS in the fixed order kp = 0 .. NKW - 1 (NKW = 2: the foreign parts of each
+//     tile, 48 KiB; NKW = 4: all 96 KiB of partial tiles) and leave
 //     through the same epilogue: scale / shift (channels [0, Cout) of the arrays: y, [Cout, 2 Cout): y2), ReLU on y only.
 struct KsS2Args {
   const unsigned short* x;        // (B, H, W, Cin) bf16 NHWC
@@ -466,6 +557,10 @@ template <int NKW>
 __global__ __launch_bounds__(256, 1) void conv_ks_s2_dual_kernel(const KsS2Args a) {
   static_assert(NKW == 4 || NKW == 2, "one 32-channel chunk of nine taps per K part");
   constexpr int NPW = 4 / NKW, PXT = KS2_PXT, CT = KS2_CT, NT = PXT * NPW, NCH = NKW;
+  // OWN: the finishing wave keeps its own K part in registers (foreign parts only through LDS, slots rotated by kp, as
+  // in the stride-1 kernel).  With four K parts and three tiles a wave finishes at most one tile and the fourth none:
+  // measured slower there (profiles/r15_ks_tail_ab.txt), so NKW = 4 keeps the full exchange and tile order.
+  constexpr bool OWN = NKW == 2;
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -502,21 +597,10 @@ __global__ __launch_bounds__(256, 1) void conv_ks_s2_dual_kernel(const KsS2Args 
   for (int ct = 0; ct < CT; ++ct) wd[ct] = *reinterpret_cast<const bf16x8*>(wp + (9 * CT + ct) * 1024);
 
   const int npx = min(a.PB, HWo - p0);
-  int ab[PXT];
-  {
-    const int x_first = p0 - r0 * a.Wo;
-    const int plast = npx - 1;                                   // pixels past the block's end read its last one
-    const int yl = (x_first + plast) / a.Wo, xl = x_first + plast - yl * a.Wo;
-    int pl = ph * PXT * 16 + n;
-    int y = (x_first + pl) / a.Wo, x = x_first + pl - y * a.Wo;   // relative to r0
-#pragma unroll
-    for (int j = 0; j < PXT; ++j) {
-      const bool live = pl < npx;
-      ab[j] = (2 * (live ? y : yl) * WP + (live ? x : xl)) * 32 + (kq >> 1) * a.nposp * 32 + (kq & 1) * 16;
-      pl += 16; x += 16;
-      if (x >= a.Wo) { x -= a.Wo; ++y; }
-    }
-  }
+  const int rot = OWN ? kp : 0;
+  int ab[PXT];   // by slot, as in the stride-1 kernel; an output row is two patch rows
+  ks_slot_offsets<PXT>(ab, rot, ph * PXT * 16 + n, p0 - r0 * a.Wo, npx, a.Wo, 2 * WP,
+                       (kq >> 1) * a.nposp * 32 + (kq & 1) * 16);
   st.stamp(1);
   f32x4 acc[PXT][CT], acc2[PXT][CT];
 #pragma unroll
@@ -566,15 +650,17 @@ __global__ __launch_bounds__(256, 1) void conv_ks_s2_dual_kernel(const KsS2Args 
   __syncthreads();  // every wave is done reading the patch: its LDS is free
   f32x4* part = reinterpret_cast<f32x4*>(smem);
 #pragma unroll
-  for (int j = 0; j < PXT; ++j) {
-    const int tile = ph * PXT + j;
+  for (int i = 0; i < PXT; ++i) {
+    if (OWN && i % NKW == 0 && kp + i < PXT) continue;  // wave-uniform: finished here, from the registers
+    const int tile = ph * PXT + ks_slot_tile(i, rot, PXT);
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
-      part[(((0 * NKW + kp) * NT + tile) * CT + ct) * 64 + lane] = acc[j][ct];
-      part[(((1 * NKW + kp) * NT + tile) * CT + ct) * 64 + lane] = acc2[j][ct];
+      part[(((0 * NKW + kp) * NT + tile) * CT + ct) * 64 + lane] = acc[i][ct];
+      part[(((1 * NKW + kp) * NT + tile) * CT + ct) * 64 + lane] = acc2[i][ct];
     }
   }
-  // epilogue constants: [output][channel group g of 32][8 consecutive channels cb 64 + 32 g + 8 kq ..]
+  // epilogue constants: [output][channel group g of 32][8 consecutive channels cb 64 + 32 g + 8 kq ..] - 64 per lane,
+  // requested here: in the prologue they sit in front of its vmcnt(0) and cost the fill 0.3-0.4 us (measured)
   float sc[2][2][8], sh[2][2][8];
 #pragma unroll
   for (int o = 0; o < 2; ++o)
@@ -583,15 +669,71 @@ __global__ __launch_bounds__(256, 1) void conv_ks_s2_dual_kernel(const KsS2Args 
       ks_load_affine(a.scale, a.shift, o * a.Cout + cb * 64 + g * 32 + kq * 8, sc[o][g], sh[o][g]);
   __syncthreads();
   st.stamp(4);
-  // wave (kp, ph) finishes the tiles ph * PXT + j with j % NKW == kp, both outputs
+  // wave (kp, ph) finishes the tiles ph * PXT + j, j = kp + k NKW < PXT (slot k NKW), both outputs; every foreign part
+  // is requested before the first add
   constexpr int NOWN = (PXT + NKW - 1) / NKW;
+  if constexpr (!OWN) {
+    // full exchange: wave (kp, ph) finishes the tiles ph * PXT + j with j % NKW == kp from the NKW parts in LDS
+#pragma unroll
+    for (int k = 0; k < NOWN; ++k) {
+      const int j = kp + k * NKW;
+      if (j >= PXT) break;  // wave-uniform
+      const int tile = ph * PXT + j;
+      const int pl = tile * 16 + n;
+      const bool live = pl < npx;
+      const size_t opix = ((size_t)b * HWo + p0 + (live ? pl : 0)) * a.Cout + cb * 64 + kq * 8;
+#pragma unroll
+      for (int o = 0; o < 2; ++o)
+#pragma unroll
+        for (int g = 0; g < 2; ++g) {
+          float v[8];
+#pragma unroll
+          for (int tt = 0; tt < 2; ++tt) {
+            const f32x4 sum = ks_sum_lds<NKW>(part + ((o * NKW * NT + tile) * CT + 2 * g + tt) * 64 + lane, NT * CT * 64);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[4 * tt + i] = sum[i];
+          }
+          // (the source form this instantiation has always had, not ks_finish8: written out, the same values compile
+          // to ~40 more VALU instructions here, 0.08 us per launch in the kernel trace)
+#pragma unroll
+          for (int i = 0; i < 8; ++i) {
+            v[i] = v[i] * sc[o][g][i] + sh[o][g][i];
+            if (o == 0 && a.relu) v[i] = fmaxf(v[i], 0.f);
+          }
+          if (live) *reinterpret_cast<u32x4*>((o == 0 ? a.y : a.y2) + opix + g * 32) = ks_pack8(v);
+        }
+    }
+    st.drain();
+    return;
+  }
+  f32x4 fp[NOWN][2][CT][NKW - 1];
+#pragma unroll
+  for (int k = 0; k < NOWN; ++k) {
+    const int tile = ph * PXT + min(kp + k * NKW, PXT - 1);
+#pragma unroll
+    for (int o = 0; o < 2; ++o)
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct)
+#pragma unroll
+        for (int m = 0; m < NKW - 1; ++m)
+          fp[k][o][ct][m] = part[(((o * NKW + (m < kp ? m : m + 1)) * NT + tile) * CT + ct) * 64 + lane];
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  f32x4 sum[NOWN][2][CT];
+  ks_for_pos<NKW>(kp, [&](auto pos) __attribute__((always_inline)) {
+#pragma unroll
+    for (int k = 0; k < NOWN; ++k)
+#pragma unroll
+      for (int ct = 0; ct < CT; ++ct) {
+        sum[k][0][ct] = ks_sum_parts<NKW, decltype(pos)::value>(acc[k * NKW][ct], fp[k][0][ct]);
+        sum[k][1][ct] = ks_sum_parts<NKW, decltype(pos)::value>(acc2[k * NKW][ct], fp[k][1][ct]);
+      }
+  });
 #pragma unroll
   for (int k = 0; k < NOWN; ++k) {
     const int j = kp + k * NKW;
-    if (j >= PXT) break;  // wave-uniform
-    const int tile = ph * PXT + j;
-    const int pl = tile * 16 + n;
-    const bool live = pl < npx;
+    const int pl = (ph * PXT + j) * 16 + n;
+    const bool live = j < PXT && pl < npx;               // dead tiles and pixels compute on a clamped address, no store
     const size_t opix = ((size_t)b * HWo + p0 + (live ? pl : 0)) * a.Cout + cb * 64 + kq * 8;
 #pragma unroll
     for (int o = 0; o < 2; ++o)
@@ -599,18 +741,11 @@ __global__ __launch_bounds__(256, 1) void conv_ks_s2_dual_kernel(const KsS2Args 
       for (int g = 0; g < 2; ++g) {
         float v[8];
 #pragma unroll
-        for (int tt = 0; tt < 2; ++tt) {
-          const int ct = 2 * g + tt;
-          const f32x4 sum = ks_sum_parts<NKW>(part + ((o * NKW * NT + tile) * CT + ct) * 64 + lane, NT * CT * 64);
+        for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
-          for (int i = 0; i < 4; ++i) v[4 * tt + i] = sum[i];
-        }
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          v[i] = v[i] * sc[o][g][i] + sh[o][g][i];
-          if (o == 0 && a.relu) v[i] = fmaxf(v[i], 0.f);
-        }
-        if (live) *reinterpret_cast<u32x4*>((o == 0 ? a.y : a.y2) + opix + g * 32) = ks_pack8(v);
+          for (int i = 0; i < 4; ++i) v[4 * tt + i] = sum[k][o][2 * g + tt][i];
+        const u32x4 ov = ks_finish8<false>(v, sc[o][g], sh[o][g], make_uint4(0, 0, 0, 0), o == 0 && a.relu, o == 0);
+        if (live) *reinterpret_cast<u32x4*>((o == 0 ? a.y : a.y2) + opix + g * 32) = ov;
       }
   }
   st.drain();
