@@ -772,8 +772,10 @@ int lss_linear_res_ln_fwd(const void* x, const void* w, const float* bias, const
  * Fused 1x1 head + log-softmax + weighted NLL, forward and backward.
  * replaces: `up2[4]` = nn.Conv2d(128, outC, 1) (src/modules.py:115) followed by nn.CrossEntropyLoss(weight) of
  *           SimpleLoss / MultiLoss (src/tools.py:221-238), and their autograd: the (B, outC, H, W) logits are
- *           neither written nor read - the loss comes straight from the last activation.
- *   y (M, Cin) bf16 NHWC rows of the last conv + BatchNorm + ReLU unit, M = B*H*W, Cin = 128;
+ *           neither written nor read - the loss comes straight from the last activation.  Also `seg_head[6]` =
+ *           nn.Conv2d(64, outC, 1) of BEVEncoderTransformer (src/model_vovnet_transformer.py:143) under
+ *           MultiTaskLoss's weighted cross-entropy (train_vovnet_transformer.py:83-84).
+ *   y (M, Cin) bf16 NHWC rows of the last conv + BatchNorm + ReLU unit, M = B*H*W, Cin = 64 or 128;
  *   head_w (K, Cin) fp32, head_b (K) fp32, K = 4 or 8; target (M) int64 (entries outside [0, K) are ignored);
  *   class_w (K) fp32.  loss = sum_p class_w[t_p] * (logsumexp(logit_p) - logit_p[t_p]) / sum_p class_w[t_p].
  *   workspace: lss_head_ce_workspace_bytes(K) bytes.  sums (2) fp32 out: {sum w*nll, sum w}, kept for the backward.
@@ -789,9 +791,10 @@ int lss_head_ce_bwd(const void* y, const float* head_w, const float* head_b, con
 
 /* The 1x1 head ALONE, forward and backward, for a training-mode `model(x)` whose loss the caller computes
  * (ref src/modules.py:115 `up2[4] = nn.Conv2d(128, outC, kernel_size=1)` and its autograd behind train.py:61 when the
- * loss is `MultiLoss` over returned logits, src/tools.py:232-251).  y: (M, 128) bf16 NHWC rows, M = B * HW;
- * logits / grad_logits: (B, K, H, W) fp32 NCHW; K in {4, 8}.  The backward leaves dy (M, 128) bf16 and the
- * fixed-order sums d_head_w (K, 128), d_head_b (K); workspace: lss_head_ce_workspace_bytes(K).  Exists because the
+ * loss is `MultiLoss` over returned logits, src/tools.py:232-251; likewise `seg_head[6] = nn.Conv2d(64, outC, 1)`,
+ * src/model_vovnet_transformer.py:143).  y: (M, Cin) bf16 NHWC rows, M = B * HW, Cin = 64 or 128;
+ * logits / grad_logits: (B, K, H, W) fp32 NCHW; K in {4, 8}.  The backward leaves dy (M, Cin) bf16 and the
+ * fixed-order sums d_head_w (K, Cin), d_head_b (K); workspace: lss_head_ce_workspace_bytes(K).  Exists because the
  * library convolution's backward is not replay-safe inside a HIP graph. */
 int lss_head1x1_fwd(const void* y, const float* head_w, const float* head_b, long long M, long long HW, int Cin, int K,
                     float* logits, void* stream);

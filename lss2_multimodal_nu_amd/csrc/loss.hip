@@ -138,14 +138,16 @@ namespace {
 // ---------------------------------------------------------------------------
 // Fused 1x1 head + log-softmax + weighted NLL, forward and backward.
 // replaces: `up2[4]` (nn.Conv2d(128, outC, 1), src/modules.py:115) followed by nn.CrossEntropyLoss(weight) of
-//           SimpleLoss / MultiLoss (src/tools.py:221-238), and their autograd.
+//           SimpleLoss / MultiLoss (src/tools.py:221-238), and their autograd; with CIN = 64 the `seg_head[6]`
+//           (nn.Conv2d(64, outC, 1), src/model_vovnet_transformer.py:143) of BEVEncoderTransformer.
 //   logit[p][k] = b[k] + sum_c y[p][c] * W[k][c];  loss = sum_p w[t_p] * (lse_p - logit[p][t_p]) / sum_p w[t_p]
 // y is the NHWC bf16 activation the last conv + BatchNorm + ReLU unit produced; the (B, K, H, W) logits are never
 // written (forward) nor read (backward: they are recomputed from y, which autograd keeps anyway).
 // Work split: a pixel's Cin channels sit on Cin/8 consecutive lanes (8 channels = one 16-B load per lane), so a wave
 // covers 64 / (Cin/8) pixels per pass; the K <= 8 partial dot products of a lane are summed over the pixel's lanes
-// with DPP row operations (Cin = 128: a whole DPP row of 16).  Forward: per-workgroup partial sums in a fixed order
-// (bit-reproducible), finalize as the plain CE.  Backward: dy[p][c] = sum_k g[p][k] W[k][c] with
+// with DPP row operations (Cin = 128: a whole DPP row of 16; Cin = 64: half a row, 8 lanes).  Forward: per-workgroup
+// partial sums in a fixed order (bit-reproducible), finalize as the plain CE.
+// Backward: dy[p][c] = sum_k g[p][k] W[k][c] with
 // g = grad * w[t] * (softmax - onehot) / sum w, written bf16; dW[k][c] = sum_p g[p][k] y[p][c] and db accumulate in
 // registers per lane, meet in LDS per workgroup and leave as per-workgroup partials that a second kernel sums in a
 // fixed order.
@@ -156,12 +158,16 @@ template <int DPP>
 __device__ __forceinline__ float hc_dpp(float x) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), DPP, 0xf, 0xf, false));
 }
-// sum over the 16 lanes of a DPP row (every lane gets the total): xor 1, xor 2 (quad_perm), half-mirror, mirror
-__device__ __forceinline__ float hc_row_sum16(float v) {
+// sum over the LPP lanes of a pixel (every lane gets the total): xor 1, xor 2 (quad_perm), half-mirror - the 8 lanes
+// of a 64-channel pixel, half a DPP row - and for the 16 lanes of a 128-channel pixel the row mirror, which for 8 lanes
+// would add the neighbouring pixel
+template <int LPP>
+__device__ __forceinline__ float hc_pixel_sum(float v) {
+  static_assert(LPP == 8 || LPP == 16, "a pixel sits on 8 or 16 lanes");
   v += hc_dpp<0xB1>(v);
   v += hc_dpp<0x4E>(v);
   v += hc_dpp<0x141>(v);
-  v += hc_dpp<0x140>(v);
+  if constexpr (LPP == 16) v += hc_dpp<0x140>(v);
   return v;
 }
 
@@ -169,7 +175,7 @@ __device__ __forceinline__ float hc_row_sum16(float v) {
 // NCHW fp32: `logits[(b K + k) HW + pix]`) and backward (g[p][k] read from the NCHW fp32 gradient of the logits): the
 // `up2[4]` of a training-mode `model(x)` call whose loss is computed elsewhere.  The library's convolution is not an
 // option there: its backward is not safe inside a HIP graph ("What the graph exposed").
-template <int K, int MODE>
+template <int K, int MODE, int CIN>
 __global__ __launch_bounds__(256) void head_ce_kernel(const unsigned short* __restrict__ y,
                                                       const float* __restrict__ hw, const float* __restrict__ hb,
                                                       const long long* __restrict__ tgt,
@@ -179,7 +185,9 @@ __global__ __launch_bounds__(256) void head_ce_kernel(const unsigned short* __re
                                                       float* __restrict__ dw_part, float* __restrict__ logits_io,
                                                       long long HW) {
   constexpr bool BWD = MODE == 1 || MODE == 3, PLAIN = MODE >= 2;
-  constexpr int CIN = 128, LPP = CIN / 8;  // lanes per pixel (16 = one DPP row)
+  constexpr int LPP = CIN / 8;  // lanes per pixel (16 = one DPP row, 8 = half of one)
+  static_assert(CIN == 64 || CIN == 128, "head_ce_kernel: 64 or 128 input channels");
+  static_assert(K <= LPP, "lane `sub == k` stores class k");
   __shared__ float red[2][256];
   __shared__ float dwred[BWD ? 4 * K * CIN : 1];
   __shared__ float dbred[BWD ? 4 * K : 1];
@@ -206,7 +214,7 @@ __global__ __launch_bounds__(256) void head_ce_kernel(const unsigned short* __re
       for (int j = 0; j < 8; ++j) dwa[k][j] = 0.f;
     }
   }
-  constexpr int PPW = 64 / LPP;  // pixels per wave pass (4)
+  constexpr int PPW = 64 / LPP;  // pixels per wave pass (4, or 8 with 64 channels)
   const long long stride = (long long)gridDim.x * 4 * PPW;
   for (long long p0 = ((long long)blockIdx.x * 4 + wave) * PPW; p0 < M; p0 += stride) {
     const long long p = p0 + prow;
@@ -231,7 +239,7 @@ __global__ __launch_bounds__(256) void head_ce_kernel(const unsigned short* __re
           float a = 0.f;
 #pragma unroll
           for (int j = 0; j < 8; ++j) a = fmaf(yv[j], w[k][j], a);
-          a = hc_row_sum16(a) + bias[k];
+          a = hc_pixel_sum<LPP>(a) + bias[k];
           if (sub == k) mine = a;
         }
         if (live && sub < K) lp[(size_t)sub * HW] = mine;
@@ -269,7 +277,7 @@ __global__ __launch_bounds__(256) void head_ce_kernel(const unsigned short* __re
       float a = 0.f;
 #pragma unroll
       for (int j = 0; j < 8; ++j) a = fmaf(yv[j], w[k][j], a);
-      logit[k] = hc_row_sum16(a) + bias[k];
+      logit[k] = hc_pixel_sum<LPP>(a) + bias[k];
       mx = fmaxf(mx, logit[k]);
     }
     float ex[K], se = 0.f;
@@ -336,18 +344,20 @@ __global__ __launch_bounds__(256) void head_ce_kernel(const unsigned short* __re
       part[2 * blockIdx.x + 1] = red[1][0];
     }
   } else {
-    // dW / db of this workgroup: the 4 pixel rows of a wave meet through shuffles (xor 16, xor 32), the 4 waves
-    // through LDS, in a fixed order
+    // dW / db of this workgroup: the PPW pixel rows of a wave meet through shuffles ((xor 8,) xor 16, xor 32), the
+    // 4 waves through LDS, in a fixed order
 #pragma unroll
     for (int k = 0; k < K; ++k) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         float v = dwa[k][j];
+        if constexpr (LPP == 8) v += __shfl_xor(v, 8, 64);
         v += __shfl_xor(v, 16, 64);
         v += __shfl_xor(v, 32, 64);
         if (prow == 0) dwred[(wave * K + k) * CIN + sub * 8 + j] = v;
       }
       float b = dba[k];
+      if constexpr (LPP == 8) b += __shfl_xor(b, 8, 64);
       b += __shfl_xor(b, 16, 64);
       b += __shfl_xor(b, 32, 64);
       if (lane == 0) dbred[wave * K + k] = b;
@@ -379,8 +389,24 @@ __global__ __launch_bounds__(256) void head_ce_reduce_kernel(const float* __rest
   }
 }
 
+// the instantiation for K in {4, 8} classes and Cin in {64, 128} channels (the entries have checked both)
+template <int MODE>
+auto hc_kernel(int K, int Cin) -> decltype(&head_ce_kernel<4, MODE, 128>) {
+  if (Cin == 128) return K == 4 ? head_ce_kernel<4, MODE, 128> : head_ce_kernel<8, MODE, 128>;
+  return K == 4 ? head_ce_kernel<4, MODE, 64> : head_ce_kernel<8, MODE, 64>;
+}
+
+bool hc_shape_ok(int Cin, int K) { return (Cin == 64 || Cin == 128) && (K == 4 || K == 8); }
+
+// one workgroup pass covers 4 waves x PPW pixels, PPW = 64 / (Cin / 8): 16 pixels at 128 channels, 32 at 64
+int hc_grid(long long M, int Cin) {
+  const long long per = 4 * (64 / (Cin / 8)), want = (M + per - 1) / per;
+  return (int)(want > HC_BLOCKS ? HC_BLOCKS : want);
+}
+
 }  // namespace
 
+// sized for Cin = 128; the 64-channel head uses the first K * 64 + K floats of each workgroup's partials
 extern "C" size_t lss_head_ce_workspace_bytes(int K) {
   if (K <= 0 || K > HC_MAXK) return 0;
   return (size_t)HC_BLOCKS * (K * 128 + K) * sizeof(float) + 2 * HC_BLOCKS * sizeof(float);
@@ -391,17 +417,14 @@ extern "C" int lss_head_ce_fwd(const void* y, const float* head_w, const float* 
                                float* loss, void* stream) {
   LSS_CHECK_PTR(y); LSS_CHECK_PTR(head_w); LSS_CHECK_PTR(head_b); LSS_CHECK_PTR(target); LSS_CHECK_PTR(class_w);
   LSS_CHECK_PTR(workspace); LSS_CHECK_PTR(sums); LSS_CHECK_PTR(loss);
-  if (M <= 0 || Cin != 128 || (K != 4 && K != 8)) return LSS_E_SHAPE;
+  if (M <= 0 || !hc_shape_ok(Cin, K)) return LSS_E_SHAPE;
   if ((reinterpret_cast<uintptr_t>(y) & 15) != 0) return LSS_E_ALIGN;
   hipStream_t st = lss_stream(stream);
-  const int grid = (int)((M + 15) / 16 > HC_BLOCKS ? HC_BLOCKS : (M + 15) / 16);
+  const int grid = hc_grid(M, Cin);
   const unsigned short* yp = reinterpret_cast<const unsigned short*>(y);
-  if (K == 4)
-    hipLaunchKernelGGL((head_ce_kernel<4, 0>), dim3(grid), dim3(256), 0, st, yp, head_w, head_b, target, class_w,
-                       M, nullptr, nullptr, workspace, nullptr, nullptr, nullptr, 0LL);
-  else
-    hipLaunchKernelGGL((head_ce_kernel<8, 0>), dim3(grid), dim3(256), 0, st, yp, head_w, head_b, target, class_w,
-                       M, nullptr, nullptr, workspace, nullptr, nullptr, nullptr, 0LL);
+  hipLaunchKernelGGL(hc_kernel<0>(K, Cin), dim3(grid), dim3(256), 0, st, yp, head_w, head_b, target, class_w, M,
+                     (const float*)nullptr, (const float*)nullptr, workspace, (unsigned short*)nullptr,
+                     (float*)nullptr, (float*)nullptr, 0LL);
   hipLaunchKernelGGL(weighted_ce_finalize_kernel, dim3(1), dim3(64), 0, st, workspace, grid, sums, loss);
   return lss_launch_status();
 }
@@ -413,42 +436,36 @@ extern "C" int lss_head_ce_bwd(const void* y, const float* head_w, const float* 
   LSS_CHECK_PTR(y); LSS_CHECK_PTR(head_w); LSS_CHECK_PTR(head_b); LSS_CHECK_PTR(target); LSS_CHECK_PTR(class_w);
   LSS_CHECK_PTR(sums); LSS_CHECK_PTR(grad_loss); LSS_CHECK_PTR(workspace); LSS_CHECK_PTR(dy);
   LSS_CHECK_PTR(d_head_w); LSS_CHECK_PTR(d_head_b);
-  if (M <= 0 || Cin != 128 || (K != 4 && K != 8)) return LSS_E_SHAPE;
+  if (M <= 0 || !hc_shape_ok(Cin, K)) return LSS_E_SHAPE;
   if (((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(dy)) & 15) != 0) return LSS_E_ALIGN;
   hipStream_t st = lss_stream(stream);
-  const int grid = (int)((M + 15) / 16 > HC_BLOCKS ? HC_BLOCKS : (M + 15) / 16);
+  const int grid = hc_grid(M, Cin);
   const unsigned short* yp = reinterpret_cast<const unsigned short*>(y);
   unsigned short* dyp = reinterpret_cast<unsigned short*>(dy);
-  if (K == 4)
-    hipLaunchKernelGGL((head_ce_kernel<4, 1>), dim3(grid), dim3(256), 0, st, yp, head_w, head_b, target, class_w, M,
-                       sums, grad_loss, nullptr, dyp, workspace, nullptr, 0LL);
-  else
-    hipLaunchKernelGGL((head_ce_kernel<8, 1>), dim3(grid), dim3(256), 0, st, yp, head_w, head_b, target, class_w, M,
-                       sums, grad_loss, nullptr, dyp, workspace, nullptr, 0LL);
-  const int n = K * 128 + K;
+  hipLaunchKernelGGL(hc_kernel<1>(K, Cin), dim3(grid), dim3(256), 0, st, yp, head_w, head_b, target, class_w, M, sums,
+                     grad_loss, (float*)nullptr, dyp, workspace, (float*)nullptr, 0LL);
+  const int n = K * Cin + K;
   hipLaunchKernelGGL(head_ce_reduce_kernel, dim3((n + 3) / 4), dim3(256), 0, st, workspace, grid, n, d_head_w,
-                     d_head_b, K * 128);
+                     d_head_b, K * Cin);
   return lss_launch_status();
 }
 
 // The 1x1 head alone (ref src/modules.py:115, up2[4] = nn.Conv2d(128, outC, 1)), forward and backward, for a
-// training-mode forward whose loss is computed by the caller: y (M, 128) bf16 NHWC rows -> logits (B, K, H, W) fp32
-// NCHW (M = B * HW); backward: grad_logits (B, K, H, W) fp32 -> dy (M, 128) bf16, d_head_w (K, 128), d_head_b (K),
+// training-mode forward whose loss is computed by the caller: y (M, Cin) bf16 NHWC rows, Cin = 64 or 128 -> logits
+// (B, K, H, W) fp32 NCHW (M = B * HW); backward: grad_logits (B, K, H, W) fp32 -> dy (M, Cin) bf16, d_head_w (K, Cin),
+// d_head_b (K),
 // fixed-order partial sums (bit-reproducible).  workspace: lss_head_ce_workspace_bytes(K).
 extern "C" int lss_head1x1_fwd(const void* y, const float* head_w, const float* head_b, long long M, long long HW,
                                int Cin, int K, float* logits, void* stream) {
   LSS_CHECK_PTR(y); LSS_CHECK_PTR(head_w); LSS_CHECK_PTR(head_b); LSS_CHECK_PTR(logits);
-  if (M <= 0 || HW <= 0 || M % HW != 0 || Cin != 128 || (K != 4 && K != 8)) return LSS_E_SHAPE;
+  if (M <= 0 || HW <= 0 || M % HW != 0 || !hc_shape_ok(Cin, K)) return LSS_E_SHAPE;
   if ((reinterpret_cast<uintptr_t>(y) & 15) != 0) return LSS_E_ALIGN;
-  const int grid = (int)((M + 15) / 16 > HC_BLOCKS ? HC_BLOCKS : (M + 15) / 16);
+  const int grid = hc_grid(M, Cin);
   const unsigned short* yp = reinterpret_cast<const unsigned short*>(y);
   hipStream_t st = lss_stream(stream);
-  if (K == 4)
-    hipLaunchKernelGGL((head_ce_kernel<4, 2>), dim3(grid), dim3(256), 0, st, yp, head_w, head_b, nullptr, nullptr, M,
-                       nullptr, nullptr, nullptr, nullptr, nullptr, logits, HW);
-  else
-    hipLaunchKernelGGL((head_ce_kernel<8, 2>), dim3(grid), dim3(256), 0, st, yp, head_w, head_b, nullptr, nullptr, M,
-                       nullptr, nullptr, nullptr, nullptr, nullptr, logits, HW);
+  hipLaunchKernelGGL(hc_kernel<2>(K, Cin), dim3(grid), dim3(256), 0, st, yp, head_w, head_b,
+                     (const long long*)nullptr, (const float*)nullptr, M, (const float*)nullptr,
+                     (const float*)nullptr, (float*)nullptr, (unsigned short*)nullptr, (float*)nullptr, logits, HW);
   return lss_launch_status();
 }
 
@@ -457,20 +474,17 @@ extern "C" int lss_head1x1_bwd(const void* y, const float* head_w, const float* 
                                float* d_head_b, void* stream) {
   LSS_CHECK_PTR(y); LSS_CHECK_PTR(head_w); LSS_CHECK_PTR(head_b); LSS_CHECK_PTR(grad_logits); LSS_CHECK_PTR(workspace);
   LSS_CHECK_PTR(dy); LSS_CHECK_PTR(d_head_w); LSS_CHECK_PTR(d_head_b);
-  if (M <= 0 || HW <= 0 || M % HW != 0 || Cin != 128 || (K != 4 && K != 8)) return LSS_E_SHAPE;
+  if (M <= 0 || HW <= 0 || M % HW != 0 || !hc_shape_ok(Cin, K)) return LSS_E_SHAPE;
   if (((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(dy)) & 15) != 0) return LSS_E_ALIGN;
-  const int grid = (int)((M + 15) / 16 > HC_BLOCKS ? HC_BLOCKS : (M + 15) / 16);
+  const int grid = hc_grid(M, Cin);
   const unsigned short* yp = reinterpret_cast<const unsigned short*>(y);
   hipStream_t st = lss_stream(stream);
   float* gl = const_cast<float*>(grad_logits);  // read only (the kernel's logits pointer serves both modes)
-  if (K == 4)
-    hipLaunchKernelGGL((head_ce_kernel<4, 3>), dim3(grid), dim3(256), 0, st, yp, head_w, head_b, nullptr, nullptr, M,
-                       nullptr, nullptr, nullptr, reinterpret_cast<unsigned short*>(dy), workspace, gl, HW);
-  else
-    hipLaunchKernelGGL((head_ce_kernel<8, 3>), dim3(grid), dim3(256), 0, st, yp, head_w, head_b, nullptr, nullptr, M,
-                       nullptr, nullptr, nullptr, reinterpret_cast<unsigned short*>(dy), workspace, gl, HW);
-  const int n = K * 128 + K;
+  hipLaunchKernelGGL(hc_kernel<3>(K, Cin), dim3(grid), dim3(256), 0, st, yp, head_w, head_b,
+                     (const long long*)nullptr, (const float*)nullptr, M, (const float*)nullptr,
+                     (const float*)nullptr, (float*)nullptr, reinterpret_cast<unsigned short*>(dy), workspace, gl, HW);
+  const int n = K * Cin + K;
   hipLaunchKernelGGL(head_ce_reduce_kernel, dim3((n + 3) / 4), dim3(256), 0, st, workspace, grid, n, d_head_w,
-                     d_head_b, K * 128);
+                     d_head_b, K * Cin);
   return lss_launch_status();
 }

@@ -25,11 +25,12 @@ from torch import nn
 from torch.autograd.function import once_differentiable
 from torch.nn import functional as F
 
-from . import ops
+from . import modules, ops
 from .heads import SceneUnder
 from .model_BEV_TXT import _LiftSplatMixin, _histogram_guard
 from .modules import _FoldedConv, _PRECISIONS, _needs_autograd, _to_nhwc, default_precision
 from .tools import QuickCumsum, gen_dx_bx  # noqa: F401  (reference's import surface)
+from .tools import head_1x1, head_weighted_cross_entropy, weighted_cross_entropy
 from .transformer_modules import LightweightBEVTransformer
 
 
@@ -38,6 +39,11 @@ from .transformer_modules import LightweightBEVTransformer
 # backward on K7 + K10; the lifted (B,N,D,fH,fW,C) tensor exists in neither direction.
 # ----------------------------------------------------------------------------
 LIFT_CALLS = {"native": 0, "composition": 0}  # which form `get_voxels` took when it had to be differentiable
+# which form BEVEncoderTransformer.forward / forward_loss took when it had to be differentiable: "native" = the 1x1
+# compress unit, the two biased 3x3 units and the 64-channel head on the HIP kernels (bf16 autocast)
+BEV_ENCODER_CALLS = {"native": 0, "composition": 0}
+# LSS_BEV_ENCODER_NATIVE unset: see DESIGN.md 4b for the measurement that decides this
+_BEV_ENCODER_NATIVE_DEFAULT = "1"
 
 
 class _HeadProjFn(torch.autograd.Function):
@@ -225,7 +231,10 @@ class CamEncodeV2(nn.Module):
 
 
 class BEVEncoderTransformer(nn.Module):
-    """1x1 compress conv-BN-ReLU -> deformable-attention transformer layer -> 3x3/3x3/1x1 seg head."""
+    """1x1 compress conv-BN-ReLU -> deformable-attention transformer layer -> 3x3/3x3/1x1 seg head.
+    Training under bf16 autocast on the GPU: the convs run on the HIP units too (`_train_native_ok`; the 1x1 unit,
+    two `_ConvBNActFn` units with the conv bias absorbed by the train-mode BatchNorm, the 64-channel head kernels);
+    LSS_BEV_ENCODER_NATIVE=0 and every other case take the torch composition."""
 
     def __init__(self, in_channels, out_channels=4, precision=None):
         super().__init__()
@@ -259,14 +268,56 @@ class BEVEncoderTransformer(nn.Module):
         seg = ops.conv2d_nhwc(s, w, (1, 1), 1, 0, None, shift, None, False, dt=dt, out_f32=True)
         return seg.permute(0, 3, 1, 2).contiguous(), refined
 
+    def _train_native_ok(self, x):
+        """Does this differentiable call take the native route?  (The switch LSS_BEV_ENCODER_NATIVE, a GPU input under
+        bf16 autocast - `modules._native_training()` -, the reference's widths 256 / 128 / 64 with 4 or 8 classes and
+        a compress width the 1x1 unit takes, and the three BatchNorms in training mode.)"""
+        if os.environ.get("LSS_BEV_ENCODER_NATIVE", _BEV_ENCODER_NATIVE_DEFAULT) == "0":
+            return False
+        if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4):
+            return False
+        cc, cb = self.compress[0], self.compress[1]
+        s0, b0, s1, b1, head = (self.seg_head[i] for i in (0, 1, 3, 4, 6))
+        if (cc.out_channels, s0.in_channels, s0.out_channels, s1.in_channels, s1.out_channels) != (256, 256, 128, 128, 64):
+            return False
+        if (head.in_channels != 64 or head.out_channels not in (4, 8) or head.kernel_size != (1, 1)
+                or head.stride != (1, 1) or head.bias is None):
+            return False
+        return (modules._conv1x1_unit_ok(cc, cb, x)
+                and all(modules._biased_conv3x3_unit_ok(c, b, True, c.in_channels) for c, b in ((s0, b0), (s1, b1))))
+
+    def _train_native_features(self, x):
+        """compress unit -> transformer (unchanged) -> the two 3x3 units; returns (the 64-channel activation the head
+        reads, refined), both logical NCHW views of NHWC memory."""
+        h = modules._train_conv1x1_bn_act(self.compress[0], self.compress[1], x)
+        refined = self.transformer(h)
+        s = modules._train_conv_bn_act(self.seg_head[0], self.seg_head[1], refined, relu=True)
+        return modules._train_conv_bn_act(self.seg_head[3], self.seg_head[4], s, relu=True), refined
+
     def forward(self, x):
         """(B, C_in, H, W) -> seg (B, out_C, H, W), refined (B, 256, H, W)."""
         if _needs_autograd(self, x):
+            if self._train_native_ok(x):
+                BEV_ENCODER_CALLS["native"] += 1
+                s, refined = self._train_native_features(x)
+                return head_1x1(s, self.seg_head[6]).float(), refined
+            BEV_ENCODER_CALLS["composition"] += 1
             refined = self.transformer(self.compress(x))
             return self.seg_head(refined), refined
         dt = _dt(self.precision)
         seg, refined = self.forward_nhwc(_to_nhwc(x, dt), dt)
         return seg, ops.nhwc_to_nchw(refined, dt)
+
+    def forward_loss(self, x, target, class_weight):
+        """(nn.CrossEntropyLoss(weight=class_weight)(seg, target), refined) for `seg, refined = self(x)`: the BEV term
+        of MultiTaskLoss (ref train_vovnet_transformer.py:83-84, 107), the counterpart of `LSS.forward_loss`.  On the
+        native route the classifier and the loss are one kernel per direction and the logits never reach HBM."""
+        if _needs_autograd(self, x) and self._train_native_ok(x):
+            BEV_ENCODER_CALLS["native"] += 1
+            s, refined = self._train_native_features(x)
+            return head_weighted_cross_entropy(s, self.seg_head[6], target, class_weight), refined
+        seg, refined = self(x)
+        return weighted_cross_entropy(seg.float(), target, class_weight), refined
 
 
 # ----------------------------------------------------------------------------

@@ -479,6 +479,8 @@ def _train_conv_bn_act(conv, bn, x1, relu, residual=None, up=None, x2=None):
     """act(bn(conv(x)) (+ residual)) on the autograd path, x = x1 or cat([x2, up(x1)]).  One fused
     HIP node when the shapes allow and the caller asked for bf16 math; otherwise composed from
     the separate (native or library) pieces."""
+    if conv.bias is not None:
+        return _train_biased_conv_bn_act(conv, bn, x1, relu, residual, up, x2)
     c2 = 0 if x2 is None else x2.shape[1]
     scale = 1 if up is None else int(up.scale_factor)
     if (x1.is_cuda and _native_training() and _bn_native_ok(bn, True) and conv.kernel_size == (3, 3)
@@ -512,6 +514,98 @@ def _train_bn_act(bn, z, relu, residual=None):
     return F.relu(y) if relu else y
 
 
+class _AbsorbedBiasFn(torch.autograd.Function):
+    """Identity on y that ties a conv bias into the graph when a train-mode BatchNorm directly behind the conv
+    removes it: BN(conv(x) + b) = BN(conv(x)), so the units run bias-free and the exact gradient of b is zero.  The
+    backward hands the optimizer that zeros tensor (what the torch composition leaves there up to rounding) instead of
+    no gradient at all, which ClipAdam would treat differently."""
+
+    @staticmethod
+    def forward(ctx, y, bias):
+        ctx.meta = (bias.shape, bias.dtype)
+        return y.view_as(y)
+
+    @staticmethod
+    def backward(ctx, gy):
+        shape, dtype = ctx.meta
+        return gy, torch.zeros(shape, dtype=dtype, device=gy.device)
+
+
+def _absorb_conv_bias(conv, bn, y):
+    """After a native unit ran `conv` bias-free into the train-mode `bn`: the kernels wrote running_mean =
+    (1 - m) rm + m mean(conv(x)); nn.BatchNorm2d would hold m b more (the batch mean of conv(x) + b).  One in-place
+    add on the current stream (graph-safe); running_var, the saved statistics, y and every other gradient are those
+    of the biased conv already."""
+    with torch.no_grad():
+        bn.running_mean.add_(conv.bias.detach().to(bn.running_mean.dtype), alpha=float(bn.momentum))
+    return _AbsorbedBiasFn.apply(y, conv.bias)
+
+
+def _biased_conv3x3_unit_ok(conv, bn, is_cuda, c_in):
+    """Does a 3x3 conv WITH bias + BatchNorm on a c_in-channel input take the bias-free native kernels?  The conditions of the
+    bias-free units, and a BatchNorm in training mode that `_bn_native_ok` accepts (an eval-mode BatchNorm does not
+    remove the bias)."""
+    return (is_cuda and _native_training() and _bn_native_ok(bn, True) and conv.kernel_size == (3, 3)
+            and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1
+            and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0 and c_in == conv.in_channels)
+
+
+def _train_biased_conv_bn_act(conv, bn, x1, relu, residual=None, up=None, x2=None):
+    """`_train_conv_bn_act` for a conv with a bias (every nn.Conv2d of the vovnet reference is built with the default
+    one, ref src/model_vovnet_transformer.py:131-143).  Plain 3x3 / stride 1 / pad 1 in front of a train-mode
+    BatchNorm: the bias-free fused node, or the unfused native pair where the fused one does not apply (synchronised
+    statistics, non-fp32 weights), then `_absorb_conv_bias`.  Everything else is the composition it always was."""
+    if up is None and x2 is None and _biased_conv3x3_unit_ok(conv, bn, x1.is_cuda, x1.shape[1]):
+        if "_lss_sync" not in bn.__dict__ and conv.weight.dtype == torch.float32:
+            y = _ConvBNActFn.apply(x1, None, conv.weight, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var,
+                                   float(bn.momentum), float(bn.eps), bool(relu), 1)
+            _count_batch(bn)
+        else:
+            y = _train_bn_act(bn, _train_conv(conv, x1, bias_into_bn=True), relu, residual)
+        return _absorb_conv_bias(conv, bn, y)
+    z = _train_conv(conv, x1) if up is None else _train_up_conv(conv, up, x1, x2)
+    return _train_bn_act(bn, z, relu, residual)
+
+
+def _conv1x1_unit_ok(conv, bn, x):
+    """Does `conv1x1 -> BatchNorm(train) -> ReLU` on x (B, C_in, H, W) take the native 1x1 unit?  (GPU, bf16 autocast,
+    a plain 1x1 conv whose token GEMM `ops.linear_wgrad_ok` accepts - widths that are multiples of 64 in 64..1024 -
+    and a train-mode BatchNorm `_bn_native_ok` accepts.)"""
+    return (x.is_cuda and x.dim() == 4 and _native_training() and _bn_native_ok(bn, True)
+            and "_lss_sync" not in bn.__dict__ and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
+            and conv.padding == (0, 0) and conv.groups == 1 and conv.weight.dtype == torch.float32
+            and x.shape[1] == conv.in_channels
+            and ops.linear_wgrad_ok(x.shape[0] * x.shape[2] * x.shape[3], conv.out_channels, conv.in_channels))
+
+
+_zero_bias = {}
+
+
+def _train_conv1x1_bn_act(conv, bn, x, relu=True):
+    """act(bn(conv1x1(x))) over NHWC bf16 token rows as two native nodes (ref src/model_vovnet_transformer.py:131-132,
+    `compress`): the GEMM node of the transformer's linears (forward and input gradient on the MFMA GEMM, weight
+    gradient on K11) with a zero bias, `_BNActFn`, and the conv's own bias absorbed by the BatchNorm
+    (`_absorb_conv_bias`).  At most one layout copy: x -> (B, H, W, C) bf16 in one pass unless it already is; z and y
+    are handed on as logical NCHW views of NHWC memory.  The caller has checked `_conv1x1_unit_ok`."""
+    from .transformer_modules import _LinearFn  # (transformer_modules imports this module)
+    xn = x.permute(0, 2, 3, 1)
+    if xn.dtype != torch.bfloat16 or not xn.is_contiguous():
+        xn = torch.empty(xn.shape, dtype=torch.bfloat16, device=x.device).copy_(xn)  # cast + transpose, one kernel
+    Cout = conv.out_channels
+    key = (str(x.device), Cout)
+    zb = _zero_bias.get(key)
+    if zb is None:
+        if x_is_capturing():
+            raise RuntimeError("the 1x1 unit's zero bias for %s is not built yet and a stream capture is active: run "
+                               "one eager training step before capturing" % (key,))
+        zb = _zero_bias[key] = torch.zeros(Cout, dtype=torch.float32, device=x.device)
+    z = _LinearFn.apply(xn, conv.weight.view(Cout, conv.in_channels), zb)      # (B, H, W, Cout) bf16
+    y = _BNActFn.apply(z.permute(0, 3, 1, 2), bn.weight, bn.bias, None, bn.running_mean, bn.running_var,
+                       float(bn.momentum), float(bn.eps), bool(relu))
+    _count_batch(bn)
+    return y if conv.bias is None else _absorb_conv_bias(conv, bn, y)
+
+
 def _native_training():
     """Training convs go to the HIP kernels when the caller asked for bf16 math (bf16 autocast);
     plain fp32 training keeps torch's fp32 convolutions.  LSS_TRAIN_NATIVE=0 disables."""
@@ -530,10 +624,14 @@ def _train_up_conv(conv, up, x1, x2):
     return _train_conv(conv, x1 if x2 is None else torch.cat([x2, x1], dim=1))
 
 
-def _train_conv(conv, x):
+def _train_conv(conv, x, bias_into_bn=False):
     """conv(x) on the autograd path: the 3x3/s1/p1 shapes (95 % of BevEncode's FLOPs) run
     forward and backward on the HIP kernels, everything else on the library.  out_channels % 64 == 0 (here, in
-    _train_up_conv and in _train_conv_bn_act): the input-gradient conv reads the layer's Cout in K blocks of 64."""
+    _train_up_conv and in _train_conv_bn_act): the input-gradient conv reads the layer's Cout in K blocks of 64.
+    A conv with a bias is the library's, unless the caller (`_train_biased_conv_bn_act`, which has checked
+    `_biased_conv3x3_unit_ok`) feeds a train-mode BatchNorm that absorbs the bias: then conv(x) WITHOUT it."""
+    if conv.bias is not None:
+        return _Conv3x3Fn.apply(x, conv.weight) if bias_into_bn else conv(x)
     if (x.is_cuda and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
             and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
             and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0 and _native_training()):

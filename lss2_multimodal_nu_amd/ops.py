@@ -1517,10 +1517,19 @@ def _head_ce_workspace(K, device):
     return ws
 
 
-def head_ce_fwd(y, head_w, head_b, target, class_w):
-    """Fused 1x1 head + weighted cross-entropy.  y (..., 128) contiguous bf16 NHWC rows; head_w (K, 128) fp32;
-    head_b (K); target int64 with y's leading shape; class_w (K).  Returns (loss 0-d tensor, sums (2,))."""
+def _head_shape(head_w):
     K, Cin = head_w.shape
+    if Cin not in (64, 128) or K not in (4, 8):
+        raise ValueError("the head kernels take 64 or 128 input channels and 4 or 8 classes, got head_w %s"
+                         % (tuple(head_w.shape),))
+    return K, Cin
+
+
+def head_ce_fwd(y, head_w, head_b, target, class_w):
+    """Fused 1x1 head + weighted cross-entropy.  y (..., Cin) contiguous bf16 NHWC rows, Cin = 64 or 128; head_w
+    (K, Cin) fp32, K = 4 or 8; head_b (K); target int64 with y's leading shape; class_w (K).  Returns (loss 0-d
+    tensor, sums (2,))."""
+    K, Cin = _head_shape(head_w)
     if y.dtype != torch.bfloat16 or not y.is_contiguous() or y.shape[-1] != Cin:
         raise ValueError("y must be contiguous bf16 rows of %d channels" % Cin)
     _f32c(head_w, "head_w", (K, Cin))
@@ -1539,7 +1548,7 @@ def head_ce_fwd(y, head_w, head_b, target, class_w):
 
 def head_ce_bwd(y, head_w, head_b, target, class_w, sums, grad_loss):
     """Backward of head_ce_fwd: returns (dy bf16 like y, d_head_w (K, Cin) fp32, d_head_b (K) fp32)."""
-    K, Cin = head_w.shape
+    K, Cin = _head_shape(head_w)
     M = y.numel() // Cin
     dy = torch.empty_like(y)
     dw = torch.empty(K, Cin, dtype=torch.float32, device=y.device)
@@ -1553,8 +1562,9 @@ def head_ce_bwd(y, head_w, head_b, target, class_w, sums, grad_loss):
 
 
 def head1x1_fwd(y, head_w, head_b):
-    """The 1x1 head alone: y (B, H, W, 128) contiguous bf16 -> logits (B, K, H, W) fp32 NCHW (lss_head1x1_fwd)."""
-    K, Cin = head_w.shape
+    """The 1x1 head alone: y (B, H, W, Cin) contiguous bf16, Cin = 64 or 128 -> logits (B, K, H, W) fp32 NCHW, K = 4 or
+    8 (lss_head1x1_fwd)."""
+    K, Cin = _head_shape(head_w)
     if y.dtype != torch.bfloat16 or not y.is_contiguous() or y.dim() != 4 or y.shape[-1] != Cin:
         raise ValueError("y must be a contiguous (B, H, W, %d) bf16 tensor" % Cin)
     _f32c(head_w, "head_w", (K, Cin))
@@ -1569,7 +1579,7 @@ def head1x1_fwd(y, head_w, head_b):
 
 def head1x1_bwd(y, head_w, head_b, grad_logits):
     """Backward of head1x1_fwd: grad_logits (B, K, H, W) fp32 contiguous -> (dy bf16 like y, d_head_w (K, Cin), d_head_b (K))."""
-    K, Cin = head_w.shape
+    K, Cin = _head_shape(head_w)
     B, H, W, _ = y.shape
     _f32c(grad_logits, "grad_logits", (B, K, H, W))
     dy = torch.empty_like(y)

@@ -126,9 +126,10 @@ class _HeadCEFn(torch.autograd.Function):
 
 
 class _Head1x1Fn(torch.autograd.Function):
-    """`head(y)` for the 1x1 head `nn.Conv2d(128, K, 1)` (ref src/modules.py:115) on the HIP kernels, both ways: the
+    """`head(y)` for the 1x1 head `nn.Conv2d(128, K, 1)` (ref src/modules.py:115; with 64 channels the `seg_head[6]` of
+    BEVEncoderTransformer, ref src/model_vovnet_transformer.py:143) on the HIP kernels, both ways: the
     logits of a training-mode `model(x)` whose loss the caller computes (ref train.py:52, 62).  y: logical
-    (B, 128, H, W) tensor whose memory is NHWC bf16; returns (B, K, H, W) fp32.  Replaces torch's convolution there
+    (B, Cin, H, W) tensor whose memory is NHWC bf16; returns (B, K, H, W) fp32.  Replaces torch's convolution there
     because the library's backward is not safe inside a HIP graph: round 3's data-parallel graph step went wrong in
     exactly this op."""
 
@@ -155,23 +156,23 @@ class _Head1x1Fn(torch.autograd.Function):
 
 
 def head_1x1(y, head):
-    """head(y) on the autograd path: the HIP head kernels when the shapes fit (128 input channels, 4 or 8 classes, a
-    bf16 activation on the GPU), torch's convolution otherwise (fp32 parity mode, or LSS_TRAIN_NATIVE=0 - the
+    """head(y) on the autograd path: the HIP head kernels when the shapes fit (64 or 128 input channels, 4 or 8 classes,
+    a bf16 activation on the GPU), torch's convolution otherwise (fp32 parity mode, or LSS_TRAIN_NATIVE=0 - the
     library comparison leg of the tests; NOT safe inside a HIP graph)."""
-    if (os.environ.get("LSS_TRAIN_NATIVE", "1") != "0" and y.is_cuda and y.dtype == torch.bfloat16 and y.dim() == 4 and y.shape[1] == 128 and head.kernel_size == (1, 1)
+    if (os.environ.get("LSS_TRAIN_NATIVE", "1") != "0" and y.is_cuda and y.dtype == torch.bfloat16 and y.dim() == 4 and y.shape[1] in (64, 128) and head.kernel_size == (1, 1)
             and head.stride == (1, 1) and head.bias is not None and head.out_channels in (4, 8)):
         return _Head1x1Fn.apply(y, head.weight, head.bias)
     return head(y)
 
 
 def head_weighted_cross_entropy(y, head, ytgt, weight):
-    """nn.CrossEntropyLoss(weight=weight)(head(y), ytgt) for a 1x1 `head` = nn.Conv2d(128, K, 1) applied to the
-    (B, 128, H, W) activation y: fused into one HIP kernel per direction on the GPU when the shapes
-    fit (128 input channels, 4 or 8 classes) AND y is already bf16 (autocast / bf16 precision: the kernel reads y
+    """nn.CrossEntropyLoss(weight=weight)(head(y), ytgt) for a 1x1 `head` = nn.Conv2d(Cin, K, 1) applied to the
+    (B, Cin, H, W) activation y: fused into one HIP kernel per direction on the GPU when the shapes
+    fit (64 or 128 input channels, 4 or 8 classes) AND y is already bf16 (autocast / bf16 precision: the kernel reads y
     as bf16 and returns dy rounded to bf16, which for a bf16 y loses nothing).  An fp32 y (parity mode) takes the two
     separate ops, so that `forward_loss` equals `forward` + `SimpleLoss` to fp32 accuracy, loss and gradients."""
-    if (y.is_cuda and y.dtype == torch.bfloat16 and y.dim() == 4 and y.shape[1] == 128 and head.kernel_size == (1, 1)
-            and head.bias is not None
+    if (y.is_cuda and y.dtype == torch.bfloat16 and y.dim() == 4 and y.shape[1] in (64, 128)
+            and head.kernel_size == (1, 1) and head.bias is not None
             and head.out_channels in (4, 8) and ytgt.dtype == torch.int64
             and tuple(ytgt.shape) == (y.shape[0], y.shape[2], y.shape[3])):
         return _HeadCEFn.apply(y, head.weight, head.bias, ytgt, weight)
