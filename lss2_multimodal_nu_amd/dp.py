@@ -349,14 +349,13 @@ class GraphedTrainStep:
     CHECK_REPLAYS = 3  # replays of the self-check after capture (ordinary steps on the capture inputs)
 
     def __init__(self, model, bucket, opt, loss_fn, feats, calib, clip=5.0, warmup=3):
-        from . import modules
         from .data import CalibrationPack, prepare_calibration
         if warmup < 1:
             raise ValueError("GraphedTrainStep needs at least one eager warm-up step before the capture (first-call "
-                             "work - kernel attributes, index tables, optimizer state - must not happen inside it)")
+                             "work - kernel attributes, the stride-2 weight gradients' gather index, optimizer state - "
+                             "must not happen inside it)")
         if not feats.is_cuda:
             raise ValueError("GraphedTrainStep: features must be on the GPU")
-        modules.warm_s2_tables(feats.device)  # (pageable H2D copies: refused inside a capture)
         self._prepare = prepare_calibration
         self.feats = feats.detach().clone()
         host = calib if isinstance(calib, CalibrationPack) else prepare_calibration(*calib)

@@ -9,12 +9,23 @@ the inference arithmetic runs in the HIP kernels of csrc/ (conv_mfma.hip and, fo
 the three big 3x3 layers at the sizes it takes, conv_ring.hip; depthnet.hip) through
 the C ABI - there is no eager fallback for it.
 
-Training mode under bf16 autocast: every `conv3x3/s1 -> BatchNorm(train) -> (+residual)
--> ReLU` unit (95 % of BevEncode's FLOPs, the fused upsample + concat input of `Up`
-included) is ONE autograd node on the HIP kernels (conv forward / dgrad / wgrad,
-batch-statistics BN forward / backward: conv_grad.hip, bn_train.hip); the 7x7/2 stem,
-the stride-2 and 1x1 convs and plain-fp32 training run the same parameters through
-torch's GPU ops.  See DESIGN.md section 9.
+Training mode under bf16 autocast runs the same parameters through autograd nodes on the
+HIP kernels, chosen by `_train_conv_bn_act` / `_train_conv` /
+`_train_bn_act`:
+  - `conv3x3/s1 -> BatchNorm(train) -> (+residual) -> ReLU` (95 % of BevEncode's FLOPs, the
+    fused upsample + concat input of `Up` included): ONE node, `_ConvBNActFn` (conv forward /
+    dgrad / wgrad, batch-statistics BN forward / backward: conv_grad.hip, conv_wgrad.hip,
+    bn_train.hip).  A conv bias directly in front of the BatchNorm is absorbed by it.
+  - where only the fusion does not apply (statistics synchronised over ranks, non-fp32
+    weights, a BatchNorm the kernels do not take): `_Conv3x3Fn`, then `_BNActFn` /
+    `_SyncBNActFn` or the library's BatchNorm.
+  - the 7x7/2 stem, the 3x3/2 convs and the 1x1/2 shortcuts: `_ConvS2Fn` over phase planes,
+    then `_BNActFn`.
+  - `conv1x1 -> BatchNorm(train) -> ReLU` (the vovnet encoder's `compress`): the token GEMM
+    node of the transformer's linears, then `_BNActFn` (`_train_conv1x1_bn_act`).
+`_conv3x3_native_ok` is the one guard of the 3x3 kernels.  What the guards turn down
+(channel counts that are no multiple of 64, dilated or grouped convs, a conv bias without a
+train-mode BatchNorm behind it) and all plain-fp32 training go through torch's GPU ops.
 """
 import os
 
@@ -61,38 +72,59 @@ def _needs_autograd(module, *inputs):
     return False
 
 
+def _nhwc_bf16(t):
+    """Logical (B,C,H,W) tensor -> the contiguous bf16 NHWC operand of the kernels (no copy when it already is one)."""
+    t = t.permute(0, 2, 3, 1)
+    if t.dtype != torch.bfloat16:
+        t = t.to(torch.bfloat16)
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _nchw_as(t, dtype):
+    """The inverse for a result or gradient of the kernels: NHWC -> logical (B,C,H,W) view in `dtype`; None stays None."""
+    if t is None:
+        return None
+    t = t.permute(0, 3, 1, 2)
+    return t if t.dtype == dtype else t.to(dtype)
+
+
 class _Conv3x3Fn(torch.autograd.Function):
-    """Bias-free 3x3 / stride 1 / pad 1 conv with BOTH directions on the HIP kernels: forward = K8,
-    input gradient = K8 on the flipped/transposed weight pack, weight gradient = split-K MFMA GEMM
-    over channel-major copies (csrc/conv_grad.hip).  Takes / returns logical (B,C,H,W) tensors; the
-    arithmetic is bf16 NHWC with fp32 accumulation, the weight gradient fp32."""
+    """Bias-free 3x3 / stride 1 / pad 1 conv of x1, or of cat([x2, bilinear_align_corners(x1, up)]) with the upsample
+    and the concat fused into the conv's operand gather (neither tensor exists), with ALL directions on the HIP
+    kernels: forward = K8, input gradient = K8 on the flipped/transposed weight pack, weight gradient = split-K MFMA
+    GEMM over channel-major copies (csrc/conv_grad.hip).  Behind an upsample or a concat the backward adds the
+    upsample's adjoint as a gather kernel and re-materialises the concatenated input in bf16 for the weight-gradient
+    GEMM only.  Takes / returns logical (B,C,H,W) tensors (x2 may be None); the arithmetic is bf16 NHWC with fp32
+    accumulation, the weight gradient fp32.  The weight is packed per call."""
 
     @staticmethod
-    def forward(ctx, x, weight):
-        xn = x.permute(0, 2, 3, 1)
-        if xn.dtype != torch.bfloat16:
-            xn = xn.to(torch.bfloat16)
-        xn = xn.contiguous()  # no copy when x is already channels_last
+    def forward(ctx, x1, x2, weight, up):
+        x1n = _nhwc_bf16(x1)
+        x2n = None if x2 is None else _nhwc_bf16(x2)
         wp = ops.pack_conv_weight(weight.detach().float().contiguous(), ops.DT_BF16)
-        y = ops.conv2d_nhwc(xn, wp, (3, 3), 1, 1, tag="conv2d_train_fwd")
-        ctx.save_for_backward(xn, weight)
-        ctx.x_dtype = x.dtype
+        y = ops.conv2d_nhwc(x1n, wp, (3, 3), 1, 1, x2=x2n, up=up, tag="conv2d_train_fwd")
+        ctx.save_for_backward(x1n, x2n, weight)
+        ctx.cfg = (up, x1.dtype, None if x2 is None else x2.dtype)
         return y.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, gy):
-        xn, weight = ctx.saved_tensors
-        gyn = gy.permute(0, 2, 3, 1)
-        if gyn.dtype != torch.bfloat16:
-            gyn = gyn.to(torch.bfloat16)
-        gyn = gyn.contiguous()
-        gx = gw = None
-        if ctx.needs_input_grad[0]:
+        x1n, x2n, weight = ctx.saved_tensors
+        up, dt1, dt2 = ctx.cfg
+        plain = up == 1 and x2n is None   # the conv reads x1 itself: no adjoint, nothing to re-materialise
+        C2 = 0 if x2n is None else x2n.shape[3]
+        gyn = _nhwc_bf16(gy)
+        g1 = g2 = gw = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
             wd = ops.pack_conv_weight_dgrad(weight.detach().float().contiguous(), ops.DT_BF16)
-            gx = ops.conv2d_nhwc(gyn, wd, (3, 3), 1, 1, tag="conv2d_dgrad").permute(0, 3, 1, 2).to(ctx.x_dtype)
-        if ctx.needs_input_grad[1]:
-            gw = ops.conv3x3_wgrad(xn, gyn).to(weight.dtype)
-        return gx, gw
+            gcat = ops.conv2d_nhwc(gyn, wd, (3, 3), 1, 1, tag="conv2d_dgrad")  # (B, H*up, W*up, C2+Cx)
+            if ctx.needs_input_grad[0]:
+                g1 = _nchw_as(gcat if plain else ops.upsample_bwd_nhwc(gcat, C2, x1n.shape[3], up), dt1)
+            if ctx.needs_input_grad[1]:
+                g2 = _nchw_as(gcat[..., :C2], dt2)
+        if ctx.needs_input_grad[2]:
+            gw = ops.conv3x3_wgrad(x1n if plain else ops.upsample_cat_nhwc(x1n, x2n, up), gyn).to(weight.dtype)
+        return g1, g2, gw, None
 
 
 def conv_s2_backward_gemm(g, x, weight, pad, need_x=True, need_w=True):
@@ -118,26 +150,6 @@ def conv_s2_backward_gemm(g, x, weight, pad, need_x=True, need_w=True):
     return gx, gw
 
 
-_s2_tap_index = {}
-
-
-def _s2_tables(device, K):
-    """(phase, tap) index tensors of a K x K / stride-2 kernel on `device`: kernel row k reads input row
-    2 oy + k - K // 2 = 2 (oy + d) + p, i.e. phase p and tap index t = d - d_min.  Building them is a pageable
-    host-to-device copy, which a stream capture refuses: `warm_s2_tables` builds them ahead of any capture
-    (dp.GraphedTrainStep calls it; BevEncode does when it is moved to a device)."""
-    key = (str(device), K)
-    idx = _s2_tap_index.get(key)
-    if idx is None:
-        if torch.device(device).type == "cuda" and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("stride-2 tap tables for %s are not built yet and a stream capture is active: call "
-                               "modules.warm_s2_tables(device) before capturing" % (device,))
-        ds = [(k - K // 2) // 2 for k in range(K)]
-        idx = _s2_tap_index[key] = (torch.tensor([(k - K // 2) % 2 for k in range(K)], device=device),
-                                    torch.tensor([d - min(ds) for d in ds], device=device))
-    return idx
-
-
 _s2_gather_index = {}
 
 
@@ -152,9 +164,10 @@ def _s2_wgrad_gather(g6, K):
     if idx is None:
         if g6.is_cuda and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("stride-2 gather index %s is not built yet and a stream capture is active: run one eager "
-                               "training step (or modules.warm_s2_tables) before capturing" % (key,))
-        ph = torch.tensor([(k - K // 2) % 2 for k in range(K)])
+                               "training step before capturing" % (key,))
+        # kernel row k reads input row 2 oy + k - K // 2 = 2 (oy + d) + p: phase p, tap index d - d_min
         ds = [(k - K // 2) // 2 for k in range(K)]
+        ph = torch.tensor([(k - K // 2) % 2 for k in range(K)])
         tp = torch.tensor([d - min(ds) for d in ds])
         co = torch.arange(Co).view(Co, 1, 1, 1)
         ci = torch.arange(C).view(1, C, 1, 1)
@@ -162,11 +175,6 @@ def _s2_wgrad_gather(g6, K):
         flat = ((((co * 2 + ph[ky]) * 2 + ph[kx]) * C + ci) * T + tp[ky]) * T + tp[kx]
         idx = _s2_gather_index[key] = flat.reshape(-1).to(g6.device)
     return g6.reshape(-1).index_select(0, idx).view(Co, C, K, K)
-
-
-def warm_s2_tables(device):
-    for K in (1, 3, 7):
-        _s2_tables(device, K)
 
 
 def conv_s2_wgrad_phase_planes(xn, gyn, K):
@@ -179,7 +187,6 @@ def conv_s2_wgrad_phase_planes(xn, gyn, K):
     B, H, W, C = xn.shape
     Co = gyn.shape[3]
     xs = xn.view(B, H // 2, 2, W // 2, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(B, H // 2, W // 2, 4 * C)
-    ph, tp = _s2_tables(xn.device, K)
     if K == 7:  # the stem: taps d in {-2 .. 1} -> the 4x4-tap form of K9w (two launches of eight consumer waves)
         return _s2_wgrad_gather(ops.conv4x4_wgrad(xs, gyn).view(Co, 2, 2, C, 4, 4), K)
     g6 = ops.conv3x3_wgrad(xs, gyn).view(Co, 2, 2, C, 3, 3)   # [co][py][px][ci][ty][tx], tap t = d + 1
@@ -227,10 +234,7 @@ class _ConvS2Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight, pad):
-        xn = x.permute(0, 2, 3, 1)
-        if xn.dtype != torch.bfloat16:
-            xn = xn.to(torch.bfloat16)
-        xn = xn.contiguous()  # no copy when x is already channels_last bf16
+        xn = _nhwc_bf16(x)
         w32 = weight.detach().float().contiguous()
         K = weight.shape[2]
         wp = (ops.prepacked(w32, ("s2d", pad), lambda w: ops.pack_conv_weight_s2d(w, pad)) if K > 1 else
@@ -252,12 +256,12 @@ class _ConvS2Fn(torch.autograd.Function):
             # 3x3 / 2 and 1x1 / 2: K9w over phase planes; the 7x7 / 2 stem (taps dy in {-2 .. 1}): im2col + GEMM
             K = weight.shape[2]
             if _s2_wgrad_native_ok(xn, weight.shape[0], K):
-                gw = conv_s2_wgrad_phase_planes(xn, g.permute(0, 2, 3, 1).contiguous(), K)
+                gw = conv_s2_wgrad_phase_planes(xn, _nhwc_bf16(g), K)
             else:
                 _, gw = conv_s2_backward_gemm(g.contiguous(), x, weight.detach(), pad, need_x=False)
         if ctx.needs_input_grad[0]:
             if _s2_dgrad_native_ok(xn, weight.shape[0], weight.shape[2]):
-                gx = conv_s2_dgrad_phase_planes(g.permute(0, 2, 3, 1).contiguous(), weight, pad, xn.shape[1],
+                gx = conv_s2_dgrad_phase_planes(_nhwc_bf16(g), weight, pad, xn.shape[1],
                                                 xn.shape[2]).permute(0, 3, 1, 2)
             elif x.is_cuda and os.environ.get("LSS_S2_DGRAD_GEMM") != "1":
                 # data gradient: the library's transposed-conv kernels (no accumulation buffers; replay-checked by
@@ -270,48 +274,6 @@ class _ConvS2Fn(torch.autograd.Function):
         return (None if gx is None else gx.to(x_dtype), None if gw is None else gw.to(weight.dtype), None)
 
 
-class _UpConv3x3Fn(torch.autograd.Function):
-    """conv3x3(cat([x2, bilinear_align_corners(x1, up)])) with the upsample and the concat fused into
-    the conv's operand gather in the forward (neither tensor exists), and in the backward: one dgrad
-    conv for the concatenated input, the upsample's adjoint as a gather kernel, and the concatenated
-    input re-materialised in bf16 only for the weight-gradient GEMM.  x2 may be None (plain upsample)."""
-
-    @staticmethod
-    def forward(ctx, x1, x2, weight, up):
-        def nhwc(t):
-            t = t.permute(0, 2, 3, 1)
-            return (t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16)).contiguous()
-
-        x1n = nhwc(x1)
-        x2n = None if x2 is None else nhwc(x2)
-        wp = ops.pack_conv_weight(weight.detach().float().contiguous(), ops.DT_BF16)
-        y = ops.conv2d_nhwc(x1n, wp, (3, 3), 1, 1, x2=x2n, up=up, tag="conv2d_train_fwd")
-        ctx.save_for_backward(x1n, x2n, weight)
-        ctx.up = up
-        ctx.dtypes = (x1.dtype, None if x2 is None else x2.dtype)
-        return y.permute(0, 3, 1, 2)
-
-    @staticmethod
-    def backward(ctx, gy):
-        x1n, x2n, weight = ctx.saved_tensors
-        up = ctx.up
-        C2 = 0 if x2n is None else x2n.shape[3]
-        Cx = x1n.shape[3]
-        gyn = gy.permute(0, 2, 3, 1)
-        gyn = (gyn if gyn.dtype == torch.bfloat16 else gyn.to(torch.bfloat16)).contiguous()
-        g1 = g2 = gw = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            wd = ops.pack_conv_weight_dgrad(weight.detach().float().contiguous(), ops.DT_BF16)
-            gcat = ops.conv2d_nhwc(gyn, wd, (3, 3), 1, 1, tag="conv2d_dgrad")  # (B, H*up, W*up, C2+Cx)
-            if ctx.needs_input_grad[0]:
-                g1 = ops.upsample_bwd_nhwc(gcat, C2, Cx, up).permute(0, 3, 1, 2).to(ctx.dtypes[0])
-            if x2n is not None and ctx.needs_input_grad[1]:
-                g2 = gcat[..., :C2].permute(0, 3, 1, 2).to(ctx.dtypes[1])
-        if ctx.needs_input_grad[2]:
-            gw = ops.conv3x3_wgrad(ops.upsample_cat_nhwc(x1n, x2n, up), gyn).to(weight.dtype)
-        return g1, g2, gw, None
-
-
 class _BNActFn(torch.autograd.Function):
     """Training-mode BatchNorm2d (+ residual add, + ReLU) on the HIP kernels (csrc/bn_train.hip),
     forward and backward; logical (B,C,H,W) tensors in, computed on bf16 NHWC rows.  Running
@@ -319,12 +281,8 @@ class _BNActFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, gamma, beta, residual, running_mean, running_var, momentum, eps, relu):
-        def nhwc(t):
-            t = t.permute(0, 2, 3, 1)
-            return (t if t.dtype == torch.bfloat16 else t.to(torch.bfloat16)).contiguous()
-
-        zn = nhwc(z)
-        rn = None if residual is None else nhwc(residual)
+        zn = _nhwc_bf16(z)
+        rn = None if residual is None else _nhwc_bf16(residual)
         g32, b32 = gamma.detach().float().contiguous(), beta.detach().float().contiguous()
         y, mean, invstd = ops.bn_train_fwd(zn, g32, b32, running_mean, running_var, momentum, eps, relu, rn)
         ctx.save_for_backward(zn, y, g32, mean, invstd)
@@ -337,21 +295,12 @@ class _BNActFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         zn, y, g32, mean, invstd = ctx.saved_tensors
-        gyn = gy.permute(0, 2, 3, 1)
-        gyn = (gyn if gyn.dtype == torch.bfloat16 else gyn.to(torch.bfloat16)).contiguous()
         want_res = ctx.has_res and ctx.needs_input_grad[3]
-        dz, dres, dgamma, dbeta = ops.bn_train_bwd(gyn, y, zn, g32, mean, invstd, ctx.relu, want_res)
-        gz = dz.permute(0, 3, 1, 2).to(ctx.dtypes[0]) if ctx.needs_input_grad[0] else None
-        gres = dres.permute(0, 3, 1, 2).to(ctx.dtypes[1]) if want_res else None
+        dz, dres, dgamma, dbeta = ops.bn_train_bwd(_nhwc_bf16(gy), y, zn, g32, mean, invstd, ctx.relu, want_res)
+        gz = _nchw_as(dz, ctx.dtypes[0]) if ctx.needs_input_grad[0] else None
+        gres = _nchw_as(dres, ctx.dtypes[1]) if want_res else None
         return (gz, dgamma.to(ctx.dtypes[2]) if ctx.needs_input_grad[1] else None,
                 dbeta.to(ctx.dtypes[2]) if ctx.needs_input_grad[2] else None, gres, None, None, None, None, None)
-
-
-def _nhwc_bf16(t):
-    t = t.permute(0, 2, 3, 1)
-    if t.dtype != torch.bfloat16:
-        t = t.to(torch.bfloat16)
-    return t if t.is_contiguous() else t.contiguous()
 
 
 class _ConvBNActFn(torch.autograd.Function):
@@ -382,15 +331,8 @@ class _ConvBNActFn(torch.autograd.Function):
         g1, g2, gw, dgamma, dbeta, dres = ops.conv_bn_act_train_bwd(
             _nhwc_bf16(gy), y, z, x1n, x2n, w, g32, stat, relu, up, has_res and need[5], need[0],
             x2n is not None and need[1], need[2])
-
-        def out(t, dt):
-            if t is None:
-                return None
-            t = t.permute(0, 3, 1, 2)
-            return t if t.dtype == dt else t.to(dt)
-
-        return (out(g1, dt1), out(g2, dt2), gw, dgamma if need[3] else None, dbeta if need[4] else None,
-                out(dres, dtr), None, None, None, None, None, None)
+        return (_nchw_as(g1, dt1), _nchw_as(g2, dt2), gw, dgamma if need[3] else None, dbeta if need[4] else None,
+                _nchw_as(dres, dtr), None, None, None, None, None, None)
 
 
 class _SyncBNActFn(torch.autograd.Function):
@@ -426,15 +368,8 @@ class _SyncBNActFn(torch.autograd.Function):
         dist.all_reduce(glob, group=group)
         want_res = has_res and ctx.needs_input_grad[3]
         dz, dres = ops.bn_train_bwd_from_sums(gyn, y, zn, glob, m_total, g32, mean, invstd, relu, want_res)
-
-        def out(t, dt):
-            if t is None:
-                return None
-            t = t.permute(0, 3, 1, 2)
-            return t if t.dtype == dt else t.to(dt)
-
-        return (out(dz, dtz), local[1] if ctx.needs_input_grad[1] else None, local[0] if ctx.needs_input_grad[2] else None,
-                out(dres, dtr), None, None, None, None, None, None)
+        return (_nchw_as(dz, dtz), local[1] if ctx.needs_input_grad[1] else None,
+                local[0] if ctx.needs_input_grad[2] else None, _nchw_as(dres, dtr), None, None, None, None, None, None)
 
 
 def enable_sync_bn(module, group=None):
@@ -475,25 +410,53 @@ def _bn_native_ok(bn, z_is_cuda):
             and C % 8 == 0 and 256 % (C // 8) == 0 and bn.weight.dtype == torch.float32)
 
 
+def _native_training():
+    """Training convs go to the HIP kernels when the caller asked for bf16 math (bf16 autocast);
+    plain fp32 training keeps torch's fp32 convolutions.  LSS_TRAIN_NATIVE=0 disables."""
+    return (os.environ.get("LSS_TRAIN_NATIVE", "1") != "0" and torch.is_autocast_enabled("cuda")
+            and torch.get_autocast_dtype("cuda") == torch.bfloat16)
+
+
+def _conv3x3_native_ok(conv, is_cuda, c1, c2=0):
+    """Can `conv` on a c1-channel input (behind a concat: c2 skip channels in front of it) run on the HIP forward,
+    dgrad and wgrad kernels?  THE guard of every native 3x3 unit: plain 3x3 / stride 1 / pad 1, every channel count a
+    multiple of 64 (the kernels' K block; the input-gradient conv reads the layer's Cout in such blocks), the input as
+    wide as the conv expects.  The bias is the caller's business: the kernels have none."""
+    return (is_cuda and _native_training() and conv.kernel_size == (3, 3) and conv.stride == (1, 1)
+            and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and c1 % 64 == 0
+            and c2 % 64 == 0 and conv.out_channels % 64 == 0 and c1 + c2 == conv.in_channels)
+
+
+def _bn_apply(fn, bn, head, residual, relu, *tail):
+    """`fn.apply` of a node that holds a native train-mode BatchNorm: the node's leading tensors, the BatchNorm's
+    arguments, whatever the node takes behind them - and the batch counter nn.BatchNorm2d's own forward would bump."""
+    y = fn.apply(*head, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var, float(bn.momentum),
+                 float(bn.eps), bool(relu), *tail)
+    _count_batch(bn)
+    return y
+
+
 def _train_conv_bn_act(conv, bn, x1, relu, residual=None, up=None, x2=None):
-    """act(bn(conv(x)) (+ residual)) on the autograd path, x = x1 or cat([x2, up(x1)]).  One fused
-    HIP node when the shapes allow and the caller asked for bf16 math; otherwise composed from
-    the separate (native or library) pieces."""
-    if conv.bias is not None:
-        return _train_biased_conv_bn_act(conv, bn, x1, relu, residual, up, x2)
+    """act(bn(conv(x)) (+ residual)) on the autograd path, x = x1 or cat([x2, up(x1)]): the fused HIP node; where only
+    that one does not apply (synchronised statistics, non-fp32 weights) the native conv node and a native BatchNorm
+    node; otherwise the library's conv (or the stride-2 node) and whatever `_train_bn_act` picks.  A conv bias (every
+    nn.Conv2d of the vovnet reference has the default one, ref src/model_vovnet_transformer.py:131-143) is the
+    library conv's - except directly in front of a train-mode native BatchNorm, which removes it: then the unit runs
+    bias-free on the kernels and `_absorb_conv_bias` finishes it."""
     c2 = 0 if x2 is None else x2.shape[1]
     scale = 1 if up is None else int(up.scale_factor)
-    if (x1.is_cuda and _native_training() and _bn_native_ok(bn, True) and conv.kernel_size == (3, 3)
-            and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1
-            and conv.bias is None and conv.weight.dtype == torch.float32 and x1.shape[1] % 64 == 0 and c2 % 64 == 0
-            and conv.out_channels % 64 == 0 and (scale == 1 or (x1.shape[2] > 1 and x1.shape[3] > 1))):
-        if "_lss_sync" not in bn.__dict__:
-            y = _ConvBNActFn.apply(x1, x2, conv.weight, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var,
-                                   float(bn.momentum), float(bn.eps), bool(relu), scale)
-            _count_batch(bn)
-            return y
-    z = _train_conv(conv, x1) if up is None else _train_up_conv(conv, up, x1, x2)
-    return _train_bn_act(bn, z, relu, residual)
+    bn_ok = _bn_native_ok(bn, x1.is_cuda)
+    absorb = conv.bias is not None and bn_ok and up is None and x2 is None
+    conv_ok = ((conv.bias is None or absorb) and _conv3x3_native_ok(conv, x1.is_cuda, x1.shape[1], c2)
+               and (up is None or (x1.shape[2] > 1 and x1.shape[3] > 1)))
+    if conv_ok and bn_ok and "_lss_sync" not in bn.__dict__ and conv.weight.dtype == torch.float32:
+        y = _bn_apply(_ConvBNActFn, bn, (x1, x2, conv.weight), residual, relu, scale)
+    elif conv_ok:
+        y = _train_bn_act(bn, _Conv3x3Fn.apply(x1, x2, conv.weight, scale), relu, residual)
+    else:
+        z = _train_conv(conv, x1) if up is None else _train_up_conv(conv, up, x1, x2)
+        y = _train_bn_act(bn, z, relu, residual)
+    return _absorb_conv_bias(conv, bn, y) if absorb and conv_ok else y
 
 
 def _train_bn_act(bn, z, relu, residual=None):
@@ -501,13 +464,8 @@ def _train_bn_act(bn, z, relu, residual=None):
     caller asked for bf16 math and the module is in training mode, the library ops otherwise."""
     if _native_training() and _bn_native_ok(bn, z.is_cuda):
         if "_lss_sync" in bn.__dict__:
-            y = _SyncBNActFn.apply(z, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var,
-                                   float(bn.momentum), float(bn.eps), bool(relu), bn.__dict__["_lss_sync"][0])
-        else:
-            y = _BNActFn.apply(z, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var, float(bn.momentum),
-                               float(bn.eps), bool(relu))
-        _count_batch(bn)
-        return y
+            return _bn_apply(_SyncBNActFn, bn, (z,), residual, relu, bn.__dict__["_lss_sync"][0])
+        return _bn_apply(_BNActFn, bn, (z,), residual, relu)
     y = bn(z)
     if residual is not None:
         y = y + residual
@@ -542,29 +500,10 @@ def _absorb_conv_bias(conv, bn, y):
 
 
 def _biased_conv3x3_unit_ok(conv, bn, is_cuda, c_in):
-    """Does a 3x3 conv WITH bias + BatchNorm on a c_in-channel input take the bias-free native kernels?  The conditions of the
-    bias-free units, and a BatchNorm in training mode that `_bn_native_ok` accepts (an eval-mode BatchNorm does not
-    remove the bias)."""
-    return (is_cuda and _native_training() and _bn_native_ok(bn, True) and conv.kernel_size == (3, 3)
-            and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1
-            and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0 and c_in == conv.in_channels)
-
-
-def _train_biased_conv_bn_act(conv, bn, x1, relu, residual=None, up=None, x2=None):
-    """`_train_conv_bn_act` for a conv with a bias (every nn.Conv2d of the vovnet reference is built with the default
-    one, ref src/model_vovnet_transformer.py:131-143).  Plain 3x3 / stride 1 / pad 1 in front of a train-mode
-    BatchNorm: the bias-free fused node, or the unfused native pair where the fused one does not apply (synchronised
-    statistics, non-fp32 weights), then `_absorb_conv_bias`.  Everything else is the composition it always was."""
-    if up is None and x2 is None and _biased_conv3x3_unit_ok(conv, bn, x1.is_cuda, x1.shape[1]):
-        if "_lss_sync" not in bn.__dict__ and conv.weight.dtype == torch.float32:
-            y = _ConvBNActFn.apply(x1, None, conv.weight, bn.weight, bn.bias, residual, bn.running_mean, bn.running_var,
-                                   float(bn.momentum), float(bn.eps), bool(relu), 1)
-            _count_batch(bn)
-        else:
-            y = _train_bn_act(bn, _train_conv(conv, x1, bias_into_bn=True), relu, residual)
-        return _absorb_conv_bias(conv, bn, y)
-    z = _train_conv(conv, x1) if up is None else _train_up_conv(conv, up, x1, x2)
-    return _train_bn_act(bn, z, relu, residual)
+    """Does a 3x3 conv WITH bias + BatchNorm on a c_in-channel input take the bias-free native kernels?  The conditions
+    of the bias-free units, and a BatchNorm in training mode that `_bn_native_ok` accepts (an eval-mode BatchNorm does
+    not remove the bias)."""
+    return _bn_native_ok(bn, is_cuda) and _conv3x3_native_ok(conv, is_cuda, c_in)
 
 
 def _conv1x1_unit_ok(conv, bn, x):
@@ -600,45 +539,31 @@ def _train_conv1x1_bn_act(conv, bn, x, relu=True):
                                "one eager training step before capturing" % (key,))
         zb = _zero_bias[key] = torch.zeros(Cout, dtype=torch.float32, device=x.device)
     z = _LinearFn.apply(xn, conv.weight.view(Cout, conv.in_channels), zb)      # (B, H, W, Cout) bf16
-    y = _BNActFn.apply(z.permute(0, 3, 1, 2), bn.weight, bn.bias, None, bn.running_mean, bn.running_var,
-                       float(bn.momentum), float(bn.eps), bool(relu))
-    _count_batch(bn)
+    y = _bn_apply(_BNActFn, bn, (z.permute(0, 3, 1, 2),), None, relu)
     return y if conv.bias is None else _absorb_conv_bias(conv, bn, y)
-
-
-def _native_training():
-    """Training convs go to the HIP kernels when the caller asked for bf16 math (bf16 autocast);
-    plain fp32 training keeps torch's fp32 convolutions.  LSS_TRAIN_NATIVE=0 disables."""
-    return (os.environ.get("LSS_TRAIN_NATIVE", "1") != "0" and torch.is_autocast_enabled("cuda")
-            and torch.get_autocast_dtype("cuda") == torch.bfloat16)
 
 
 def _train_up_conv(conv, up, x1, x2):
     """conv(cat([x2, upsample(x1)])) on the autograd path (x2 may be None)."""
     c2 = 0 if x2 is None else x2.shape[1]
-    if (x1.is_cuda and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
-            and conv.bias is None and x1.shape[1] % 64 == 0 and c2 % 64 == 0 and conv.out_channels % 64 == 0
-            and x1.shape[2] > 1 and x1.shape[3] > 1 and _native_training()):
-        return _UpConv3x3Fn.apply(x1, x2, conv.weight, int(up.scale_factor))
+    if (conv.bias is None and x1.shape[2] > 1 and x1.shape[3] > 1
+            and _conv3x3_native_ok(conv, x1.is_cuda, x1.shape[1], c2)):
+        return _Conv3x3Fn.apply(x1, x2, conv.weight, int(up.scale_factor))
     x1 = up(x1)
     return _train_conv(conv, x1 if x2 is None else torch.cat([x2, x1], dim=1))
 
 
-def _train_conv(conv, x, bias_into_bn=False):
-    """conv(x) on the autograd path: the 3x3/s1/p1 shapes (95 % of BevEncode's FLOPs) run
-    forward and backward on the HIP kernels, everything else on the library.  out_channels % 64 == 0 (here, in
-    _train_up_conv and in _train_conv_bn_act): the input-gradient conv reads the layer's Cout in K blocks of 64.
-    A conv with a bias is the library's, unless the caller (`_train_biased_conv_bn_act`, which has checked
-    `_biased_conv3x3_unit_ok`) feeds a train-mode BatchNorm that absorbs the bias: then conv(x) WITHOUT it."""
+def _train_conv(conv, x):
+    """conv(x) on the autograd path: the bias-free 3x3 / stride 1 shapes `_conv3x3_native_ok` accepts (95 % of
+    BevEncode's FLOPs) and the bias-free stride-2 convs of the stem and of layer2 / layer3 run forward and backward on
+    the HIP kernels, everything else - every conv with a bias - on the library."""
     if conv.bias is not None:
-        return _Conv3x3Fn.apply(x, conv.weight) if bias_into_bn else conv(x)
-    if (x.is_cuda and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
-            and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
-            and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0 and _native_training()):
-        return _Conv3x3Fn.apply(x, conv.weight)
+        return conv(x)
+    if _conv3x3_native_ok(conv, x.is_cuda, x.shape[1]):
+        return _Conv3x3Fn.apply(x, None, conv.weight, 1)
     k, p = conv.kernel_size[0], conv.padding[0]
     if (x.is_cuda and conv.stride == (2, 2) and conv.kernel_size in ((1, 1), (3, 3), (7, 7)) and conv.padding == (k // 2, k // 2)
-            and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None and conv.in_channels % 64 == 0
+            and conv.dilation == (1, 1) and conv.groups == 1 and conv.in_channels % 64 == 0
             and conv.out_channels % 64 == 0 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and _native_training()):
         return _ConvS2Fn.apply(x, conv.weight, p)
     return conv(x)
@@ -1056,11 +981,7 @@ class BevEncode(nn.Module):
 
     def _apply(self, fn, *a, **k):
         self.invalidate_plan()
-        out = super()._apply(fn, *a, **k)
-        dev = self.conv1.weight.device
-        if dev.type == "cuda" and not torch.cuda.is_current_stream_capturing():
-            warm_s2_tables(dev)  # index tensors of the stride-2 weight gradients: never built inside a capture
-        return out
+        return super()._apply(fn, *a, **k)
 
     def load_state_dict(self, *a, **k):
         self.invalidate_plan()

@@ -1,12 +1,15 @@
 """Every autograd node of the BevEncode training step on its own against fp64: `_ConvBNActFn` over the dispatch table of
-`ops.conv_bn_act_train_fwd/bwd` (ring / K-split / tile for the forward and for the gradient conv), `_Conv3x3Fn`,
-`_ConvS2Fn`, `_UpConv3x3Fn`, `_BNActFn`, `_SyncBNActFn` and the split BatchNorm entry points `ops.bn_partial_sums`,
-`ops.bn_train_fwd_from_sums`, `ops.bn_train_bwd_from_sums`, driven through the functions the model uses
-(`modules._train_conv_bn_act`, `_train_conv`, `_train_up_conv`, `_train_bn_act`); plus `ops.weighted_ce_fwd/bwd`.
+`ops.conv_bn_act_train_fwd/bwd` (ring / K-split / tile for the forward and for the gradient conv), `_Conv3x3Fn`
+(plain, and behind the fused upsample + concat), `_ConvS2Fn`, `_BNActFn`, `_SyncBNActFn` and the split BatchNorm entry
+points `ops.bn_partial_sums`, `ops.bn_train_fwd_from_sums`, `ops.bn_train_bwd_from_sums`, driven through the functions
+the model uses (`modules._train_conv_bn_act`, `_train_conv`, `_train_up_conv`, `_train_bn_act`); the table of which
+unit takes which nodes (`test_train_unit_dispatch_table`); plus `ops.weighted_ce_fwd/bwd`.
 
 Reference, ReLU mask handling and tolerances: tests/train_node_ref.py.  Every bound is 3 x the rounding floor of the
 case (computed on the CPU, nothing taken from a kernel), at least 2^-8 for bf16 and 2e-4 for fp32 outputs; every measured
 error is `report`ed next to its floor."""
+import contextlib
+
 import pytest
 import torch
 from torch import nn
@@ -267,13 +270,15 @@ def test_prepacked_weight_images_of_a_unit(u, report):
 
 @pytest.mark.parametrize("u", R.CONV + R.UPCONV, ids=lambda u: u.name)
 def test_conv_nodes_vs_fp64(u, report):
-    """`_Conv3x3Fn` (_train_conv) and `_UpConv3x3Fn` (_train_up_conv; with and without x2, up 2 and 4)."""
+    """`_Conv3x3Fn` through _train_conv (plain: the gradient conv's output is the input gradient, the weight gradient
+    reads the saved input - no upsample kernel runs) and through _train_up_conv (with and without x2, up 2 and 4: the
+    upsample's adjoint and the re-materialised concatenated input)."""
     op = R.make_operands(u)
     op["bn"], op["relu"] = False, False
     got, tags, nodes = _run(op, "conv")
-    node = "_Conv3x3FnBackward" if u.up == 1 else "_UpConv3x3FnBackward"
-    assert nodes == [node, node], nodes
-    assert {"conv2d_train_fwd", "conv2d_dgrad", "conv2d_wgrad"} <= tags and (u.up == 1 or "upsample_bwd" in tags), tags
+    assert nodes == ["_Conv3x3FnBackward"] * 2, nodes
+    assert {"conv2d_train_fwd", "conv2d_dgrad", "conv2d_wgrad"} <= tags, tags
+    assert ("upsample_bwd" in tags) == ("upsample_cat" in tags) == (u.up > 1), tags
     _same_bits(got, _run(op, "conv")[0])
     _compare(report, u.name, got, op, _expected_outputs(op, u.need, "conv"))
     ops.assert_no_timeouts(u.name)
@@ -337,8 +342,7 @@ def test_fused_node_vs_conv_node_plus_bn_node(u, report):
     parts, tags, n2 = _run(op, "unfused", need)
     _same_bits(fused, _run(op, "fused", need)[0])
     _same_bits(parts, _run(op, "unfused", need)[0])
-    assert n1 == ["_ConvBNActFnBackward"] and n2 == ["_Conv3x3FnBackward" if u.up == 1 else "_UpConv3x3FnBackward",
-                                                    "_BNActFnBackward"], (n1, n2)
+    assert n1 == ["_ConvBNActFnBackward"] and n2 == ["_Conv3x3FnBackward", "_BNActFnBackward"], (n1, n2)
     assert {"bn_train_fwd", "bn_train_bwd", "conv2d_train_fwd", "conv2d_dgrad", "conv2d_wgrad"} <= tags, tags
     _compare(report, u.name + ".fused", fused, op, _expected_outputs(op, need, "fused"))
     _compare(report, u.name + ".unfused", parts, op, _expected_outputs(op, need, "unfused"))
@@ -510,17 +514,26 @@ def test_split_batchnorm_statistics_with_the_shared_pivot(report):
     ops.assert_no_timeouts("split_bn_shared_pivot")
 
 
+@contextlib.contextmanager
+def _one_rank_group(tmp_path):
+    """A world-size-1 gloo group on a file store, created and destroyed around the block."""
+    import torch.distributed as dist
+    assert not dist.is_initialized()
+    dist.init_process_group("gloo", store=dist.FileStore(str(tmp_path / "store"), 1), rank=0, world_size=1)
+    try:
+        yield
+    finally:
+        dist.destroy_process_group()
+
+
 def test_sync_bn_node_on_a_one_rank_group_equals_the_local_node(report, tmp_path):
     """`_SyncBNActFn` through _train_bn_act + enable_sync_bn on a world-size-1 group (file store, created and destroyed
     here): within the bound of fp64, and equal to `_BNActFn` on the same tensors up to the fp32 summation order (the two
     sum about different pivots)."""
-    import torch.distributed as dist
     u = R.BN[0]
     op = R.make_operands(u)
     local, _, _ = _run(op, "bn")
-    assert not dist.is_initialized()
-    dist.init_process_group("gloo", store=dist.FileStore(str(tmp_path / "store"), 1), rank=0, world_size=1)
-    try:
+    with _one_rank_group(tmp_path):
         mods = _modules(op)
         M.enable_sync_bn(mods[1])
         sync, _, nodes = _run(op, "bn", mods=mods)
@@ -528,8 +541,6 @@ def test_sync_bn_node_on_a_one_rank_group_equals_the_local_node(report, tmp_path
         mods = _modules(op)
         M.enable_sync_bn(mods[1])
         _same_bits(sync, _run(op, "bn", mods=mods)[0])
-    finally:
-        dist.destroy_process_group()
     expect = _expected_outputs(op, u.need, "bn")
     _compare(report, u.name + ".sync", sync, op, expect)
     _compare(report, u.name + ".local", local, op, expect)
@@ -539,6 +550,87 @@ def test_sync_bn_node_on_a_one_rank_group_equals_the_local_node(report, tmp_path
         assert R.errors(sync[k], local[k])[0] < 1e-5, k
     assert R.errors(sync["y"], local["y"])[0] <= 2.0 ** -7
     ops.assert_no_timeouts(u.name)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# which unit takes which nodes
+
+_LIB = {"Convolution": "library conv", "BatchNorm": "library BN"}
+
+
+def _nodes_along_first_input(y):
+    """The custom autograd nodes and the library's conv / BatchNorm nodes from y down its first input, outermost first."""
+    names, fn = [], y.grad_fn
+    while fn is not None:
+        n = type(fn).__name__
+        if n.startswith("_") and n.endswith("FnBackward"):
+            names.append(n[:-len("Backward")])
+        names += [v for k, v in _LIB.items() if k in n]
+        fn = fn.next_functions[0][0] if fn.next_functions else None
+    return names
+
+
+# (id, arguments of the case, nodes outermost first); "changed": the library composition where `_train_up_conv` used to
+# hand a dilated / grouped conv to the dense native node
+DISPATCH = [
+    ("plain", {}, ["_ConvBNActFn"]),
+    ("sync_bn", {"sync": True}, ["_SyncBNActFn", "_Conv3x3Fn"]),
+    ("bf16_weight", {"w_bf16": True}, ["_BNActFn", "_Conv3x3Fn"]),
+    ("cout_32", {"cout": 32}, ["_BNActFn", "library conv"]),
+    ("dilation_2", {"dilation": 2}, ["_BNActFn", "library conv"]),
+    ("up2", {"up": 2}, ["_ConvBNActFn"]),
+    ("up2_skip", {"up": 2, "c2": 64}, ["_ConvBNActFn"]),
+    ("up2_skip_dilation_2_changed", {"up": 2, "c2": 64, "dilation": 2}, ["_BNActFn", "library conv"]),
+    ("up2_groups_2_changed", {"up": 2, "groups": 2}, ["_BNActFn", "library conv"]),
+    ("biased", {"bias": True}, ["_AbsorbedBiasFn", "_ConvBNActFn"]),
+    ("biased_sync_bn", {"bias": True, "sync": True}, ["_AbsorbedBiasFn", "_SyncBNActFn", "_Conv3x3Fn"]),
+    ("biased_bf16_weight", {"bias": True, "w_bf16": True}, ["_AbsorbedBiasFn", "_BNActFn", "_Conv3x3Fn"]),
+    ("biased_up2", {"bias": True, "up": 2}, ["_BNActFn", "library conv"]),
+    ("biased_eval_bn", {"bias": True, "bn_eval": True}, ["library BN", "library conv"]),
+    ("s2_k3", {"k": 3, "stride": 2}, ["_BNActFn", "_ConvS2Fn"]),
+    ("s2_k1", {"k": 1, "stride": 2}, ["_BNActFn", "_ConvS2Fn"]),
+    ("s2_k7", {"k": 7, "stride": 2}, ["_BNActFn", "_ConvS2Fn"]),
+    ("no_autocast", {"autocast": False}, ["library BN", "library conv"]),
+]
+
+
+@pytest.mark.parametrize("case", DISPATCH, ids=lambda c: c[0])
+def test_train_unit_dispatch_table(case, tmp_path):
+    """`_train_conv_bn_act` on B = 1, 9 x 7 (12 x 12 for the stride-2 convs), 64 channels: one forward, and the nodes
+    from y down the first input are the table's.  The two rows that changed (a dilated / grouped conv behind an
+    upsample) must also have the shape of torch's own conv(cat([x2, up(x1)])) - a dilated 3x3 with pad 1 loses two rows
+    and columns, the dense native node would not; every other row runs one backward with finite gradients."""
+    name, a, expect = case
+    k, stride, up, c2, dil = a.get("k", 3), a.get("stride", 1), a.get("up", 0), a.get("c2", 0), a.get("dilation", 1)
+    autocast = a.get("autocast", True)
+    g = torch.Generator().manual_seed(len(name))
+    conv = nn.Conv2d(64 + c2, a.get("cout", 64), k, stride, 1 if dil > 1 else k // 2, dil, a.get("groups", 1),
+                     a.get("bias", False)).cuda()
+    if a.get("w_bf16"):
+        conv = conv.to(torch.bfloat16)
+    bn = nn.BatchNorm2d(conv.out_channels).cuda().train(not a.get("bn_eval"))
+    H, W = (12, 12) if stride == 2 else (9, 7)
+    dt = torch.bfloat16 if autocast else torch.float32
+    x1 = torch.randn(1, 64, H, W, generator=g).cuda().to(dt).requires_grad_(True)
+    x2 = torch.randn(1, c2, H * up, W * up, generator=g).cuda().to(dt).requires_grad_(True) if c2 else None
+    upm = nn.Upsample(scale_factor=up, mode="bilinear", align_corners=True) if up else None
+    with _one_rank_group(tmp_path) if a.get("sync") else contextlib.nullcontext():
+        if a.get("sync"):
+            M.enable_sync_bn(bn)
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=autocast):
+            y = M._train_conv_bn_act(conv, bn, x1, True, None, upm, x2)
+            assert _nodes_along_first_input(y) == expect, (_nodes_along_first_input(y), expect)
+            if name.endswith("_changed"):
+                with torch.no_grad():
+                    u = upm(x1)
+                    want = conv(u if x2 is None else torch.cat([x2, u], dim=1))
+                assert y.shape == want.shape, (tuple(y.shape), tuple(want.shape))
+                return
+        leaves = [t for t in (x1, x2) if t is not None] + list(conv.parameters()) + list(bn.parameters())
+        grads = torch.autograd.grad(y, leaves, torch.randn(y.shape, generator=g).cuda().to(y.dtype))
+        torch.cuda.synchronize()
+    assert all(bool(torch.isfinite(t).all()) for t in grads)
+    ops.assert_no_timeouts(name)
 
 
 # ---------------------------------------------------------------------------------------------------------------------

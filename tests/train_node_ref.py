@@ -59,7 +59,8 @@ FUSED = [
 ]
 RING_AB = "ring_ab_200x200"   # run once more with LSS_CONV_RING=0: tile / tile, same bound
 
-# the unfused nodes: _Conv3x3Fn, _UpConv3x3Fn (conv stage only), _BNActFn (BatchNorm stage only)
+# the unfused nodes: _Conv3x3Fn plain (CONV) and behind the fused upsample + concat (UPCONV) (conv stage only), _BNActFn
+# (BatchNorm stage only)
 CONV = [
     U("conv_37x29", 1, 37, 29, 64, 64),
     U("conv_9x7_c128", 2, 9, 7, 128, 64),
