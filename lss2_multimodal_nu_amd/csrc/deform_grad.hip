@@ -167,7 +167,10 @@ __global__ __launch_bounds__(256) void deform_absmax_kernel(const float* __restr
     const f32x4 v = p[i];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const int a = __builtin_bit_cast(int, v[k]) & 0x7fffffff;
+      // a scalar copy first: __builtin_bit_cast of the vector ELEMENT v[k] read element 0 for every k (the compiled loop
+      // loaded one dword of the four), so three quarters of d_out never reached the maximum
+      const float f = v[k];
+      const int a = __builtin_bit_cast(int, f) & 0x7fffffff;
       m = (a < 0x7f800000) ? max(m, a) : m;
     }
   }
