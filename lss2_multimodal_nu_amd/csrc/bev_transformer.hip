@@ -9,31 +9,11 @@
 // 8-B accesses, no LDS.
 #include <type_traits>
 
-#include "lss_common.h"
+#include "lss_device.h"
 
 namespace {
 
 constexpr int TC = 256;  // d_model of the reference's transformer (8 heads x 32 channels)
-
-template <typename T>
-__device__ __forceinline__ f32x4 load4(const T* p);
-template <>
-__device__ __forceinline__ f32x4 load4<float>(const float* p) {
-  return *reinterpret_cast<const f32x4*>(p);
-}
-template <>
-__device__ __forceinline__ f32x4 load4<unsigned short>(const unsigned short* p) {
-  const uint2 v = *reinterpret_cast<const uint2*>(p);
-  return (f32x4){lss_bf2f((unsigned short)(v.x & 0xffff)), lss_bf2f((unsigned short)(v.x >> 16)),
-                 lss_bf2f((unsigned short)(v.y & 0xffff)), lss_bf2f((unsigned short)(v.y >> 16))};
-}
-__device__ __forceinline__ void store4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-__device__ __forceinline__ void store4(unsigned short* p, f32x4 v) {
-  uint2 o;
-  o.x = lss_pack_bf2(v[0], v[1]);
-  o.y = lss_pack_bf2(v[2], v[3]);
-  *reinterpret_cast<uint2*>(p) = o;
-}
 
 // q[b, t, :] = x[b, t, :] + pos[t, :]
 template <typename T>
@@ -44,9 +24,9 @@ __global__ __launch_bounds__(256) void add_pos_kernel(const T* __restrict__ x,
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const int t = (int)(row % T_tok);
-  const f32x4 a = load4<T>(x + row * TC + 4 * lane);
+  const f32x4 a = lss_load4<T>(x + row * TC + 4 * lane);
   const f32x4 p = *reinterpret_cast<const f32x4*>(pos + (size_t)t * TC + 4 * lane);
-  store4(q + row * TC + 4 * lane, (f32x4){a[0] + p[0], a[1] + p[1], a[2] + p[2], a[3] + p[3]});
+  lss_store4(q + row * TC + 4 * lane, (f32x4){a[0] + p[0], a[1] + p[1], a[2] + p[2], a[3] + p[3]});
 }
 
 // The kernel is VALU-issue bound (address arithmetic, bf16 unpacking, the blend), not cache
@@ -94,8 +74,6 @@ __device__ __forceinline__ TapSet make_taps(float offx, float offy, float aw, fl
   t.i00 = cy0 * W + cx0; t.i01 = cy0 * W + cx1; t.i10 = cy1 * W + cx0; t.i11 = cy1 * W + cx1;
   return t;
 }
-
-typedef __attribute__((ext_vector_type(2))) float f32x2;
 
 // acc[0..7] += w * (8 channels at p)
 __device__ __forceinline__ void blend8(f32x2 (&acc)[4], const unsigned short* p, float w) {
@@ -185,7 +163,7 @@ __global__ __launch_bounds__(256) void deform_attn_kernel(
     constexpr int Q = decltype(qc)::value;
     constexpr int CTRL = Q | (Q << 2) | (Q << 4) | (Q << 6);  // quad_perm [Q, Q, Q, Q]
     auto bi = [&](int v) { return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, false); };
-    auto bf = [&](float v) { return __builtin_bit_cast(float, bi(__builtin_bit_cast(int, v))); };
+    auto bf = [&](float v) { return lss_dpp_f32<CTRL>(v); };
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
       const TapSet& m = half ? tb : ta;
@@ -217,18 +195,16 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const TI* __restrict__ x
   const int lane = threadIdx.x & 63;
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  const f32x4 v = load4<TI>(x + row * TC + 4 * lane);
+  const f32x4 v = lss_load4<TI>(x + row * TC + 4 * lane);
   const float mean = lss_wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.f / TC);
   const f32x4 d = (f32x4){v[0] - mean, v[1] - mean, v[2] - mean, v[3] - mean};
   const float var = lss_wave_sum(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3]) * (1.f / TC);
   const float inv = rsqrtf(var + eps);
   const f32x4 g = *reinterpret_cast<const f32x4*>(gamma + 4 * lane);
   const f32x4 bt = *reinterpret_cast<const f32x4*>(beta + 4 * lane);
-  store4(y + row * TC + 4 * lane, (f32x4){d[0] * inv * g[0] + bt[0], d[1] * inv * g[1] + bt[1],
+  lss_store4(y + row * TC + 4 * lane, (f32x4){d[0] * inv * g[0] + bt[0], d[1] * inv * g[1] + bt[1],
                                           d[2] * inv * g[2] + bt[2], d[3] * inv * g[3] + bt[3]});
 }
-
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 
@@ -237,7 +213,7 @@ extern "C" int lss_add_pos_fwd(const void* x, const float* pos, int B, int T, in
   LSS_CHECK_PTR(x); LSS_CHECK_PTR(pos); LSS_CHECK_PTR(q);
   LSS_CHECK_POS(B); LSS_CHECK_POS(T);
   if (C != TC) return LSS_E_SHAPE;
-  if (!aligned16(x) || !aligned16(pos) || !aligned16(q)) return LSS_E_ALIGN;
+  if (!lss_aligned(x, 16) || !lss_aligned(pos, 16) || !lss_aligned(q, 16)) return LSS_E_ALIGN;
   const long long rows = (long long)B * T;
   if (rows >= (1LL << 31)) return LSS_E_SHAPE;
   dim3 grid(lss_cdiv(rows, 4));
@@ -262,8 +238,8 @@ extern "C" int lss_deform_attn_fwd(const void* value, int value_layout, const fl
   LSS_CHECK_POS(B); LSS_CHECK_POS(H); LSS_CHECK_POS(W);
   if (n_heads != 8 || n_points != 8 || C != TC) return LSS_E_SHAPE;  // the reference's configuration
   if (value_layout != LSS_VALUE_NHWC && value_layout != LSS_VALUE_HEAD_MAJOR) return LSS_E_LAYOUT;
-  if (!aligned16(value) || !aligned16(offsets_logits) || !aligned16(out)) return LSS_E_ALIGN;
-  if (token_bias && !aligned16(token_bias)) return LSS_E_ALIGN;  // read with 16-B loads; null = no bias
+  if (!lss_aligned(value, 16) || !lss_aligned(offsets_logits, 16) || !lss_aligned(out, 16)) return LSS_E_ALIGN;
+  if (token_bias && !lss_aligned(token_bias, 16)) return LSS_E_ALIGN;  // read with 16-B loads; null = no bias
   const long long rows = (long long)B * H * W;
   if (rows >= (1LL << 31)) return LSS_E_SHAPE;
   const long long HW = (long long)H * W;
@@ -292,7 +268,7 @@ extern "C" int lss_deform_attn_pts_fwd(const float* value, const float* offsets_
   LSS_CHECK_POS(B); LSS_CHECK_POS(H); LSS_CHECK_POS(W);
   if (n_heads != 8 || n_points != 8 || C != TC) return LSS_E_SHAPE;
   if (ref_bstride < 0) return LSS_E_SHAPE;
-  if (!aligned16(value) || !aligned16(offsets_logits) || !aligned16(out)) return LSS_E_ALIGN;
+  if (!lss_aligned(value, 16) || !lss_aligned(offsets_logits, 16) || !lss_aligned(out, 16)) return LSS_E_ALIGN;
   if ((reinterpret_cast<uintptr_t>(ref_pts) & 7) != 0 || (ref_bstride & 1) != 0) return LSS_E_ALIGN;
   const long long rows = (long long)B * H * W;
   if (rows >= (1LL << 31)) return LSS_E_SHAPE;
@@ -308,7 +284,7 @@ extern "C" int lss_layernorm_fwd(const void* x, int x_dt, const float* gamma, co
   LSS_CHECK_PTR(x); LSS_CHECK_PTR(gamma); LSS_CHECK_PTR(beta); LSS_CHECK_PTR(y);
   if (rows <= 0 || rows >= (1LL << 31)) return LSS_E_SHAPE;
   if (C != TC) return LSS_E_SHAPE;
-  if (!aligned16(x) || !aligned16(gamma) || !aligned16(beta) || !aligned16(y)) return LSS_E_ALIGN;
+  if (!lss_aligned(x, 16) || !lss_aligned(gamma, 16) || !lss_aligned(beta, 16) || !lss_aligned(y, 16)) return LSS_E_ALIGN;
   dim3 grid(lss_cdiv(rows, 4));
   hipStream_t st = lss_stream(stream);
 #define LSS_LN(TI, TO)                                                                              \

@@ -12,26 +12,11 @@
 // the statistics and one for the elementwise part (z is read twice, bf16).  Channel sums are
 // two-stage and fixed-order (per-workgroup partials, then one small kernel), so results are
 // bit-reproducible.  Thread layout of the reductions: C/8 channel groups x 256/(C/8) row lanes.
-#include "lss_common.h"
+#include "lss_device.h"
 
 namespace {
 
 constexpr int RED_BLOCKS = 512;
-
-__device__ __forceinline__ void unpack8(const uint4& v, float (&f)[8]) {
-  const unsigned int u[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    f[2 * k] = lss_bf2f((unsigned short)(u[k] & 0xffff));
-    f[2 * k + 1] = lss_bf2f((unsigned short)(u[k] >> 16));
-  }
-}
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-  uint4 o;
-  o.x = lss_pack_bf2(f[0], f[1]); o.y = lss_pack_bf2(f[2], f[3]);
-  o.z = lss_pack_bf2(f[4], f[5]); o.w = lss_pack_bf2(f[6], f[7]);
-  return o;
-}
 
 // per-workgroup partial sums: part[blk][0][c] = sum a, part[blk][1][c] = sum b over the
 // workgroup's rows, where (a, b) = (z - p, (z - p)^2) [MODE 0] or (g, g * xhat) [MODE 1].
@@ -73,7 +58,7 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const unsigned short* __
     const long long r0 = (long long)blockIdx.x * rows_per, r1 = min(M, r0 + rows_per);
     for (long long r = r0 + lane; r < r1; r += L) {
       float zv[8];
-      unpack8(*reinterpret_cast<const uint4*>(z + r * C + g * 8), zv);
+      lss_unpack8(*reinterpret_cast<const uint4*>(z + r * C + g * 8), zv);
       if (MODE == 0) {
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
@@ -83,8 +68,8 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const unsigned short* __
         }
       } else {
         float gv[8], yv[8];
-        unpack8(*reinterpret_cast<const uint4*>(dy + r * C + g * 8), gv);
-        if (relu) unpack8(*reinterpret_cast<const uint4*>(y + r * C + g * 8), yv);
+        lss_unpack8(*reinterpret_cast<const uint4*>(dy + r * C + g * 8), gv);
+        if (relu) lss_unpack8(*reinterpret_cast<const uint4*>(y + r * C + g * 8), yv);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
           const float gk = (relu && !(yv[k] > 0.f)) ? 0.f : gv[k];
@@ -165,15 +150,15 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const unsigned short* __r
   for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n8; e += (long long)gridDim.x * 256) {
     const int g = (int)(e % G);
     float v[8], r[8];
-    unpack8(*reinterpret_cast<const uint4*>(z + e * 8), v);
-    if (res) unpack8(*reinterpret_cast<const uint4*>(res + e * 8), r);
+    lss_unpack8(*reinterpret_cast<const uint4*>(z + e * 8), v);
+    if (res) lss_unpack8(*reinterpret_cast<const uint4*>(res + e * 8), r);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       float t = fmaf(v[k], scale[g * 8 + k], shift[g * 8 + k]);
       if (res) t += r[k];
       v[k] = relu ? fmaxf(t, 0.f) : t;
     }
-    *reinterpret_cast<uint4*>(y + e * 8) = pack8(v);
+    *reinterpret_cast<uint4*>(y + e * 8) = lss_pack8(v);
   }
 }
 
@@ -208,9 +193,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const unsigned short*
   for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n8; e += (long long)gridDim.x * 256) {
     const int g = (int)(e % G);
     float zv[8], gv[8], yv[8], o[8];
-    unpack8(*reinterpret_cast<const uint4*>(z + e * 8), zv);
-    unpack8(*reinterpret_cast<const uint4*>(dy + e * 8), gv);
-    if (relu) unpack8(*reinterpret_cast<const uint4*>(y + e * 8), yv);
+    lss_unpack8(*reinterpret_cast<const uint4*>(z + e * 8), zv);
+    lss_unpack8(*reinterpret_cast<const uint4*>(dy + e * 8), gv);
+    if (relu) lss_unpack8(*reinterpret_cast<const uint4*>(y + e * 8), yv);
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const int c = g * 8 + k;
@@ -219,8 +204,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const unsigned short*
       const float xhat = (zv[k] - mean[c]) * invstd[c];
       o[k] = coef[2 * C + c] * (gk - coef[c] - xhat * coef[C + c]);
     }
-    *reinterpret_cast<uint4*>(dz + e * 8) = pack8(o);
-    if (dres) *reinterpret_cast<uint4*>(dres + e * 8) = pack8(gv);
+    *reinterpret_cast<uint4*>(dz + e * 8) = lss_pack8(o);
+    if (dres) *reinterpret_cast<uint4*>(dres + e * 8) = lss_pack8(gv);
   }
 }
 
@@ -300,10 +285,7 @@ extern "C" int lss_bn_train_bwd(const void* dy, const void* y, const void* z, lo
 // framework-bound (a Python autograd node costs more than most of these kernels run), so the
 // host side hands over every pointer once and the launches are chained here.
 // LSS_CONV_RING=0: the tile kernel everywhere (developer A/B, same switch as ops.conv_ring_ok)
-static bool train_ring_enabled() {
-  const char* e = getenv("LSS_CONV_RING");
-  return e == nullptr || atoi(e) != 0;
-}
+static bool train_ring_enabled() { return lss_env_on("LSS_CONV_RING"); }
 
 // The weight image a training unit of this shape runs on - forward (dgrad = 0) or input-gradient conv (dgrad = 1):
 // ring kernel where the shape qualifies, K-split kernel for the launch-bound layers, tile kernel otherwise.  ONE place

@@ -16,19 +16,8 @@
 //        column shift is materialised and the row shift is not.  The GEMM is linear_mfma.hip's
 //        kernel in split-K mode (grid.y = split x tap, fp32 partial tiles), followed by a
 //        fixed-order reduction over the splits (bit-reproducible; no atomics).
-#include <stdlib.h>
-
-#include "lss_common.h"
-
-int lss_wgrad_gemm_launch(const void* dyt, const void* const xt[3], float* partial, int M, int N,
-                          long long ld, long long split_k, int nsplit, int ntap, long long tap_row,
-                          hipStream_t st);  // linear_mfma.hip
-// conv_wgrad.hip: the direct kernel (NHWC operands as they lie, transposed reads); 0 splits = not a case for it
-int lss_wgrad_direct_splits(int B, int H, int W, int Cin, int Cout);
-int lss_wgrad_direct_launch(const void* x, const void* dy, int B, int H, int W, int Cin, int Cout, float* partial,
-                            hipStream_t st);
-int lss_wgrad_taps4x4_launch(const void* x, const void* dy, int B, int H, int W, int Cin, int Cout, float* partial,
-                             hipStream_t st);
+#include "conv_launch.h"
+#include "lss_device.h"
 
 namespace {
 
@@ -203,21 +192,6 @@ __global__ void wgrad_reduce_kernel(const float* __restrict__ partial, int nspli
 
 inline size_t align256(size_t v) { return (v + 255) / 256 * 256; }
 
-__device__ __forceinline__ void unpack8(const uint4& v, float (&f)[8]) {
-  const unsigned int u[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    f[2 * k] = lss_bf2f((unsigned short)(u[k] & 0xffff));
-    f[2 * k + 1] = lss_bf2f((unsigned short)(u[k] >> 16));
-  }
-}
-__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
-  uint4 o;
-  o.x = lss_pack_bf2(f[0], f[1]); o.y = lss_pack_bf2(f[2], f[3]);
-  o.z = lss_pack_bf2(f[4], f[5]); o.w = lss_pack_bf2(f[6], f[7]);
-  return o;
-}
-
 // out[b, Y, X, :] = [ x2[b, Y, X, :C2] | bilinear_align_corners(x)[b, Y, X, :Cx] ]   (ref Up.forward,
 // src/modules.py:22-24, materialised: only the weight-gradient GEMM needs it as a tensor)
 __global__ __launch_bounds__(256) void upsample_cat_kernel(const unsigned short* __restrict__ x,
@@ -241,14 +215,14 @@ __global__ __launch_bounds__(256) void upsample_cat_kernel(const unsigned short*
       const int y1 = y0 < H - 1 ? y0 + 1 : y0, x1 = x0 < W - 1 ? x0 + 1 : x0;
       const unsigned short* base = x + (size_t)b * H * W * Cx + (c - C2);
       float a[8], bq[8], cq[8], d[8], r[8];
-      unpack8(*reinterpret_cast<const uint4*>(base + ((size_t)y0 * W + x0) * Cx), a);
-      unpack8(*reinterpret_cast<const uint4*>(base + ((size_t)y0 * W + x1) * Cx), bq);
-      unpack8(*reinterpret_cast<const uint4*>(base + ((size_t)y1 * W + x0) * Cx), cq);
-      unpack8(*reinterpret_cast<const uint4*>(base + ((size_t)y1 * W + x1) * Cx), d);
+      lss_unpack8(*reinterpret_cast<const uint4*>(base + ((size_t)y0 * W + x0) * Cx), a);
+      lss_unpack8(*reinterpret_cast<const uint4*>(base + ((size_t)y0 * W + x1) * Cx), bq);
+      lss_unpack8(*reinterpret_cast<const uint4*>(base + ((size_t)y1 * W + x0) * Cx), cq);
+      lss_unpack8(*reinterpret_cast<const uint4*>(base + ((size_t)y1 * W + x1) * Cx), d);
 #pragma unroll
       for (int k = 0; k < 8; ++k)
         r[k] = (1.f - ly) * ((1.f - lx) * a[k] + lx * bq[k]) + ly * ((1.f - lx) * cq[k] + lx * d[k]);
-      o = pack8(r);
+      o = lss_pack8(r);
     }
     *reinterpret_cast<uint4*>(out + (size_t)pix * Ct + c) = o;
   }
@@ -283,13 +257,13 @@ __global__ __launch_bounds__(256) void upsample_bwd_kernel(const unsigned short*
         const float wx = x0 == x ? 1.f - lx : ((x0 + 1 == x && x0 < W - 1) ? lx : 0.f);
         if (wx == 0.f) continue;
         float v[8];
-        unpack8(*reinterpret_cast<const uint4*>(g + (((size_t)b * Hh + Y) * Wh + X) * Ct + c_off + p8 * 8), v);
+        lss_unpack8(*reinterpret_cast<const uint4*>(g + (((size_t)b * Hh + Y) * Wh + X) * Ct + c_off + p8 * 8), v);
         const float wgt = wy * wx;
 #pragma unroll
         for (int k = 0; k < 8; ++k) acc[k] = fmaf(wgt, v[k], acc[k]);
       }
     }
-    *reinterpret_cast<uint4*>(dx + (size_t)pix * Cx + p8 * 8) = pack8(acc);
+    *reinterpret_cast<uint4*>(dx + (size_t)pix * Cx + p8 * 8) = lss_pack8(acc);
   }
 }
 
@@ -338,13 +312,13 @@ __global__ __launch_bounds__(256) void upsample_bwd_rows_kernel(const unsigned s
       for (int i = 0; i < NW; ++i) {
         if (wxv[i] == 0.f) continue;
         float v[8];
-        unpack8(r[i], v);
+        lss_unpack8(r[i], v);
         const float wgt = wy * wxv[i];
 #pragma unroll
         for (int k = 0; k < 8; ++k) acc[k] = fmaf(wgt, v[k], acc[k]);
       }
     }
-    *reinterpret_cast<uint4*>(dx + (size_t)pix * Cx + p8 * 8) = pack8(acc);
+    *reinterpret_cast<uint4*>(dx + (size_t)pix * Cx + p8 * 8) = lss_pack8(acc);
   }
 }
 
@@ -494,7 +468,7 @@ extern "C" int lss_upsample_bwd_nhwc(const void* g, int B, int H, int W, int Cx,
   const int grid = (int)((n + 255) / 256 > 65536 ? 65536 : (n + 255) / 256);
   // columns a window can span: candidates floor((x - 1) / rx) .. ceil((x + 1) / rx)
   const int span = (int)ceilf(2.f / rx) + 3;
-  const bool rows_form = getenv("LSS_UPSAMPLE_BWD_ROWS") == nullptr || atoi(getenv("LSS_UPSAMPLE_BWD_ROWS")) != 0;
+  const bool rows_form = lss_env_on("LSS_UPSAMPLE_BWD_ROWS");
 #define LSS_UB(KERNEL)                                                                                      \
   hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(256), 0, lss_stream(stream), static_cast<const unsigned short*>(g), B, H, \
                      W, Cx, Ct, c_off, up, ry, rx, static_cast<unsigned short*>(dx))

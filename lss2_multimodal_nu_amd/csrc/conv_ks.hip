@@ -27,11 +27,10 @@
 //     channel tile t are the channels {8 q + 4 t + i}, so lane (q, n) ends with 8 CONSECUTIVE channels of pixel n and
 //     the four q lanes of a pixel write 64 contiguous bytes (no LDS staging of the output tile).
 // No inter-workgroup communication, no bounded waits: nothing here can hang.
-#include <stdlib.h>
-
 #include <type_traits>
 
-#include "lss_common.h"
+#include "conv_launch.h"
+#include "lss_device.h"
 
 namespace {
 
@@ -40,11 +39,6 @@ constexpr int KS_POSB = 64;       // bytes per patch position and chunk (32 chan
 constexpr int KS_LDS_MAX = 160 * 1024;
 
 __device__ __attribute__((aligned(128))) unsigned char lss_ks_zero_page[128];  // source of out-of-image patch pieces
-
-__device__ __forceinline__ void ks_glds16(const void* gsrc, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
 
 // Input patch -> LDS by LDS-DMA: [chunk][channel half][position][32 B]; a piece = 32 positions of one half; patch
 // position (pr, pc) of `rows` x `pitch` (padded to nposp) is input pixel map(pr, pc) or, outside the image, the zero page
@@ -84,7 +78,7 @@ __device__ __forceinline__ void ks_fill_patch(unsigned char* smem, const unsigne
     const unsigned short* src = xb + (in ? (iy * W + ix) * Cin : 0);
 #pragma unroll
     for (int c = 0; c < NCH; ++c)
-      ks_glds16(in ? (const void*)(src + c * 32) : (const void*)zsrc,
+      lss_glds16(in ? (const void*)(src + c * 32) : (const void*)zsrc,
                 smem + ((size_t)(c * 2 + h) * nposp + 32 * (i >> 1)) * 32);
     pr += q64; pc += r64;
     if (pc >= pitch) { pc -= pitch; ++pr; }
@@ -112,11 +106,17 @@ struct KsStamps {
   __device__ __forceinline__ void drain() const {
     if (base != nullptr) {
       stamp(5);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // stores acknowledged
+      lss_wait_vmcnt<0>();  // stores acknowledged
       stamp(6);
     }
   }
 };
+
+// lss_pack8 as the vector type the write-through buffer store takes
+__device__ __forceinline__ u32x4 ks_pack8(const float (&v)[8]) {
+  const uint4 o = lss_pack8(v);
+  return (u32x4){o.x, o.y, o.z, o.w};
+}
 
 // epilogue constants of a lane's 8 consecutive channels ch .. ch + 7 (null scale: 1, null shift: 0)
 __device__ __forceinline__ void ks_load_affine(const float* scale, const float* shift, int ch, float (&sc)[8], float (&sh)[8]) {
@@ -125,12 +125,6 @@ __device__ __forceinline__ void ks_load_affine(const float* scale, const float* 
   if (shift) { h0 = *reinterpret_cast<const f32x4*>(shift + ch); h1 = *reinterpret_cast<const f32x4*>(shift + ch + 4); }
 #pragma unroll
   for (int i = 0; i < 4; ++i) { sc[i] = s0[i]; sc[4 + i] = s1[i]; sh[i] = h0[i]; sh[4 + i] = h1[i]; }
-}
-
-// 8 x fp32 -> the 16-B store value of 8 consecutive bf16 channels
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
-__device__ __forceinline__ u32x4 ks_pack8(const float (&v)[8]) {
-  return (u32x4){lss_pack_bf2(v[0], v[1]), lss_pack_bf2(v[2], v[3]), lss_pack_bf2(v[4], v[5]), lss_pack_bf2(v[6], v[7])};
 }
 
 // The K parts meet through LDS - the FOREIGN ones only.  Wave (kp, ph) finishes the tiles j = kp, kp + NKW, .. of its
@@ -328,7 +322,7 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(const KsArgs a) {
     acc[j][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
     acc[j][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the patch pieces (and the weight fragments) have landed
+  lss_wait_vmcnt<0>();  // the patch pieces (and the weight fragments) have landed
   __syncthreads();
   st.stamp(2);
 
@@ -447,16 +441,7 @@ __global__ void pack_weights_ks_kernel(const float* __restrict__ w, int Cout, in
 
 // ---- host side shared by the three modes ----
 // LSS_CONV_KS=0 switches every mode of this file off (the *_ok functions answer 0)
-bool ks_enabled() {
-  const char* e = getenv("LSS_CONV_KS");
-  return e == nullptr || atoi(e) != 0;
-}
-
-// the diagnostic stamp buffer of tools/bench_ks.py --stamps (every kernel of this file), or null
-unsigned long long* ks_stamps_from_env() {
-  const char* e = getenv("LSS_KS_STAMPS");
-  return e ? reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 16)) : nullptr;
-}
+bool ks_enabled() { return lss_env_on("LSS_CONV_KS"); }
 
 // grid of a weight-pack kernel over n elements (256 threads, grid-stride)
 int ks_pack_grid(size_t n) { return (int)((n + 255) / 256 > 4096 ? 4096 : (n + 255) / 256); }
@@ -464,7 +449,7 @@ int ks_pack_grid(size_t n) { return (int)((n + 255) / 256 > 4096 ? 4096 : (n + 2
 // every pointer 16-byte aligned (null passes)
 template <class... P>
 bool ks_aligned16(const P*... p) {
-  return ((reinterpret_cast<uintptr_t>(p) | ...) & 15) == 0;
+  return (lss_aligned(p, 16) && ...);
 }
 
 // one launch of kernel K: the dynamic-LDS attribute is set once per instantiation and device
@@ -610,7 +595,7 @@ __global__ __launch_bounds__(256, 1) void conv_ks_s2_dual_kernel(const KsS2Args 
       acc[j][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
       acc2[j][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
     }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  lss_wait_vmcnt<0>();
   __syncthreads();
   st.stamp(2);
 
@@ -894,7 +879,7 @@ __global__ __launch_bounds__(256, 1) void conv_ks_stem_kernel(const KsStemArgs a
   const int ch = cb * 64 + g * 32 + kq * 8;
   float sc[8], sh[8];
   ks_load_affine(a.scale, a.shift, ch, sc, sh);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the patch pieces have landed
+  lss_wait_vmcnt<0>();  // the patch pieces have landed
   __syncthreads();
   st.stamp(2);
 
@@ -1030,7 +1015,7 @@ int lss_conv_ks_launch(const void* x, const void* w_ks, const float* scale, cons
   a.residual = reinterpret_cast<const unsigned short*>(residual);
   a.y = reinterpret_cast<unsigned short*>(y);
   a.relu = relu; a.wt = wt;
-  a.stamps = ks_stamps_from_env();
+  a.stamps = lss_env_device_ptr("LSS_KS_STAMPS");
   if (p.variant == 0) return ks_launch<conv_ks_kernel<18, 4, 5>>(p.grid, p.lds, a, st);
   if (p.variant == 1) return ks_launch<conv_ks_kernel<9, 4, 10>>(p.grid, p.lds, a, st);
   return ks_launch<conv_ks_kernel<9, 2, 10>>(p.grid, p.lds, a, st);
@@ -1072,7 +1057,7 @@ extern "C" int lss_conv2d_ks_s2_dual_fwd(const void* x, const void* w_packed, co
   a.y = reinterpret_cast<unsigned short*>(y);
   a.y2 = reinterpret_cast<unsigned short*>(y2);
   a.relu = relu;
-  a.stamps = ks_stamps_from_env();
+  a.stamps = lss_env_device_ptr("LSS_KS_STAMPS");
   return p.nkw == 4 ? ks_launch<conv_ks_s2_dual_kernel<4>>(p.grid, p.lds, a, lss_stream(stream))
                     : ks_launch<conv_ks_s2_dual_kernel<2>>(p.grid, p.lds, a, lss_stream(stream));
 }
@@ -1109,6 +1094,6 @@ extern "C" int lss_conv2d_ks_stem_fwd(const void* x, const void* w_packed, const
   a.scale = scale; a.shift = shift;
   a.y = reinterpret_cast<unsigned short*>(y);
   a.relu = relu;
-  a.stamps = ks_stamps_from_env();
+  a.stamps = lss_env_device_ptr("LSS_KS_STAMPS");
   return ks_launch<conv_ks_stem_kernel>(p.grid, ST_LDS, a, lss_stream(stream));
 }

@@ -16,20 +16,8 @@
 // contiguous run of channels (32 bf16 / 4 f32) and k-step s consumes its s-th
 // piece on BOTH operands, so activations (NHWC) and weights ([tap][co][ci]) keep
 // their natural layouts - only the order of the K summation is permuted.
-#include <stdlib.h>
-
-#include "lss_common.h"
-
-int lss_linear_bf16_launch(const void* x, const void* w, const float* scale, const float* shift,
-                           const void* residual, void* y, long long M, int N, int K, int act,
-                           int out_f32, int group_hw, hipStream_t st);  // linear_mfma.hip
-
-int lss_conv_ring_launch(const void* x, const void* x2, const void* w_ring, const float* scale, const float* shift,
-                         void* y, const float* head_w, const float* head_b, float* head_out, int head_n, int B, int H,
-                         int W, int Cx, int C2, int up, int Cout, int relu, int wt, hipStream_t st);  // conv_ring.hip
-
-int lss_conv_ks_launch(const void* x, const void* w_ks, const float* scale, const float* shift, const void* residual,
-                       void* y, int B, int H, int W, int Cin, int Cout, int relu, int wt, hipStream_t st);  // conv_ks.hip
+#include "conv_launch.h"
+#include "lss_device.h"
 
 namespace {
 
@@ -68,12 +56,7 @@ struct ConvArgs {
   int src_lds;  // MODE 1, KC = 32: the low-res source patch of a chunk is staged in LDS (see SRC below)
 };
 
-// LSS_CONV_STAMPS=<hex device address of a u64 buffer, 8 entries per workgroup> switches the phase stamps on
-static unsigned long long* conv_stamps_from_env() {
-  const char* e = getenv("LSS_CONV_STAMPS");
-  return e ? reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 16)) : nullptr;
-}
-
+// libm's erff, not lss_gelu's polynomial: the fp32 parity path runs through here
 __device__ __forceinline__ float conv_act(float v, int act) {
   if (act == 1) return fmaxf(v, 0.f);
   if (act == 2) return 0.5f * v * (1.f + erff(v * 0.70710678118654752f));
@@ -95,22 +78,6 @@ struct Frag<float> {
   static constexpr int KBLOCK = 8;  // 2 halves x 1 piece (4 k-steps of 2)
 };
 
-// Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains
-// vmcnt(0), which would expose the latency of the weight / patch prefetch loads
-// that are meant to stay in flight across it (cdna_hip_programming.md section 5,
-// "Pipelining across barriers").
-// x of the lane a DPP control selects (quad_perm / row_mirror / row_half_mirror: all inside a row of 16)
-template <int CTRL>
-__device__ __forceinline__ float dpp_f32(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, 0xf, 0xf, false));
-}
-
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-
 __device__ __forceinline__ f32x4 lerp4(f32x4 a, f32x4 b, float t) {
   f32x4 r;
 #pragma unroll
@@ -120,7 +87,7 @@ __device__ __forceinline__ f32x4 lerp4(f32x4 a, f32x4 b, float t) {
 
 // bilinear blend of four 8-channel bf16 pieces in the four-weight form, on (lo, hi)
 // channel pairs: float2 arithmetic maps to v_pk_mul_f32 / v_pk_fma_f32.  One rounding to bf16.
-typedef __attribute__((ext_vector_type(2))) float f32x2;
+// (conv_ring.hip's rk_blend is the scalar-FMA form of the same blend, on purpose.)
 __device__ __forceinline__ f32x2 unpack_bf2(unsigned int u) {
   f32x2 v;
   v[0] = __builtin_bit_cast(float, u << 16);
@@ -326,16 +293,7 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(ConvArgs a) {
 // multiple of 256 B, which makes the two pixel rows of a 32-row MFMA tile land on complementary bank
 // sets (conflict-free ds_read_b128); weight rows are KC*2 B, XOR-swizzled in 16-B pieces on the DMA's
 // SOURCE address (the DMA destination is lane-linear) and on the read address.
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
+//
 // MODE 0: plain NHWC input, stride 1.  MODE 1: fused [x2 | bilinear-upsampled x] input.
 // MODE 2: stride-2 conv as a stride-1 conv over the 4 parity phases of the input
 // (space-to-depth done by the gather: chunk -> (phase, 64-channel block); weights
@@ -486,7 +444,7 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
       const int row = KC == 64 ? rblk * 8 + (lane >> 3) : rblk * 16 + (lane >> 2);
       const int part = KC == 64 ? (lane & 7) ^ ((row >> 1) & 7) : (lane & 3) ^ ((row >> 2) & 3);
       const int co = min(n0 + row, a.Cout - 1);  // rows past Cout: any valid address (never stored)
-      glds16(wg + ((size_t)tap * a.Cout + co) * a.Cin + chunk * KC + part * 8,
+      lss_glds16(wg + ((size_t)tap * a.Cout + co) * a.Cin + chunk * KC + part * 8,
              w_tile + slot * W_BYTES + blk * 1024);
     }
   };
@@ -583,7 +541,7 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
     const int cx = (cbase + chunk) * KC - a.C2;
 #pragma unroll
     for (int i = 0; i < (SRC ? SRC_DMA : 0); ++i)
-      if (i * 4 + wave < SRC_PIECES) glds16(xp + src_o[i] + cx, src_tile + (i * 4 + wave) * 1024);
+      if (i * 4 + wave < SRC_PIECES) lss_glds16(xp + src_o[i] + cx, src_tile + (i * 4 + wave) * 1024);
   };
   // does `chunk` read the upsampled tensor through src_tile?
   auto src_chunk = [&](int chunk) { return use_src && chunk < nchunks && (cbase + chunk) * KC >= a.C2; };
@@ -646,7 +604,7 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
     const int row = KC == 64 ? rblk * 8 + (lane >> 3) : rblk * 16 + (lane >> 2);
     const int part = KC == 64 ? (lane & 7) ^ ((row >> 1) & 7) : (lane & 3) ^ ((row >> 2) & 3);
     const int co = min(n0 + row, a.Cout - 1);
-    glds16(wg + ((size_t)tap * a.Cout + co) * a.Cin + (cbase + chunk) * KC + part * 8,
+    lss_glds16(wg + ((size_t)tap * a.Cout + co) * a.Cin + (cbase + chunk) * KC + part * 8,
            w_tile + slot * W_BYTES + blk * 1024);
   };
 
@@ -704,13 +662,13 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
   for (int q = 1; q < LA; ++q)
     if (nsteps > q) issue_w(q, q);
   if (src_chunk(0)) {
-    wait_vmcnt<0>();
-    lds_barrier();  // the source pixels of chunk 0 are in LDS for every wave
+    lss_wait_vmcnt<0>();
+    lss_lds_barrier();  // the source pixels of chunk 0 are in LDS for every wave
   }
   if (FUSED) gather_fused(0);
   else gather_in(0, true);
-  wait_vmcnt<0>();
-  lds_barrier();
+  lss_wait_vmcnt<0>();
+  lss_lds_barrier();
   stamp(1);
 
   // Main loop.  The NT taps of a chunk are fully unrolled (static patch offsets and
@@ -770,7 +728,7 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
       if (SRC && st == 0 && srcq) issue_src(chunk + 1);
       if (prefetch) gather_in(chunk + 1, false);  // next patch -> registers
       if (st == NS - 1 && !last_chunk) {
-        lds_barrier();  // every wave is done with this chunk's patch
+        lss_lds_barrier();  // every wave is done with this chunk's patch
         if (FUSED) gather_fused(chunk + 1);
         else store_in();
       }
@@ -779,14 +737,14 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
       // (younger than W(step+1): the slabs of steps step+2 .. step+LA, and - in steps 0 .. LA-1 of a chunk - the source
       // copies issued in its step 0: one per wave, two for the waves that carry the pieces past the fourth)
       constexpr int WYOUNG = (LA - 1) * WPT;
-      if (prefetch) wait_vmcnt<WYOUNG + IPT>();
+      if (prefetch) lss_wait_vmcnt<WYOUNG + IPT>();
       else if (SRC && st < LA && srcq && more) {
-        if (SRC_DMA == 2 && wave + 4 < SRC_PIECES) wait_vmcnt<WYOUNG + 2>();
-        else wait_vmcnt<WYOUNG + (SRC_DMA >= 1 ? 1 : 0)>();
+        if (SRC_DMA == 2 && wave + 4 < SRC_PIECES) lss_wait_vmcnt<WYOUNG + 2>();
+        else lss_wait_vmcnt<WYOUNG + (SRC_DMA >= 1 ? 1 : 0)>();
       }
-      else if (more) wait_vmcnt<WYOUNG>();
-      else wait_vmcnt<0>();
-      lds_barrier();
+      else if (more) lss_wait_vmcnt<WYOUNG>();
+      else lss_wait_vmcnt<0>();
+      lss_lds_barrier();
       slot = slot == NSL - 1 ? 0 : slot + 1;
       if (st < NS - 1) read_b(0, slot, 0);
     }
@@ -799,7 +757,7 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
   // residual (one 16-B load), ReLU, rounds to bf16 once, and stores 16 B.
   float* otile = reinterpret_cast<float*>(smem);
   stamp(2);
-  // (the loop's final lds_barrier already guarantees every wave is done reading LDS)
+  // (the loop's final lss_lds_barrier already guarantees every wave is done reading LDS)
   if (KSP == 2) {
     // split-K: the second group's partial sums meet the first group's through LDS (same lane ->
     // same element in both groups, so only the group hand-over needs barriers)
@@ -814,7 +772,7 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
             otile[((prow0 + 2 * rt + (row >> 4)) * 16 + (row & 15)) * OLD + wc * 64 + ct * 32 + r] = acc[rt][ct][i];
           }
     }
-    lds_barrier();
+    lss_lds_barrier();
     if (grp == 0) {
 #pragma unroll
       for (int ct = 0; ct < 2; ++ct)
@@ -826,7 +784,7 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
             acc[rt][ct][i] += otile[((prow0 + 2 * rt + (row >> 4)) * 16 + (row & 15)) * OLD + wc * 64 + ct * 32 + r];
           }
     }
-    lds_barrier();  // the partials are consumed before group 0 restages the tile below
+    lss_lds_barrier();  // the partials are consumed before group 0 restages the tile below
   }
   // (the epilogue of the launch-bound layers is instruction-issue time, not bandwidth)
   // dual-output launches: this workgroup's channel block belongs to y (columns [0, split)) or y2
@@ -890,7 +848,7 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
         }
       }
     }
-    lds_barrier();
+    lss_lds_barrier();
     if (half == 0) stamp(3);
     if (grp != 0) {
       // second K-split group: its sums were handed over above; it only keeps the barriers company
@@ -903,11 +861,10 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
       // ~60 FMA / DPP instructions to ~12 conversions.  A: lane (r = pixel, q) <- 8 consecutive channels of the
       // fp32 tile in LDS (2 ds_read_b128); B: lane (k = lane & 15, q) <- 8 consecutive weights of class k from
       // global (L1-resident: 2 KiB); D: lane (k, q) holds pixels 4q..4q+3 of the row = ONE 16-B NCHW store.
-      typedef __attribute__((ext_vector_type(4))) float f32x4_t;
       const int hr = lane & 15, hq = lane >> 4;
       for (int row = wave; row < HROWS; row += 4) {
         const int oy = oy0 + half * HROWS + row;
-        f32x4_t hacc = {0.f, 0.f, 0.f, 0.f};
+        f32x4 hacc = {0.f, 0.f, 0.f, 0.f};
         const float* arow = otile + (row * 16 + hr) * OLD + hq * 8;
         const float* wrow = a.head_w + (size_t)min(hr, a.head_n - 1) * BN + hq * 8;
         // rolled: one k-step's 16 operand floats live at a time (the other half-tile's waves still hold their
@@ -947,7 +904,7 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
           const float hb = a.head_b[hr];
           float* op = a.head_out + (((size_t)b * a.head_n + hr) * a.Ho + oy) * a.Wo + ox0 + hq * 4;
           if ((a.Wo & 3) == 0 && ox0 + hq * 4 + 4 <= a.Wo) {
-            *reinterpret_cast<f32x4_t*>(op) = (f32x4_t){hacc[0] + hb, hacc[1] + hb, hacc[2] + hb, hacc[3] + hb};
+            *reinterpret_cast<f32x4*>(op) = (f32x4){hacc[0] + hb, hacc[1] + hb, hacc[2] + hb, hacc[3] + hb};
           } else {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
@@ -978,10 +935,10 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
             // sum over the CG lanes of the pixel on DPP row operations (no LDS round trips): lane ^ 1,
             // lane ^ 2, then - every quad now holding its sum - the other quad of the 8 (row_half_mirror)
             // and the other half of the 16 (row_mirror)
-            part += dpp_f32<0xB1>(part);
-            part += dpp_f32<0x4E>(part);
-            part += dpp_f32<0x141>(part);
-            if (CG == 16) part += dpp_f32<0x140>(part);
+            part += lss_dpp_f32<0xB1>(part);
+            part += lss_dpp_f32<0x4E>(part);
+            part += lss_dpp_f32<0x141>(part);
+            if (CG == 16) part += lss_dpp_f32<0x140>(part);
             if (hc8 == 0 && oy < a.Ho && hx < a.Wo)
               a.head_out[(((size_t)b * a.head_n + k) * a.Ho + oy) * a.Wo + hx] = part + a.head_b[k];
           }
@@ -1029,7 +986,6 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
             if (a.wt) {
               // write-through (sc1) 16-B store: a dependent kernel boundary otherwise pays
               // (dirty bytes / 6 TB/s) for the L2 write-back (MI355X_MICROARCH.md, row 'boundary')
-              typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
               __builtin_amdgcn_raw_buffer_store_b128((u32x4){ov.x, ov.y, ov.z, ov.w}, yrsrc, (int)(o * 2), 0, 16);
             } else {
               *reinterpret_cast<uint4*>(y + o) = ov;
@@ -1048,11 +1004,11 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
         }
       }
     }
-    if (half + 1 < EPH) lds_barrier();  // everyone has read this half before the next one is staged
+    if (half + 1 < EPH) lss_lds_barrier();  // everyone has read this half before the next one is staged
   }
   if (a.stamps != nullptr) {
     stamp(4);
-    wait_vmcnt<0>();  // stores acknowledged
+    lss_wait_vmcnt<0>();  // stores acknowledged
     stamp(5);
   }
 }
@@ -1109,8 +1065,7 @@ inline int s2d_taps(int K, int pad) {
 // May the KC = 32 fused kernel stage its low-res source pixels in LDS?  Its 10 x 18 patch must map
 // into the SRC_H x SRC_W = 7 x 11 source window: floor(9 ry) + 2 <= 7 and floor(17 rx) + 2 <= 11.
 inline int conv_src_lds_ok(const ConvArgs& a) {
-  if (const char* e = getenv("LSS_CONV_SRC"))
-    if (atoi(e) == 0) return 0;
+  if (!lss_env_on("LSS_CONV_SRC")) return 0;
   return a.up >= 2 && a.ry * 9.f < 4.99f && a.rx * 17.f < 8.99f;
 }
 
@@ -1166,7 +1121,7 @@ void launch_conv_lds(const ConvArgs& a, hipStream_t st) {
       // K loop over two 4-wave groups inside the workgroup - half the latency-bound steps each.
       const long long nwg1 = (long long)g.x * g.y;
       bool ksplit = MODE != 1 && nwg1 <= 256 && (a.Cin / 64) % 2 == 0 && a.Cin >= 128;
-      if (const char* e = getenv("LSS_CONV_KSPLIT")) ksplit = ksplit && atoi(e) != 0;
+      ksplit = ksplit && lss_env_on("LSS_CONV_KSPLIT");
       if constexpr (MODE != 1) {
         if (ksplit) {
           hipLaunchKernelGGL((conv_lds_kernel<1, 128, MODE, KH, KW, PAD, 64, 2>), g, dim3(512), 0, st, a, tilesX, tilesY);
@@ -1179,10 +1134,7 @@ void launch_conv_lds(const ConvArgs& a, hipStream_t st) {
 }
 
 // LSS_CONV_WT=0: write-back epilogue stores.  Read on every call, like every switch here: tests flip them in-process
-inline bool conv_wt_from_env() {
-  const char* e = getenv("LSS_CONV_WT");
-  return e == nullptr || atoi(e) != 0;
-}
+inline bool conv_wt_from_env() { return lss_env_on("LSS_CONV_WT"); }
 
 // The one fill of ConvArgs: geometry, activation word (`act` = ACT_* | LSS_OUT_F32), write-through, align_corners
 // ratios.  An entry checks its own arguments, calls this, then sets what only it has.  rc: 0 or LSS_E_SHAPE (no
@@ -1197,7 +1149,7 @@ ConvFill conv_args_fill(const void* x, const void* x2, const void* w, const floa
   ConvFill f = {};  // zero: one output (y2, split), no fused head (head_*), no LDS source staging (src_lds)
   f.rc = LSS_E_SHAPE;
   ConvArgs& a = f.a;
-  a.stamps = conv_stamps_from_env();
+  a.stamps = lss_env_device_ptr("LSS_CONV_STAMPS");  // u64 buffer, 8 entries per workgroup: switches the phase stamps on
   a.x = x; a.x2 = x2; a.w = w; a.scale = scale; a.shift = shift; a.residual = residual;
   a.y = y; a.stats = stats;
   a.B = B; a.H = H; a.W = W; a.Cx = Cx; a.C2 = C2; a.up = up;
@@ -1281,7 +1233,7 @@ extern "C" int lss_conv2d_fwd(const void* x, const void* x2, const void* w_packe
       return LSS_E_SHAPE;
     // write-back stores here (LSS_KS_WT=1: write-through like the other kernels): 5 MB of output per launch at most,
     // read back by the next launch - measured in a dependent chain 9.47 / 8.22 / 7.48 -> 9.07 / 8.11 / 7.36 us per launch
-    const bool wt_ks = getenv("LSS_KS_WT") != nullptr && atoi(getenv("LSS_KS_WT")) != 0;
+    const bool wt_ks = lss_env_set_on("LSS_KS_WT");
     return lss_conv_ks_launch(x, w_packed, scale, shift, residual, y, B, H, W, Cx, Cout, relu & 1, wt_ks ? 1 : 0,
                               lss_stream(stream));
   }

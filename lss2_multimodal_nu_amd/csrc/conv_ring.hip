@@ -34,11 +34,10 @@
 //   flags  FULL_W[slot] = fill count (weight loader), FREE_W[slot] = releases (consumers, LDS atomic add),
 //          FULL_P / FREE_P the same for the two patch buffers, FULL_S / FREE_S for the source window
 // Every flag wait is bounded (ring_prims.h); lss_conv2d_ring_timeouts() must read 0.
-#include <stdlib.h>
-
 #include <type_traits>
 
-#include "lss_common.h"
+#include "conv_launch.h"
+#include "lss_device.h"
 
 namespace {
 
@@ -106,10 +105,9 @@ constexpr int F_FULL_W = 0, F_FREE_W = 8, F_FULL_P = 16, F_FREE_P = 18, F_HEAD =
 // -fno-slp-vectorize): packed f32 VALU issued next to MFMAs costs ~20 cycles more per v_pk_fma_f32 than the two plain
 // FMAs it replaces (MI355X_MICROARCH.md, 'price of one filler beside MFMAs'), and the blend runs on SIMDs whose other
 // two waves issue MFMAs back to back; one v_cvt_pk_bf16_f32 per channel pair.
-typedef __attribute__((ext_vector_type(2))) float rk_f32x2;
 typedef __attribute__((ext_vector_type(2))) __bf16 rk_bf16x2;
 __device__ __forceinline__ unsigned int rk_pack_bf2(float lo, float hi) {
-  const rk_f32x2 v = {lo, hi};
+  const f32x2 v = {lo, hi};
   return __builtin_bit_cast(unsigned int, __builtin_convertvector(v, rk_bf16x2));
 }
 __device__ __forceinline__ uint4 rk_blend(const uint4& q00, const uint4& q01, const uint4& q10, const uint4& q11,
@@ -248,13 +246,13 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
     int slot = 0, gen = 1, pslot = 0, pgen = 1, inflight = 0;  // inflight = issued, not yet published
     auto publish_oldest = [&]() {
       switch (inflight) {  // all but the inflight - 1 youngest slabs have landed
-        case 1: rk_wait_vmcnt<0>(); break;
-        case 2: rk_wait_vmcnt<8>(); break;
-        case 3: rk_wait_vmcnt<16>(); break;
-        case 4: rk_wait_vmcnt<24>(); break;
-        case 5: rk_wait_vmcnt<32>(); break;
-        case 6: rk_wait_vmcnt<40>(); break;
-        default: rk_wait_vmcnt<48>(); break;
+        case 1: lss_wait_vmcnt<0>(); break;
+        case 2: lss_wait_vmcnt<8>(); break;
+        case 3: lss_wait_vmcnt<16>(); break;
+        case 4: lss_wait_vmcnt<24>(); break;
+        case 5: lss_wait_vmcnt<32>(); break;
+        case 6: lss_wait_vmcnt<40>(); break;
+        default: lss_wait_vmcnt<48>(); break;
       }
       rk_set(flags + F_FULL_W + pslot, pgen, lane);
       if (++pslot == NSL) { pslot = 0; ++pgen; }
@@ -280,14 +278,14 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
       unsigned char* dst = smem + L::RING + slot * RK_SLAB;
 #ifndef RK_DIAG_NOWDMA  // timing-only build: no weight traffic, the hand-off protocol alone
 #pragma unroll
-      for (int k = 0; k < 8; ++k) rk_glds16(wsrc + (size_t)i * RK_SLAB + k * 1024, dst + k * 1024);
+      for (int k = 0; k < 8; ++k) lss_glds16(wsrc + (size_t)i * RK_SLAB + k * 1024, dst + k * 1024);
 #endif
       ++inflight;
       if (inflight > LA) publish_oldest();
       if (++slot == NSL) { slot = 0; ++gen; }
     }
     while (inflight > 0) publish_oldest();
-    rk_wait_vmcnt<0>();  // (see the patch loaders' exit)
+    lss_wait_vmcnt<0>();  // (see the patch loaders' exit)
     write_stats();
     return;
   }
@@ -373,7 +371,7 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
 #pragma unroll
       for (int k = 0; k < NIT; ++k) {
         const void* src = poff[k] >= 0 ? (const void*)(xfull + poff[k] + c * RK_KC) : (const void*)lss_ring_zero_page;
-        rk_glds16(src, dst + (pw + k * RK_NPATCH) * 1024);
+        lss_glds16(src, dst + (pw + k * RK_NPATCH) * 1024);
       }
     };
     if (MODE == 0) {
@@ -383,14 +381,14 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
       issue_full(0, 0);
       if (a.nch > 1) {
         issue_full(1, 1);
-        rk_wait_vmcnt<NIT>();
+        lss_wait_vmcnt<NIT>();
       } else {
-        rk_wait_vmcnt<0>();
+        lss_wait_vmcnt<0>();
       }
       rk_add1(flags + F_FULL_P + 0, lane);
       for (int c = 0; c < a.nch; ++c) {
         if (c + 1 < a.nch) {
-          rk_wait_vmcnt<0>();
+          lss_wait_vmcnt<0>();
           rk_add1(flags + F_FULL_P + ((c + 1) & 1), lane);
         }
         if (c + 2 < a.nch) {
@@ -408,9 +406,9 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
           const int it = pw + k * RK_NPATCH;
           if (T22) {
             if (it < RK_TSRC_PIECE && it * 64 + lane < RK_TSRC_H * RK_TSRC_W * 4)
-              rk_glds16(a.x + src_o[k] + cx, smem + L::SRC + it * 1024);
+              lss_glds16(a.x + src_o[k] + cx, smem + L::SRC + it * 1024);
           } else if (it < RK_NS * 5 && (it % 5) * 64 + lane < RK_SRC_H * RK_SRC_W * 4) {
-            rk_glds16(a.x + src_o[k] + cx, smem + L::SRC + (it / 5) * RK_SRC_STRIP + (it % 5) * 1024);
+            lss_glds16(a.x + src_o[k] + cx, smem + L::SRC + (it / 5) * RK_SRC_STRIP + (it % 5) * 1024);
           }
         }
       };
@@ -427,7 +425,7 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
       };
       prepare(0);
       for (int c = 0; c < a.nch; ++c) {
-        rk_wait_vmcnt<0>();
+        lss_wait_vmcnt<0>();
         if (c >= nskip) {
           // every loader's share of the source window has landed / the consumers have released the patch buffer
           rk_add1(flags + F_FULL_S, lane);
@@ -480,7 +478,7 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
               finish(k + 1, qb);
             }
           }
-          rk_wait_lgkm0();  // the blended pieces are in LDS, and this wave's reads of the source window are done
+          lss_wait_lgkm0();  // the blended pieces are in LDS, and this wave's reads of the source window are done
           rk_add1(flags + F_FREE_S, lane);
         }
         if (c + 1 < a.nch && c + 1 >= nskip) prepare(c + 1);  // the next source window, as soon as this one is free
@@ -492,7 +490,7 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
     // handed to the next workgroup while the transfer still lands.  Every path above already ends behind a vmcnt(0)
     // (each chunk's pieces are waited for before they are published); this one is free and keeps that true for any
     // timing-only build that compiles waits out (the NOWAITW fault of round 3).
-    rk_wait_vmcnt<0>();
+    lss_wait_vmcnt<0>();
     write_stats();
     return;
   }
@@ -695,14 +693,12 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
   }
   const int oy = my_oy0 + (n >> 2);
   if (!HEAD) {
-    typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
     const __amdgpu_buffer_rsrc_t yrsrc = __builtin_amdgcn_make_buffer_rsrc(
         a.y, 0, a.wt ? (int)((size_t)a.B * a.Hin * a.Win * a.Cout * 2) : 0, 0x00020000);
     // Lane (q, n) holds 32 B of pixel n as two 16-B halves; stored as they lie, one instruction would write 16 B of
     // every 32-B sector and the write-through path sends each partial sector to HBM on its own (WRITE_SIZE = 2 x the
     // output, profiles/r03_hbm_traffic.json before this).  Two row swaps (v_permlane16_swap, v_permlane32_swap) hand
     // the q lanes of a pixel consecutive 16-B pieces: one instruction = 64 contiguous bytes per pixel.
-    typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
     const int chs = T.nb * 128 + cg * 64 + kq * 8;
 #pragma unroll
     for (int j = 0; j < 5; ++j) {
@@ -759,7 +755,7 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
     if (cg == 1) {
 #pragma unroll
       for (int j = 0; j < 5; ++j) hx[(j * 16 + n) * 4 + kq] = part[j];
-      rk_wait_lgkm0();
+      lss_wait_lgkm0();
       rk_set(flags + F_HEAD + sidx, 1, lane);
     } else {
       rk_wait_ge(flags + F_HEAD + sidx, 1);
@@ -885,10 +881,7 @@ int lss_conv_ring_launch(const void* x, const void* x2, const void* w_ring, cons
   a.nstrips = B * a.SX * a.SY;
   a.nblk = Cout / 128;
   a.nch = a.Cin / RK_KC;
-  {
-    const char* e = getenv("LSS_RING_STATS");
-    a.stats = e ? reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 16)) : nullptr;
-  }
+  a.stats = lss_env_device_ptr("LSS_RING_STATS");
   const bool fused = up > 1 || C2 > 0;
   // the shared 2 x 2 tile where the tiles cover the output exactly and its 10 x 42 patch interpolates from a 7 x 23
   // source window (up2 at 200^2); every other fused shape keeps one patch per strip

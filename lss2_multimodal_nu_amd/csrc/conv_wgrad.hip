@@ -23,9 +23,8 @@
 // s) then fall in 8 different 8-bank groups - conflict-free transposed reads for every tap.
 // Output: fp32 partial tiles [split][tap][Cout][Cin], reduced in split order by conv_grad.hip's wgrad_reduce_kernel
 // (fixed order: a training step is bit-reproducible).
-#include <stdlib.h>
-
-#include "lss_common.h"
+#include "conv_launch.h"
+#include "lss_device.h"
 
 namespace {
 
@@ -58,22 +57,6 @@ struct WgradArgs {
 
 __device__ __attribute__((aligned(128))) unsigned char lss_wgrad_zero_page[128];
 
-typedef __attribute__((ext_vector_type(4))) short wk_s16x4;
-typedef __attribute__((ext_vector_type(8))) short wk_s16x8;
-typedef __attribute__((ext_vector_type(8))) __bf16 wk_bf16x8;
-typedef __attribute__((ext_vector_type(4))) float wk_f32x4;
-
-__device__ __forceinline__ int wk_swz(int pos) { return ((pos >> 1) & 1) | (((pos >> 3) & 1) << 1); }
-
-// 4 positions x 16 channels, transposed: this lane's channel at the 4 positions
-__device__ __forceinline__ wk_s16x4 wk_tr(const unsigned char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) wk_s16x4*)p);
-}
-__device__ __forceinline__ wk_bf16x8 wk_frag(const unsigned char* lo, const unsigned char* hi) {
-  const wk_s16x4 a = wk_tr(lo), b = wk_tr(hi);
-  const wk_s16x8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  return __builtin_bit_cast(wk_bf16x8, v);
-}
 // Tap grid of one launch: NTY x NTX taps (one consumer wave each, <= 9), tap (ty, tx) = displacement (DY0 + ty,
 // tx - LP): the X row image keeps LP zero positions in front of x = 0, so a tap reads position (pixel + tx).
 // <3, 3, -1, 1>: the 3x3 / pad-1 conv.  <2, 4, -2, 2> + <2, 4, 0, 2>: the 4x4 taps {-2 .. 1}^2 of a 7x7 / 2 / pad-3
@@ -110,7 +93,7 @@ __global__ __launch_bounds__((NTY * NTX + 1 + WK_NXL) * 64) void conv_wgrad_kern
       const int i = wl + k * WK_NXL;
       const int idx = 8 * i + (lane >> 3), x = idx - LP;
       const int sb = (lane & 7) >> 1, half = lane & 1;
-      const int ch = ci0 + ((sb ^ wk_swz(idx)) << 4) + half * 8;
+      const int ch = ci0 + ((sb ^ lss_tr_swz(idx)) << 4) + half * 8;
       xoff[k] = (i < npieces && x >= 0 && x < a.W) ? x * a.Cin + ch : -1;
     }
     const unsigned char* zsrc = lss_wgrad_zero_page + (lane & 7) * 16;
@@ -134,14 +117,14 @@ __global__ __launch_bounds__((NTY * NTX + 1 + WK_NXL) * 64) void conv_wgrad_kern
           int xo = xoff[kk];
           asm volatile("" : "+v"(xo));  // keeps the 64-bit addresses out of loop-invariant registers
           const void* src = (real && xo >= 0) ? (const void*)(rowp + xo) : (const void*)zsrc;
-          rk_glds16(src, dst + i * 1024);
+          lss_glds16(src, dst + i * 1024);
         }
       }
-      rk_wait_vmcnt<0>();
+      lss_wait_vmcnt<0>();
       rk_add1(flags + F_FULL_X + slot, lane);
       if (++slot == a.nxs) { slot = 0; ++uses; }
     }
-    rk_wait_vmcnt<0>();  // never end a loader wave with LDS-DMA in flight (every fill above is already drained)
+    lss_wait_vmcnt<0>();  // never end a loader wave with LDS-DMA in flight (every fill above is already drained)
     return;
   }
 
@@ -152,7 +135,7 @@ __global__ __launch_bounds__((NTY * NTX + 1 + WK_NXL) * 64) void conv_wgrad_kern
     for (int i = 0; i < 4; ++i) {
       const int pos = 8 * i + (lane >> 3);
       const int sb = (lane & 7) >> 1, half = lane & 1;
-      doff[i] = pos * a.Cout + co0 + ((sb ^ wk_swz(pos)) << 4) + half * 8;
+      doff[i] = pos * a.Cout + co0 + ((sb ^ lss_tr_swz(pos)) << 4) + half * 8;
     }
     const unsigned char* zsrc = lss_wgrad_zero_page + (lane & 7) * 16;
     int slot = 0, uses = 0;   // uses = earlier fills of `slot`
@@ -166,7 +149,7 @@ __global__ __launch_bounds__((NTY * NTX + 1 + WK_NXL) * 64) void conv_wgrad_kern
         if (uses > 0 && rk_peek(flags + F_FREE_D + slot) < WK_NCONS * uses) {
           // about to block on the consumers: everything issued so far must be visible to them first
           if (prev >= 0) {
-            rk_wait_vmcnt<0>();
+            lss_wait_vmcnt<0>();
             rk_add1(flags + F_FULL_D + prev, lane);
             prev = -1;
           }
@@ -179,10 +162,10 @@ __global__ __launch_bounds__((NTY * NTX + 1 + WK_NXL) * 64) void conv_wgrad_kern
           int dof = doff[i];
           asm volatile("" : "+v"(dof));
           const void* src = x < a.W ? (const void*)(rowp + 32 * j * a.Cout + dof) : (const void*)zsrc;
-          rk_glds16(src, dst + i * 1024);
+          lss_glds16(src, dst + i * 1024);
         }
         if (prev >= 0) {  // the block before this one has landed once at most these 4 pieces are outstanding
-          rk_wait_vmcnt<4>();
+          lss_wait_vmcnt<4>();
           rk_add1(flags + F_FULL_D + prev, lane);
         }
         prev = slot;
@@ -190,7 +173,7 @@ __global__ __launch_bounds__((NTY * NTX + 1 + WK_NXL) * 64) void conv_wgrad_kern
       }
     }
     if (prev >= 0) {
-      rk_wait_vmcnt<0>();
+      lss_wait_vmcnt<0>();
       rk_add1(flags + F_FULL_D + prev, lane);
     }
     return;
@@ -205,15 +188,15 @@ __global__ __launch_bounds__((NTY * NTX + 1 + WK_NXL) * 64) void conv_wgrad_kern
     const int pa = 8 * g + 4 * h + q, pb = pa + kx;
 #pragma unroll
     for (int ct = 0; ct < 4; ++ct) {
-      aoff[h][ct] = pa * 128 + ((ct ^ wk_swz(pa)) << 5) + p * 8;
-      boff[h][ct] = pb * 128 + ((ct ^ wk_swz(pb)) << 5) + p * 8;
+      aoff[h][ct] = pa * 128 + ((ct ^ lss_tr_swz(pa)) << 5) + p * 8;
+      boff[h][ct] = pb * 128 + ((ct ^ lss_tr_swz(pb)) << 5) + p * 8;
     }
   }
-  wk_f32x4 acc[4][4];
+  f32x4 acc[4][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (wk_f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   int dslot = 0, dfill = 1;      // dY ring position and the fill count that makes its block valid
   int xslot = ky, xfill = 1;     // row slot of this tap's row of tile 0 (row k = t + ky), its fill count
@@ -233,11 +216,11 @@ __global__ __launch_bounds__((NTY * NTX + 1 + WK_NXL) * 64) void conv_wgrad_kern
         rk_wait_ge(flags + F_FULL_D + dslot, dfill);
         const unsigned char* db = smem + DBASE + dslot * WK_BLK;
         const unsigned char* xj = xb + j * WK_BLK;
-        wk_bf16x8 fa[4], fb[4];
+        bf16x8_t fa[4], fb[4];
 #pragma unroll
-        for (int ct = 0; ct < 4; ++ct) fa[ct] = wk_frag(db + aoff[0][ct], db + aoff[1][ct]);
+        for (int ct = 0; ct < 4; ++ct) fa[ct] = lss_tr_frag(db + aoff[0][ct], db + aoff[1][ct]);
 #pragma unroll
-        for (int ct = 0; ct < 4; ++ct) fb[ct] = wk_frag(xj + boff[0][ct], xj + boff[1][ct]);
+        for (int ct = 0; ct < 4; ++ct) fb[ct] = lss_tr_frag(xj + boff[0][ct], xj + boff[1][ct]);
         // LDS operations of a wave execute in order: the add is performed after the reads above have been
         rk_add1(flags + F_FREE_D + dslot, lane);
 #pragma unroll
@@ -297,8 +280,7 @@ WgradPlan wgrad_plan(int B, int H, int W, int Cin, int Cout) {
 
 // internal (conv_grad.hip): is (shape) a case for the direct kernel, how many fp32 partial tiles it writes
 int lss_wgrad_direct_splits(int B, int H, int W, int Cin, int Cout) {
-  const char* e = getenv("LSS_WGRAD_DIRECT");
-  if (e != nullptr && atoi(e) == 0) return 0;
+  if (!lss_env_on("LSS_WGRAD_DIRECT")) return 0;
   const WgradPlan p = wgrad_plan(B, H, W, Cin, Cout);
   return p.ok ? p.nsplit : 0;
 }

@@ -327,8 +327,6 @@ __global__ void deform_zero_words_kernel(unsigned int* __restrict__ p, int n) {
   for (int i = threadIdx.x; i < n; i += blockDim.x) p[i] = 0u;
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 inline int ceil_log2(long long n) {
   int k = 0;
   while ((1LL << k) < n) ++k;
@@ -354,8 +352,8 @@ extern "C" int lss_deform_attn_bwd(const float* value, const float* offsets_logi
   if (ref_bstride < 0) return LSS_E_SHAPE;
   const long long HW = (long long)H * W, rows = (long long)B * HW;
   if (rows >= (1LL << 31) || B > 65535) return LSS_E_SHAPE;
-  if (!aligned16(value) || !aligned16(offsets_logits) || !aligned16(d_out) || !aligned16(workspace) ||
-      !aligned16(d_value) || !aligned16(d_offsets_logits))
+  if (!lss_aligned(value, 16) || !lss_aligned(offsets_logits, 16) || !lss_aligned(d_out, 16) || !lss_aligned(workspace, 16) ||
+      !lss_aligned(d_value, 16) || !lss_aligned(d_offsets_logits, 16))
     return LSS_E_ALIGN;
   if ((reinterpret_cast<uintptr_t>(ref_pts) & 7) != 0 || (ref_bstride & 1) != 0) return LSS_E_ALIGN;
   if (workspace_bytes < lss_deform_attn_bwd_workspace_bytes(B, H, W)) return LSS_E_WORKSPACE;

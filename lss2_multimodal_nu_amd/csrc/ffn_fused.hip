@@ -21,7 +21,7 @@
 // destination is lane-linear) and on every read / write address - conflict-free ds_read_b128.
 // The bf16 rounding points (x, H, the weights) and the k order of both sums are those of the
 // two-launch path, so the two agree to fp32 rounding.
-#include "lss_common.h"
+#include "lss_device.h"
 
 namespace {
 
@@ -52,28 +52,6 @@ struct FfnArgs {
   float ln_eps;
   unsigned short* y_ln;
 };
-
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-// erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7), as in linear_mfma.hip's GELU epilogue
-__device__ __forceinline__ float fast_erf(float x) {
-  const float ax = fabsf(x);
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.f));  // v_rcp_f32 (1 ulp); __frcp_rn is a 12-instruction IEEE division
-  float p = fmaf(1.061405429f, t, -1.453152027f);
-  p = fmaf(p, t, 1.421413741f);
-  p = fmaf(p, t, -0.284496736f);
-  p = fmaf(p, t, 0.254829592f);
-  const float y = 1.f - p * t * __expf(-ax * ax);
-  return copysignf(y, x);
-}
-__device__ __forceinline__ float gelu(float v) { return 0.5f * v * (1.f + fast_erf(v * 0.70710678118654752f)); }
 
 // PROJ = false: the feed-forward block.  PROJ = true: one linear layer with the same register-resident rows,
 // y = x . W2^T + b2 + res (W2 (256, F) with F = the layer's input width = 256: chunk c multiplies x's columns
@@ -116,11 +94,11 @@ __global__ __launch_bounds__(512, 1) void ffn_fused_kernel(FfnArgs a) {
     if (!PROJ) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        glds16(a.w1 + (size_t)j * HC * D + w1o[i], smem + OFF_W1 + buf * W1_BYTES + (wave * 4 + i) * 1024);
+        lss_glds16(a.w1 + (size_t)j * HC * D + w1o[i], smem + OFF_W1 + buf * W1_BYTES + (wave * 4 + i) * 1024);
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      glds16(a.w2 + (size_t)j * HC + w2o[i], smem + OFF_W2 + buf * W2_BYTES + (wave * 4 + i) * 1024);
+      lss_glds16(a.w2 + (size_t)j * HC + w2o[i], smem + OFF_W2 + buf * W2_BYTES + (wave * 4 + i) * 1024);
   };
 
   f32x16 acc2[4];
@@ -150,17 +128,17 @@ __global__ __launch_bounds__(512, 1) void ffn_fused_kernel(FfnArgs a) {
     for (int c = 0; c < D / HC; ++c)
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        glds16(a.w2 + (size_t)c * HC + w2o[i], smem + c * W2_BYTES + (wave * 4 + i) * 1024);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    lds_barrier();
+        lss_glds16(a.w2 + (size_t)c * HC + w2o[i], smem + c * W2_BYTES + (wave * 4 + i) * 1024);
+    lss_wait_vmcnt<0>();
+    lss_lds_barrier();
   } else {
     issue(0, 0);
   }
   for (int j = 0; j < nchunks; ++j) {
     const int buf = j & 1;
     if (!PROJ) {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      lds_barrier();  // (a): chunk j's weights are in LDS; every wave is done with chunk j-1
+      lss_wait_vmcnt<0>();
+      lss_lds_barrier();  // (a): chunk j's weights are in LDS; every wave is done with chunk j-1
       if (j + 1 < nchunks) issue(j + 1, buf ^ 1);
     }
 
@@ -180,11 +158,11 @@ __global__ __launch_bounds__(512, 1) void ffn_fused_kernel(FfnArgs a) {
       for (int g = 0; g < 4; ++g) {
         const f32x4 bb = *reinterpret_cast<const f32x4*>(b1s + j * HC + cg * 32 + 8 * g + 4 * h);
         uint2 pk;
-        pk.x = lss_pack_bf2(gelu(acc1[4 * g] + bb[0]), gelu(acc1[4 * g + 1] + bb[1]));
-        pk.y = lss_pack_bf2(gelu(acc1[4 * g + 2] + bb[2]), gelu(acc1[4 * g + 3] + bb[3]));
+        pk.x = lss_pack_bf2(lss_gelu(acc1[4 * g] + bb[0]), lss_gelu(acc1[4 * g + 1] + bb[1]));
+        pk.y = lss_pack_bf2(lss_gelu(acc1[4 * g + 2] + bb[2]), lss_gelu(acc1[4 * g + 3] + bb[3]));
         *reinterpret_cast<uint2*>(hbuf + hrow + (((cg * 4 + g) ^ hx) << 4) + h * 8) = pk;
       }
-      lds_barrier();  // (b): H_j complete
+      lss_lds_barrier();  // (b): H_j complete
     }
 
     // GEMM2: Y[tokens rg*32.., n cg*128..] += H_j . W2_j^T over k = 64
@@ -220,7 +198,7 @@ __global__ __launch_bounds__(512, 1) void ffn_fused_kernel(FfnArgs a) {
     rres[q] = make_uint4(0, 0, 0, 0);
     if (m < a.M) rres[q] = *reinterpret_cast<const uint4*>(a.res + (size_t)m * D + (tid & 31) * 8);
   }
-  lds_barrier();  // every wave is done reading the last chunk's buffers
+  lss_lds_barrier();  // every wave is done reading the last chunk's buffers
   float* otile = reinterpret_cast<float*>(smem);
 #pragma unroll
   for (int ct = 0; ct < 4; ++ct) {
@@ -232,7 +210,7 @@ __global__ __launch_bounds__(512, 1) void ffn_fused_kernel(FfnArgs a) {
       otile[row * OLD + n] = acc2[ct][i] + bias;
     }
   }
-  lds_barrier();
+  lss_lds_barrier();
   {
     const int c8 = tid & 31, row0 = tid >> 5;  // 512 threads = 16 rows x 32 channel groups per pass
     // LayerNorm scale / shift of this thread's 8 channels: the same for every pass (loaded once, not per pass -

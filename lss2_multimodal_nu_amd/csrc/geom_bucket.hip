@@ -584,9 +584,8 @@ int lss_depthnet_voxels(const lss_lift_splat_desc_t& d, const LssRegionPlan* pla
   a.voxel = d.voxel; a.vox_count = plan != nullptr ? nullptr : d.vox_count;
   a.use_regions = plan != nullptr;
   a.diag = getenv("LSS_K2K3_DIAG") ? atoi(getenv("LSS_K2K3_DIAG")) : 0;
-  a.k2_xcd = getenv("LSS_K2_XCD") == nullptr || atoi(getenv("LSS_K2_XCD")) != 0;
-  a.stamps = getenv("LSS_L1_STAMPS") ? reinterpret_cast<unsigned long long*>(strtoull(getenv("LSS_L1_STAMPS"), nullptr, 16))
-                                     : nullptr;
+  a.k2_xcd = lss_env_on("LSS_K2_XCD");
+  a.stamps = lss_env_device_ptr("LSS_L1_STAMPS");
   if (plan != nullptr) {
     if (plan->n2 != a.n2 || plan->rps != plan->nRx * plan->nRy) return LSS_E_WORKSPACE;
     a.rg.region_count = plan->region_count; a.rg.region_cursor = plan->region_cursor;
@@ -609,7 +608,7 @@ int lss_depthnet_voxels(const lss_lift_splat_desc_t& d, const LssRegionPlan* pla
     for (int i = 0; i < B * N * 24; ++i) cal.v[i] = calib_host[i];
   }
   // the row-split K2 (region pipeline, the shapes of the LSS depthnet: D <= 48, C <= 64, Cin a multiple of 128)
-  static const bool rows_off = getenv("LSS_K2_ROWS") != nullptr && atoi(getenv("LSS_K2_ROWS")) == 0;
+  static const bool rows_off = !lss_env_on("LSS_K2_ROWS");
   const int nd16 = (D + 15) / 16;
   if (plan != nullptr && !rows_off && (nd16 == 3 || nd16 == 4) && (C + 15) / 16 == 4 && Cin % 128 == 0 &&
       ((size_t)D * Cin * sizeof(float)) % 16 == 0) {

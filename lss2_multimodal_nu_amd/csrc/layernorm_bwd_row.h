@@ -4,32 +4,12 @@
 #pragma once
 #include <algorithm>
 
-#include "lss_common.h"
+#include "lss_device.h"
 
 namespace {
 
 constexpr int LN_C = 256;
 constexpr int LN_MAXGROUPS = 1024;
-
-template <typename T>
-__device__ __forceinline__ f32x4 ln_load4(const T* p);
-template <>
-__device__ __forceinline__ f32x4 ln_load4<float>(const float* p) {
-  return *reinterpret_cast<const f32x4*>(p);
-}
-template <>
-__device__ __forceinline__ f32x4 ln_load4<unsigned short>(const unsigned short* p) {
-  const uint2 v = *reinterpret_cast<const uint2*>(p);
-  return (f32x4){lss_bf2f((unsigned short)(v.x & 0xffff)), lss_bf2f((unsigned short)(v.x >> 16)),
-                 lss_bf2f((unsigned short)(v.y & 0xffff)), lss_bf2f((unsigned short)(v.y >> 16))};
-}
-__device__ __forceinline__ void ln_store4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
-__device__ __forceinline__ void ln_store4(unsigned short* p, f32x4 v) {
-  uint2 o;
-  o.x = lss_pack_bf2(v[0], v[1]);
-  o.y = lss_pack_bf2(v[2], v[3]);
-  *reinterpret_cast<uint2*>(p) = o;
-}
 
 // One row held by a whole wave (v: the input, gr: the incoming gradient, gm: gamma; this lane's 4 channels) -> this
 // lane's 4 input gradients; adds the row's terms to dg (dgamma) and dbt (dbeta).
@@ -106,7 +86,5 @@ inline LnSplit ln_split(long long rows) {
   sp.G = (int)((rows + sp.rpg - 1) / sp.rpg);
   return sp;
 }
-
-inline bool lg_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 }  // namespace

@@ -33,8 +33,8 @@
 //   Row ranges: groups = min(ceil(rows / 4), 1024), rows per group = ceil(rows / groups).
 #include <algorithm>
 
-#include "layernorm_bwd_row.h"  // the LayerNorm backward's row arithmetic, lg_sum_splits, ln_split, lg_aligned
-#include "lss_common.h"
+#include "layernorm_bwd_row.h"  // the LayerNorm backward's row arithmetic, lg_sum_splits, ln_split
+#include "lss_device.h"
 
 namespace {
 
@@ -56,23 +56,6 @@ struct LinWgradArgs {
   int want_dw, want_db;
 };
 
-typedef __attribute__((ext_vector_type(4))) short lg_s16x4;
-typedef __attribute__((ext_vector_type(8))) short lg_s16x8;
-typedef __attribute__((ext_vector_type(8))) __bf16 lg_bf16x8;
-typedef __attribute__((ext_vector_type(4))) float lg_f32x4;
-
-__device__ __forceinline__ int lg_swz(int pos) { return ((pos >> 1) & 1) | (((pos >> 3) & 1) << 1); }
-
-// 4 tokens x 16 channels, transposed: this lane's channel at the 4 tokens
-__device__ __forceinline__ lg_s16x4 lg_tr(const unsigned char* p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) lg_s16x4*)p);
-}
-__device__ __forceinline__ lg_bf16x8 lg_frag(const unsigned char* lo, const unsigned char* hi) {
-  const lg_s16x4 a = lg_tr(lo), b = lg_tr(hi);
-  const lg_s16x8 v = {a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-  return __builtin_bit_cast(lg_bf16x8, v);
-}
-
 __global__ __launch_bounds__(256) void linear_wgrad_kernel(const LinWgradArgs a) {
   __shared__ __attribute__((aligned(1024))) unsigned char smem[2 * LG_BUF];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -90,7 +73,7 @@ __global__ __launch_bounds__(256) void linear_wgrad_kernel(const LinWgradArgs a)
 
   // staging: thread = token p32 of each of the stage's four 32-token blocks, 16-B piece c of its 128-B row
   const int p32 = tid >> 3, c = tid & 7;
-  const int soff = p32 * 128 + (((c >> 1) ^ lg_swz(p32)) << 5) + (c & 1) * 16;
+  const int soff = p32 * 128 + (((c >> 1) ^ lss_tr_swz(p32)) << 5) + (c & 1) * 16;
   uint4 rd[4], rx[4];
   auto fetch = [&](int st) {
     const long long tb = (long long)(st0 + st) * LG_TOK + p32;
@@ -119,7 +102,7 @@ __global__ __launch_bounds__(256) void linear_wgrad_kernel(const LinWgradArgs a)
       for (int j = 0; j < 4; ++j) {
         const unsigned int w4[4] = {rd[j].x, rd[j].y, rd[j].z, rd[j].w};
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
+        for (int e = 0; e < 4; ++e) {  // lss_unpack8's loop with the adds inside (unpacking first moves the schedule)
           dbacc[2 * e] += lss_bf2f((unsigned short)(w4[e] & 0xffffu));
           dbacc[2 * e + 1] += lss_bf2f((unsigned short)(w4[e] >> 16));
         }
@@ -135,13 +118,13 @@ __global__ __launch_bounds__(256) void linear_wgrad_kernel(const LinWgradArgs a)
   for (int h = 0; h < 2; ++h) {
     const int pa = 8 * g + 4 * h + q;
 #pragma unroll
-    for (int ct = 0; ct < 4; ++ct) roff[h][ct] = pa * 128 + ((ct ^ lg_swz(pa)) << 5) + p * 8;
+    for (int ct = 0; ct < 4; ++ct) roff[h][ct] = pa * 128 + ((ct ^ lss_tr_swz(pa)) << 5) + p * 8;
   }
-  lg_f32x4 acc[4][4];
+  f32x4 acc[4][4];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (lg_f32x4){0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
   fetch(0);
   put(0);
@@ -152,11 +135,11 @@ __global__ __launch_bounds__(256) void linear_wgrad_kernel(const LinWgradArgs a)
     if (do_dw) {
       const unsigned char* db_ = smem + (s & 1) * LG_BUF + wave * LG_BLK;
       const unsigned char* xb = db_ + LG_OPER;
-      lg_bf16x8 fa[4], fb[4];
+      bf16x8_t fa[4], fb[4];
 #pragma unroll
-      for (int ct = 0; ct < 4; ++ct) fa[ct] = lg_frag(db_ + roff[0][ct], db_ + roff[1][ct]);
+      for (int ct = 0; ct < 4; ++ct) fa[ct] = lss_tr_frag(db_ + roff[0][ct], db_ + roff[1][ct]);
 #pragma unroll
-      for (int ct = 0; ct < 4; ++ct) fb[ct] = lg_frag(xb + roff[0][ct], xb + roff[1][ct]);
+      for (int ct = 0; ct < 4; ++ct) fb[ct] = lss_tr_frag(xb + roff[0][ct], xb + roff[1][ct]);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -237,9 +220,9 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const TX* __restrict
   const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + 4 * lane);
   f32x4 dg = (f32x4){0.f, 0.f, 0.f, 0.f}, dbt = (f32x4){0.f, 0.f, 0.f, 0.f};
   for (long long row = r0 + wave; row < r1; row += 4) {  // whole waves: the shuffles of ln_bwd_row see all 64 lanes
-    const f32x4 v = ln_load4<TX>(x + row * LN_C + 4 * lane);
-    const f32x4 gr = ln_load4<TG>(dy + row * LN_C + 4 * lane);
-    ln_store4(dx + row * LN_C + 4 * lane, ln_bwd_row(v, gr, gm, eps, dg, dbt));
+    const f32x4 v = lss_load4<TX>(x + row * LN_C + 4 * lane);
+    const f32x4 gr = lss_load4<TG>(dy + row * LN_C + 4 * lane);
+    lss_store4(dx + row * LN_C + 4 * lane, ln_bwd_row(v, gr, gm, eps, dg, dbt));
   }
   ln_bwd_write_partial(red, dg, dbt, part);
 }
@@ -265,8 +248,8 @@ extern "C" int lss_linear_wgrad(const void* x, const void* dy, int T, int N, int
   if (dw != nullptr) LSS_CHECK_PTR(x);
   if (dw == nullptr && db == nullptr) return LSS_E_NULL;
   if (!lss_linear_wgrad_ok(T, N, K)) return LSS_E_SHAPE;
-  if (!lg_aligned(x, 16) || !lg_aligned(dy, 16) || !lg_aligned(workspace, 16) || !lg_aligned(dw, 4) ||
-      !lg_aligned(db, 4))
+  if (!lss_aligned(x, 16) || !lss_aligned(dy, 16) || !lss_aligned(workspace, 16) || !lss_aligned(dw, 4) ||
+      !lss_aligned(db, 4))
     return LSS_E_ALIGN;
   if (workspace_bytes < lss_linear_wgrad_workspace_bytes(T, N, K)) return LSS_E_WORKSPACE;
   const LinSplit sp = lin_split(T, N, K);
@@ -308,8 +291,8 @@ extern "C" int lss_layernorm_bwd(const void* x, int x_dt, const void* dy, int dy
   if (!lss_layernorm_bwd_ok(rows, C)) return LSS_E_SHAPE;
   for (int dt : {x_dt, dy_dt, dx_dt})
     if (dt != LSS_DT_F32 && dt != LSS_DT_BF16) return LSS_E_LAYOUT;
-  if (!lg_aligned(x, 16) || !lg_aligned(dy, 16) || !lg_aligned(gamma, 16) || !lg_aligned(dx, 16) ||
-      !lg_aligned(workspace, 16) || !lg_aligned(dgamma, 4) || !lg_aligned(dbeta, 4))
+  if (!lss_aligned(x, 16) || !lss_aligned(dy, 16) || !lss_aligned(gamma, 16) || !lss_aligned(dx, 16) ||
+      !lss_aligned(workspace, 16) || !lss_aligned(dgamma, 4) || !lss_aligned(dbeta, 4))
     return LSS_E_ALIGN;
   if (workspace_bytes < lss_layernorm_bwd_workspace_bytes(rows)) return LSS_E_WORKSPACE;
   const LnSplit sp = ln_split(rows);

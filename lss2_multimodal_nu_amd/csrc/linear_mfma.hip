@@ -19,7 +19,8 @@
 // Epilogue as in conv_mfma.hip: scale/shift in registers -> fp32 tile in LDS ->
 // 8 consecutive channels per thread, residual / activation / one 16-B (bf16) or
 // 32-B (fp32) store.
-#include "lss_common.h"
+#include "conv_launch.h"
+#include "lss_device.h"
 
 namespace {
 
@@ -54,35 +55,9 @@ constexpr int OUT_BYTES = (BM / 2) * OLD * 4;         // the output tile is stag
 constexpr int SMEM_BYTES = RING_BYTES > OUT_BYTES ? RING_BYTES : OUT_BYTES;
 static_assert(SMEM_BYTES <= 53 * 1024, "three workgroups per CU");
 
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
-}
-// erf by Abramowitz & Stegun 7.1.26 (|error| <= 1.5e-7, far below a bf16 ulp): libm's erff
-// costs ~40 VALU instructions per element, which on a 1024-wide GELU layer is as much
-// time as the GEMM itself.  (The fp32 parity path - conv_direct_kernel - keeps erff.)
-__device__ __forceinline__ float fast_erf(float x) {
-  const float ax = fabsf(x);
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.f));  // v_rcp_f32 (1 ulp); __frcp_rn is a 12-instruction IEEE division
-  float p = fmaf(1.061405429f, t, -1.453152027f);
-  p = fmaf(p, t, 1.421413741f);
-  p = fmaf(p, t, -0.284496736f);
-  p = fmaf(p, t, 0.254829592f);
-  const float y = 1.f - p * t * __expf(-ax * ax);
-  return copysignf(y, x);
-}
 __device__ __forceinline__ float act_fn(float v, int act) {
   if (act == 1) return fmaxf(v, 0.f);
-  if (act == 2) return 0.5f * v * (1.f + fast_erf(v * 0.70710678118654752f));
+  if (act == 2) return lss_gelu(v);
   return v;
 }
 
@@ -126,7 +101,7 @@ __global__ __launch_bounds__(256, 3) void linear_mfma_kernel(LinearArgs a) {
   auto issue = [&](int step, int slot) {
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      glds16(gbase + goff[i] + (size_t)step * BK, smem + slot * SLOT_BYTES + dma_off + i * 1024);
+      lss_glds16(gbase + goff[i] + (size_t)step * BK, smem + slot * SLOT_BYTES + dma_off + i * 1024);
   };
 
   // fragment read offsets within a slot: k-step s of lane half h reads 16-B piece 2h + s
@@ -153,10 +128,10 @@ __global__ __launch_bounds__(256, 3) void linear_mfma_kernel(LinearArgs a) {
   issue(0, 0);
   if (nsteps > 1) issue(1, 1);
   if (nsteps > 2) issue(2, 2);
-  if (nsteps > 2) wait_vmcnt<8>();
-  else if (nsteps > 1) wait_vmcnt<4>();
-  else wait_vmcnt<0>();
-  lds_barrier();
+  if (nsteps > 2) lss_wait_vmcnt<8>();
+  else if (nsteps > 1) lss_wait_vmcnt<4>();
+  else lss_wait_vmcnt<0>();
+  lss_lds_barrier();
 
   bf16x8 fa[2][2], fb[2][2];  // [k-step][tile]
   auto read = [&](int s, int slot) {
@@ -179,9 +154,9 @@ __global__ __launch_bounds__(256, 3) void linear_mfma_kernel(LinearArgs a) {
         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0][i], fb[0][j], acc[i][j], 0, 0, 0);
     // slab step+1 must have landed in every wave's share before anyone reads it; the younger slab
     // (step+2) stays in flight across the barrier
-    if (step + 2 < nsteps) wait_vmcnt<4>();
-    else wait_vmcnt<0>();
-    lds_barrier();  // (also: every fragment of THIS slot is in registers now, in every wave)
+    if (step + 2 < nsteps) lss_wait_vmcnt<4>();
+    else lss_wait_vmcnt<0>();
+    lss_lds_barrier();  // (also: every fragment of THIS slot is in registers now, in every wave)
     // ... so the slot just consumed is free: the slab three steps ahead goes into it (a 3-slot
     // ring that runs 3 steps ahead)
     if (step + 3 < nsteps) issue(step + 3, slot);
@@ -194,7 +169,7 @@ __global__ __launch_bounds__(256, 3) void linear_mfma_kernel(LinearArgs a) {
       for (int j = 0; j < 2; ++j)
         acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1][i], fb[1][j], acc[i][j], 0, 0, 0);
   }
-  lds_barrier();  // ring no longer read: reuse it as the fp32 output tile
+  lss_lds_barrier();  // ring no longer read: reuse it as the fp32 output tile
 
   // D[row = (e&3) + 8*(e>>2) + 4*h][col = r]: a lane holds one column of 16 rows.  The fp32 tile
   // is staged in two 64-row halves (waves wr = 0, then wr = 1) so it fits the ring's 48 KiB.
@@ -221,7 +196,7 @@ __global__ __launch_bounds__(256, 3) void linear_mfma_kernel(LinearArgs a) {
           }
       }
     }
-    lds_barrier();
+    lss_lds_barrier();
     for (int e = tid; e < (BM / 2) * (BN / 8); e += 256) {
       const int row = e / (BN / 8), c8 = e % (BN / 8);
       const int m = m0 + half * (BM / 2) + row, co = n0 + c8 * 8;
@@ -268,7 +243,7 @@ __global__ __launch_bounds__(256, 3) void linear_mfma_kernel(LinearArgs a) {
         }
       }
     }
-    if (half == 0) lds_barrier();  // everyone has read half 0 before half 1 is staged
+    if (half == 0) lss_lds_barrier();  // everyone has read half 0 before half 1 is staged
   }
 }
 

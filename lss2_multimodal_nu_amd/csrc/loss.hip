@@ -6,7 +6,7 @@
 // The logits are 4 channels x 160 k pixels: pure bandwidth, so one pass reads them and writes
 // per-workgroup partial sums (fixed order -> bit-reproducible), and the backward pass re-reads
 // them to write grad = g * w[t] * (softmax - onehot) / sum w without storing the softmax.
-#include "lss_common.h"
+#include "lss_device.h"
 
 namespace {
 
@@ -154,20 +154,16 @@ namespace {
 constexpr int HC_MAXK = 8;
 constexpr int HC_BLOCKS = 512;
 
-template <int DPP>
-__device__ __forceinline__ float hc_dpp(float x) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), DPP, 0xf, 0xf, false));
-}
 // sum over the LPP lanes of a pixel (every lane gets the total): xor 1, xor 2 (quad_perm), half-mirror - the 8 lanes
 // of a 64-channel pixel, half a DPP row - and for the 16 lanes of a 128-channel pixel the row mirror, which for 8 lanes
 // would add the neighbouring pixel
 template <int LPP>
 __device__ __forceinline__ float hc_pixel_sum(float v) {
   static_assert(LPP == 8 || LPP == 16, "a pixel sits on 8 or 16 lanes");
-  v += hc_dpp<0xB1>(v);
-  v += hc_dpp<0x4E>(v);
-  v += hc_dpp<0x141>(v);
-  if constexpr (LPP == 16) v += hc_dpp<0x140>(v);
+  v += lss_dpp_f32<0xB1>(v);
+  v += lss_dpp_f32<0x4E>(v);
+  v += lss_dpp_f32<0x141>(v);
+  if constexpr (LPP == 16) v += lss_dpp_f32<0x140>(v);
   return v;
 }
 

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #include "../../include/lss_hip.h"
 
@@ -29,6 +30,27 @@ static inline int lss_launch_status() {
 static inline hipStream_t lss_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 
 static inline int lss_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// is p a multiple of a (a power of two)?
+static inline bool lss_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+// Developer switches from the environment.  Each call reads the environment: a site that tests flip in-process calls
+// these per launch, a site that may not change within a process keeps the result in a `static const`.
+// A switch that is on by default: unset or non-zero.
+static inline bool lss_env_on(const char* name) {
+  const char* e = getenv(name);
+  return e == nullptr || atoi(e) != 0;
+}
+// A switch that is off by default: set and non-zero.
+static inline bool lss_env_set_on(const char* name) {
+  const char* e = getenv(name);
+  return e != nullptr && atoi(e) != 0;
+}
+// A device address in hex (the diagnostics' stamp / counter buffers), or null when unset.
+static inline unsigned long long* lss_env_device_ptr(const char* name) {
+  const char* e = getenv(name);
+  return e ? reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 16)) : nullptr;
+}
 
 typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(16))) float f32x16;

@@ -270,8 +270,6 @@ void se_launch_logits(int dtype, bool vec, int grid, hipStream_t st, const void*
   }
 }
 
-inline bool se_aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 }  // namespace
 
 extern "C" size_t lss_seg_eval_workspace_bytes(int C) {
@@ -288,12 +286,12 @@ extern "C" int lss_seg_eval_update(const void* logits, int dtype, const long lon
   if (HW <= 0 || C > SE_MAXC || HW >= (1LL << 31) || (long long)B * HW >= (1LL << 31)) return LSS_E_SHAPE;
   if (dtype != LSS_DT_F32 && dtype != LSS_DT_BF16) return LSS_E_LAYOUT;
   const uintptr_t esz = dtype == LSS_DT_BF16 ? 2 : 4;
-  if (!se_aligned(logits, esz) || !se_aligned(target, 8) || !se_aligned(workspace, 4) || !se_aligned(confmat, 8) ||
-      !se_aligned(class_weight, 4) || !se_aligned(batch_loss, 4) || !se_aligned(loss_acc, 8))
+  if (!lss_aligned(logits, esz) || !lss_aligned(target, 8) || !lss_aligned(workspace, 4) || !lss_aligned(confmat, 8) ||
+      !lss_aligned(class_weight, 4) || !lss_aligned(batch_loss, 4) || !lss_aligned(loss_acc, 8))
     return LSS_E_ALIGN;
   if (workspace_bytes < lss_seg_eval_workspace_bytes(C)) return LSS_E_WORKSPACE;
   const long long n = (long long)B * HW;
-  const bool vec = HW % 4 == 0 && se_aligned(logits, 4 * esz) && se_aligned(target, 16);
+  const bool vec = HW % 4 == 0 && lss_aligned(logits, 4 * esz) && lss_aligned(target, 16);
   const int grid = se_grid(vec ? n / 4 : n);
   hipStream_t st = lss_stream(stream);
   unsigned* ws = static_cast<unsigned*>(workspace);
@@ -311,8 +309,8 @@ extern "C" int lss_seg_eval_update_labels(const long long* pred, const long long
   LSS_CHECK_PTR(pred); LSS_CHECK_PTR(target); LSS_CHECK_PTR(workspace); LSS_CHECK_PTR(confmat); LSS_CHECK_PTR(invalid);
   LSS_CHECK_POS(C);
   if (n <= 0 || C > SE_MAXC || n >= (1LL << 31)) return LSS_E_SHAPE;
-  if (!se_aligned(pred, 8) || !se_aligned(target, 8) || !se_aligned(workspace, 4) || !se_aligned(confmat, 8) ||
-      !se_aligned(invalid, 8))
+  if (!lss_aligned(pred, 8) || !lss_aligned(target, 8) || !lss_aligned(workspace, 4) || !lss_aligned(confmat, 8) ||
+      !lss_aligned(invalid, 8))
     return LSS_E_ALIGN;
   if (workspace_bytes < lss_seg_eval_workspace_bytes(C)) return LSS_E_WORKSPACE;
   const int grid = se_grid(n);

@@ -1,19 +1,10 @@
-// Producer / consumer primitives of the loader-consumer kernels (conv_ring.hip, conv_wgrad.hip): LDS-DMA pieces,
-// counted waits, and FULL / FREE flag words in LDS with BOUNDED polls.  Include inside the file's anonymous namespace
-// after defining RK_TIMEOUT_COUNTER (a __device__ int that counts waits which hit their bound; must stay 0).
+// The flag-word protocol of the loader-consumer kernels (conv_ring.hip, conv_wgrad.hip): FULL / FREE words in LDS with
+// BOUNDED polls.  (The LDS-DMA pieces and counted waits they hand over with are lss_device.h's.)  Include inside the
+// file's anonymous namespace after defining RK_TIMEOUT_COUNTER (a __device__ int that counts waits which hit their
+// bound; must stay 0).
 #pragma once
 
 constexpr int RK_SPIN_LIMIT = 1 << 16;  // bound of every flag wait (~10 ms): a protocol bug must end the grid, not hang it
-
-__device__ __forceinline__ void rk_glds16(const void* gsrc, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
-}
-template <int N>
-__device__ __forceinline__ void rk_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ void rk_wait_lgkm0() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // Flag words live in LDS and are addressed through address_space(3) pointers: a generic `volatile int*` made
 // hipcc emit flat_load ... sc0 sc1 followed by vmcnt(0) waits (seen in the ISA of the first build).

@@ -832,8 +832,7 @@ static bool region_plan_for(int B, int N, int D, int fH, int fW, int C, int X, i
   rp->ovf = nullptr;
   rp->ovf_ctl = nullptr;
   rp->ovf_cap = 0;
-  if (const char* e = getenv("LSS_SPLAT_LEGACY"))
-    if (atoi(e) != 0) return false;
+  if (lss_env_set_on("LSS_SPLAT_LEGACY")) return false;
   const long long nvox = (long long)B * X * Y * Z, P = (long long)B * N * D * fH * fW;
   rp->nRx = lss_cdiv(X, LSS_REGION_SIDE);
   rp->nRy = lss_cdiv(Y, LSS_REGION_SIDE);
@@ -854,7 +853,7 @@ static bool region_plan_for(int B, int N, int D, int fH, int fW, int C, int X, i
   rp->wg_absmax = reinterpret_cast<float*>(vox_list + nreg);
   // the direct form: as many slots per region as the caller's workspace holds, at most LSS_DIRECT_CAP
   if (direct_entries != nullptr && (reinterpret_cast<uintptr_t>(direct_entries) & 7) == 0 &&
-      !(getenv("LSS_SPLAT_DIRECT") != nullptr && atoi(getenv("LSS_SPLAT_DIRECT")) == 0)) {
+      lss_env_on("LSS_SPLAT_DIRECT")) {
     // the overflow list takes the buffer's tail when the buckets leave room for it
     const unsigned long long ovf_bytes = (unsigned long long)LSS_DIRECT_OVF * 16;
     const bool with_list = direct_bytes >= (unsigned long long)nreg * LSS_DIRECT_MIN_CAP * 8 + ovf_bytes;
@@ -902,9 +901,9 @@ static int region_splat_launch(const float* feat, const int32_t* entries, const 
   dim3 grid(B * rp.rps);
   const int2* en = reinterpret_cast<const int2*>(entries);
   // diagnostic runs: the splat's stamps follow the 16384 slots of the K2 || K3 launch in the same buffer
-  unsigned long long* stamps = getenv("LSS_L1_STAMPS")
-      ? reinterpret_cast<unsigned long long*>(strtoull(getenv("LSS_L1_STAMPS"), nullptr, 16)) + (size_t)16384 * 8 : nullptr;
-  static const int centre_out = getenv("LSS_SPLAT_ORDER") == nullptr || atoi(getenv("LSS_SPLAT_ORDER")) != 0;
+  unsigned long long* stamps = lss_env_device_ptr("LSS_L1_STAMPS");
+  if (stamps != nullptr) stamps += (size_t)16384 * 8;
+  static const int centre_out = lss_env_on("LSS_SPLAT_ORDER");
 #define LSS_RS(CPL, LAY)                                                                                          \
   do {                                                                                                            \
     if (lds > 64 * 1024) {                                                                                        \

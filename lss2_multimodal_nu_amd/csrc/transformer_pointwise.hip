@@ -4,7 +4,7 @@
 // lss_gelu_dropout_fwd     y = bf16(gelu(h) m)                      (tokens, d_ff) hidden, bf16 in and out
 // lss_gelu_dropout_bwd     dh = bf16(dy m (Phi(h) + h phi(h)))
 //   8 bf16 per lane and step (16-B loads and stores), one Philox call per step, capped grid with a grid-stride loop.
-//   erf by Abramowitz & Stegun 7.1.26 exactly as linear_mfma.hip's fast_erf; its exp(-x^2), x = h / sqrt 2, IS
+//   erf by Abramowitz & Stegun 7.1.26 (lss_device.h: the text the forward GEMM epilogues use); its exp(-x^2), x = h / sqrt 2, IS
 //   exp(-h^2 / 2): the backward's phi(h) costs no second exponential.  h = +-3e38: h^2 = inf, exp = 0, h phi = 0.
 // lss_add_dropout_ln_fwd   s = res + a m (fp32),  y = LayerNorm(s)   rows of 256, one wave per row, 4 channels per lane
 //   layernorm_kernel's two-pass arithmetic (bev_transformer.hip) on s: what the backward recomputes.
@@ -23,49 +23,14 @@
 
 #include "dropout_philox.h"
 #include "layernorm_bwd_row.h"
-#include "lss_common.h"
+#include "lss_device.h"
 
 namespace {
 
 constexpr int PW_MAXBLOCKS = 2048;  // 256 CUs x 8 workgroups (cdna_hip_programming.md, Guideline 11)
 
-// (1 + erf(x)) / 2 pieces of x = h / sqrt 2: erf by A&S 7.1.26 (linear_mfma.hip fast_erf), e = exp(-x^2)
-__device__ __forceinline__ float pw_erf(float x, float& e) {
-  const float ax = fabsf(x);
-  const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, ax, 1.f));
-  float p = fmaf(1.061405429f, t, -1.453152027f);
-  p = fmaf(p, t, 1.421413741f);
-  p = fmaf(p, t, -0.284496736f);
-  p = fmaf(p, t, 0.254829592f);
-  e = __expf(-ax * ax);
-  return copysignf(1.f - p * t * e, x);
-}
-__device__ __forceinline__ float pw_gelu(float v) {
-  float e;
-  return 0.5f * v * (1.f + pw_erf(v * 0.70710678118654752f, e));
-}
-// d gelu / dv = Phi(v) + v phi(v)
-__device__ __forceinline__ float pw_gelu_grad(float v) {
-  float e;
-  const float erf = pw_erf(v * 0.70710678118654752f, e);
-  return fmaf(v, e * 0.3989422804014327f, 0.5f * (1.f + erf));
-}
-
 __device__ __forceinline__ LssPhiloxKey pw_key(const unsigned long long* __restrict__ seed) {
   return lss_philox_key(seed[0], seed[1]);
-}
-
-__device__ __forceinline__ void pw_unpack8(const uint4 v, float f[8]) {
-  const unsigned int w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[2 * i] = lss_bf2f((unsigned short)(w[i] & 0xffffu));
-    f[2 * i + 1] = lss_bf2f((unsigned short)(w[i] >> 16));
-  }
-}
-__device__ __forceinline__ uint4 pw_pack8(const float f[8]) {
-  return make_uint4(lss_pack_bf2(f[0], f[1]), lss_pack_bf2(f[2], f[3]), lss_pack_bf2(f[4], f[5]),
-                    lss_pack_bf2(f[6], f[7]));
 }
 
 // n8 = n / 8 steps of 8 elements; step q is Philox call q
@@ -80,17 +45,17 @@ __global__ __launch_bounds__(256) void gelu_dropout_kernel(const uint4* __restri
   // q + stride cannot wrap: n8 <= 2^29 and stride <= 2^19
   for (unsigned int q = blockIdx.x * 256u + threadIdx.x; q < n8; q += stride) {
     float v[8], g[8], o[8];
-    pw_unpack8(h[q], v);
-    if (BWD) pw_unpack8(dy[q], g);
+    lss_unpack8(h[q], v);
+    if (BWD) lss_unpack8(dy[q], g);
     uint32_t w[4];
     if (DROP) lss_dropout_words(key, q, w);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float m = DROP ? lss_dropout_mul(w, j, thr, scale) : 1.f;
-      if (BWD) o[j] = DROP ? g[j] * m * pw_gelu_grad(v[j]) : g[j] * pw_gelu_grad(v[j]);
-      else o[j] = DROP ? pw_gelu(v[j]) * m : pw_gelu(v[j]);
+      if (BWD) o[j] = DROP ? g[j] * m * lss_gelu_grad(v[j]) : g[j] * lss_gelu_grad(v[j]);
+      else o[j] = DROP ? lss_gelu(v[j]) * m : lss_gelu(v[j]);
     }
-    out[q] = pw_pack8(o);
+    out[q] = lss_pack8(o);
   }
 }
 
@@ -120,8 +85,8 @@ __global__ __launch_bounds__(256) void add_dropout_ln_fwd_kernel(const TR* __res
   const f32x4 bt = *reinterpret_cast<const f32x4*>(beta + 4 * lane);
   // whole waves per row: the shuffles see all 64 lanes
   for (long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); row < rows; row += (long long)gridDim.x * 4) {
-    const f32x4 r = ln_load4<TR>(res + row * LN_C + 4 * lane);
-    const f32x4 av = ln_load4<TA>(a + row * LN_C + 4 * lane);
+    const f32x4 r = lss_load4<TR>(res + row * LN_C + 4 * lane);
+    const f32x4 av = lss_load4<TA>(a + row * LN_C + 4 * lane);
     f32x4 v;
     if (DROP) {
       const f32x4 m = pw_row_mask<true>(key, row, lane, thr, scale);
@@ -134,13 +99,13 @@ __global__ __launch_bounds__(256) void add_dropout_ln_fwd_kernel(const TR* __res
 #pragma unroll
       for (int i = 0; i < 4; ++i) v[i] = r[i] + av[i];
     }
-    ln_store4(s + row * LN_C + 4 * lane, v);
+    lss_store4(s + row * LN_C + 4 * lane, v);
     // layernorm_kernel's arithmetic
     const float mean = lss_wave_sum(v[0] + v[1] + v[2] + v[3]) * (1.f / LN_C);
     const f32x4 d = (f32x4){v[0] - mean, v[1] - mean, v[2] - mean, v[3] - mean};
     const float var = lss_wave_sum(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] + d[3] * d[3]) * (1.f / LN_C);
     const float inv = rsqrtf(var + eps);
-    ln_store4(y + row * LN_C + 4 * lane, (f32x4){d[0] * inv * g[0] + bt[0], d[1] * inv * g[1] + bt[1],
+    lss_store4(y + row * LN_C + 4 * lane, (f32x4){d[0] * inv * g[0] + bt[0], d[1] * inv * g[1] + bt[1],
                                                  d[2] * inv * g[2] + bt[2], d[3] * inv * g[3] + bt[3]});
   }
 }
@@ -161,12 +126,12 @@ __global__ __launch_bounds__(256) void add_dropout_ln_bwd_kernel(const float* __
   const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + 4 * lane);
   f32x4 dg = (f32x4){0.f, 0.f, 0.f, 0.f}, dbt = (f32x4){0.f, 0.f, 0.f, 0.f};
   for (long long row = r0 + wave; row < r1; row += 4) {
-    const f32x4 v = ln_load4<float>(s + row * LN_C + 4 * lane);
-    const f32x4 gr = ln_load4<TG>(dy + row * LN_C + 4 * lane);
+    const f32x4 v = lss_load4<float>(s + row * LN_C + 4 * lane);
+    const f32x4 gr = lss_load4<TG>(dy + row * LN_C + 4 * lane);
     const f32x4 dx = ln_bwd_row(v, gr, gm, eps, dg, dbt);
-    ln_store4(ds + row * LN_C + 4 * lane, dx);
+    lss_store4(ds + row * LN_C + 4 * lane, dx);
     const f32x4 m = pw_row_mask<DROP>(key, row, lane, thr, scale);
-    ln_store4(da + row * LN_C + 4 * lane,
+    lss_store4(da + row * LN_C + 4 * lane,
               DROP ? (f32x4){dx[0] * m[0], dx[1] * m[1], dx[2] * m[2], dx[3] * m[3]} : dx);
   }
   ln_bwd_write_partial(red, dg, dbt, part);
@@ -184,7 +149,7 @@ int gelu_dropout_launch(bool bwd, const void* h, const void* dy, long long n, in
   if (bwd) LSS_CHECK_PTR(dy);
   if (!lss_gelu_dropout_ok(n) || !pw_thr_ok(thr)) return LSS_E_SHAPE;
   if (out == h || out == dy) return LSS_E_LAYOUT;  // the kernels read through __restrict__ pointers
-  if (!lg_aligned(h, 16) || !lg_aligned(out, 16) || !lg_aligned(dy, 16) || !lg_aligned(seed, 8)) return LSS_E_ALIGN;
+  if (!lss_aligned(h, 16) || !lss_aligned(out, 16) || !lss_aligned(dy, 16) || !lss_aligned(seed, 8)) return LSS_E_ALIGN;
   const bool drop = pw_drop(thr, seed);
   const unsigned int n8 = (unsigned int)(n / 8);
   const dim3 grid(std::min<unsigned int>((n8 + 255u) / 256u, PW_MAXBLOCKS));
@@ -229,8 +194,8 @@ extern "C" int lss_add_dropout_ln_fwd(const void* res, int res_dt, const void* a
   if (!lss_add_dropout_ln_ok(rows, C) || !pw_thr_ok(thr)) return LSS_E_SHAPE;
   const bool drop = pw_drop(thr, seed);
   if (!pw_dt_ok(res_dt) || !pw_dt_ok(a_dt)) return LSS_E_LAYOUT;
-  if (!lg_aligned(seed, 8) || !lg_aligned(res, 16) || !lg_aligned(a, 16) || !lg_aligned(gamma, 16) || !lg_aligned(beta, 16) ||
-      !lg_aligned(s, 16) || !lg_aligned(y, 16))
+  if (!lss_aligned(seed, 8) || !lss_aligned(res, 16) || !lss_aligned(a, 16) || !lss_aligned(gamma, 16) || !lss_aligned(beta, 16) ||
+      !lss_aligned(s, 16) || !lss_aligned(y, 16))
     return LSS_E_ALIGN;
   const dim3 grid((unsigned int)std::min<long long>((rows + 3) / 4, PW_MAXBLOCKS));
   hipStream_t st = lss_stream(stream);
@@ -262,8 +227,8 @@ extern "C" int lss_add_dropout_ln_bwd(const float* s, const void* dy, int dy_dt,
   if (!lss_add_dropout_ln_ok(rows, C) || !pw_thr_ok(thr)) return LSS_E_SHAPE;
   const bool drop = pw_drop(thr, seed);
   if (!pw_dt_ok(dy_dt) || !pw_dt_ok(da_dt)) return LSS_E_LAYOUT;
-  if (!lg_aligned(seed, 8) || !lg_aligned(s, 16) || !lg_aligned(dy, 16) || !lg_aligned(gamma, 16) || !lg_aligned(ds, 16) ||
-      !lg_aligned(da, 16) || !lg_aligned(workspace, 16) || !lg_aligned(dgamma, 4) || !lg_aligned(dbeta, 4))
+  if (!lss_aligned(seed, 8) || !lss_aligned(s, 16) || !lss_aligned(dy, 16) || !lss_aligned(gamma, 16) || !lss_aligned(ds, 16) ||
+      !lss_aligned(da, 16) || !lss_aligned(workspace, 16) || !lss_aligned(dgamma, 4) || !lss_aligned(dbeta, 4))
     return LSS_E_ALIGN;
   if (workspace_bytes < lss_add_dropout_ln_bwd_workspace_bytes(rows)) return LSS_E_WORKSPACE;
   const LnSplit sp = ln_split(rows);
