@@ -175,6 +175,33 @@ int lss_depth_fuse_softmax_fwd(const float* d3, const float* d4, const float* w_
                                const float* scale, const float* shift, int BN, int D, int H, int W,
                                int H4, int W4, float* depth, void* stream);
 
+/* MultiScaleDepthNet tail in TRAINING mode, forward and backward (csrc/depth_fuse_train.hip), fp32 throughout.
+ * replaces: src/model_vovnet_transformer.py:61-69 under model.train() (F.interpolate bilinear align_corners=False,
+ *           torch.cat, fusion 1x1 conv, BatchNorm2d with batch statistics, ReLU) and the autograd nodes of those ops.
+ *   d3 (BN, D, H, W), d4 (BN, D, H4, W4) fp32 logits, H4 / W4 arbitrary; w_fusion (D, 2D), bias, gamma, beta (D) fp32
+ *   forward: z = w_fusion [d3, up(d4)] + bias and u = relu(gamma (z - mean) invstd + beta), both (BN, D, H, W) fp32
+ *            out; save_mean, save_invstd (D) out: batch mean and rsqrt(biased var + eps) over M = BN*H*W (sums about
+ *            a pivot: a large mean does not cancel the variance); running_mean / running_var (D) updated in place
+ *            as nn.BatchNorm2d does (unbiased M / (M - 1) for the variance).  3 launches.
+ *   backward from du (BN, D, H, W) fp32, contiguous: dd3 like d3, dd4 like d4 (the adjoint of the upsample as a
+ *            gather), dw (D, 2D), dgamma, dbeta (D), all overwritten; the conv bias has gradient zero and none is
+ *            written.  4 launches.
+ *   workspace: lss_depth_fuse_train_workspace_bytes(BN, D, H, W) bytes (0 for a refused shape), 16-B aligned,
+ *            reusable between calls; no allocation, no synchronisation, fixed summation order (bit-reproducible).
+ * Argument checks, all before any launch: LSS_E_NULL (every pointer is required), LSS_E_SHAPE (a size <= 0, D > 64,
+ * M < 2 - batch statistics need two values -, BN*H*W or BN*D*H4*W4 >= 2^31), LSS_E_ALIGN, LSS_E_WORKSPACE. */
+size_t lss_depth_fuse_train_workspace_bytes(int BN, int D, int H, int W);
+int lss_depth_fuse_train_fwd(const float* d3, const float* d4, const float* w_fusion, const float* bias,
+                             const float* gamma, const float* beta, float* running_mean, float* running_var,
+                             float momentum, float eps, int BN, int D, int H, int W, int H4, int W4,
+                             void* workspace, size_t workspace_bytes, float* z, float* u, float* save_mean,
+                             float* save_invstd, void* stream);
+int lss_depth_fuse_train_bwd(const float* du, const float* u, const float* z, const float* d3, const float* d4,
+                             const float* w_fusion, const float* gamma, const float* save_mean,
+                             const float* save_invstd, int BN, int D, int H, int W, int H4, int W4, void* workspace,
+                             size_t workspace_bytes, float* dd3, float* dd4, float* dw, float* dgamma, float* dbeta,
+                             void* stream);
+
 /* ---------------------------------------------------------------------------
  * K5/K6  fused lift + splat: bev[v, c] = sum_{p in voxel v} w[p] * feat[row(p), c]
  *        (w = the depth weight K4 stored next to the point id)

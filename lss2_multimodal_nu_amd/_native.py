@@ -31,6 +31,9 @@ SIGNATURES = {
     "lss_depthnet_softmax_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     "lss_camencode_v2_fwd": (_i, [_vp, _i, _vp, _vp, _i, _vp, _vp, _vp] + [_i] * 7 + [_vp, _vp, _vp]),
     "lss_depth_fuse_softmax_fwd": (_i, [_vp] * 5 + [_i] * 6 + [_vp, _vp]),
+    "lss_depth_fuse_train_workspace_bytes": (_sz, [_i] * 4),
+    "lss_depth_fuse_train_fwd": (_i, [_vp] * 8 + [ctypes.c_float, ctypes.c_float] + [_i] * 6 + [_vp, _sz] + [_vp] * 5),
+    "lss_depth_fuse_train_bwd": (_i, [_vp] * 9 + [_i] * 6 + [_vp, _sz] + [_vp] * 6),
     "lss_add_pos_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "lss_deform_attn_fwd": (_i, [_vp, _i] + [_vp] * 4 + [_i] * 7 + [_vp, _vp]),
     "lss_deform_attn_pts_fwd": (_i, [_vp] * 3 + [ctypes.c_longlong] + [_i] * 6 + [_vp, _vp]),

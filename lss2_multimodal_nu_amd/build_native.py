@@ -21,6 +21,7 @@ ARCH = "gfx950"
 SOURCES = {
     "geom_bucket.hip": ["-ffp-contract=off"],
     "depthnet.hip": [],
+    "depth_fuse_train.hip": [],
     "splat.hip": [],
     "conv_mfma.hip": [],
     "conv_ring.hip": ["-fno-slp-vectorize"],  # no v_pk_*_f32 next to MFMAs (MI355X_MICROARCH.md)

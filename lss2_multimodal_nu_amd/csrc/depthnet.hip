@@ -237,15 +237,10 @@ __global__ __launch_bounds__(256) void depth_fuse_softmax_kernel(
   const bool live = gp < (long long)BN * HW;
   const int bn = live ? (int)(gp / HW) : 0, pix = live ? (int)(gp % HW) : 0;
   const int oh = pix / W, ow = pix % W;
-  // source coordinates exactly as ATen's area_pixel_compute_source_index (align_corners=False)
-  float sh = rh * ((float)oh + 0.5f) - 0.5f;
-  float sw = rw * ((float)ow + 0.5f) - 0.5f;
-  sh = sh < 0.f ? 0.f : sh;
-  sw = sw < 0.f ? 0.f : sw;
-  const int h0 = (int)sh, w0 = (int)sw;
-  const int h1 = h0 + (h0 < H4 - 1 ? 1 : 0), w1 = w0 + (w0 < W4 - 1 ? 1 : 0);
-  const float lh1 = sh - (float)h0, lh0 = 1.f - lh1;
-  const float lw1 = sw - (float)w0, lw0 = 1.f - lw1;
+  int h0, h1, w0, w1;
+  float lh0, lh1, lw0, lw1;
+  lss_bilinear_src(rh, oh, H4, h0, h1, lh0, lh1);
+  lss_bilinear_src(rw, ow, W4, w0, w1, lw0, lw1);
   if (lane < D) {
     const float* c = d4 + ((size_t)bn * D + lane) * (H4 * W4);
     const float up = lh0 * (lw0 * c[h0 * W4 + w0] + lw1 * c[h0 * W4 + w1]) +

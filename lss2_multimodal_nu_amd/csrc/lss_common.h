@@ -78,6 +78,19 @@ __device__ __forceinline__ int lss_xcd_order(int bid, int nwg) {
   return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
 }
 
+// Source taps of output index `o` of a bilinear resize with align_corners=False, exactly as ATen's
+// area_pixel_compute_source_index: r = (float)n_in / n_out, the coordinate clamped at 0, the upper tap clamped to the
+// last input index.  The inference tail (depthnet.hip) and the training tail with its adjoint (depth_fuse_train.hip)
+// all take their taps from here, so forward, recomputation and gather cannot disagree.
+__device__ __forceinline__ void lss_bilinear_src(float r, int o, int n_in, int& i0, int& i1, float& l0, float& l1) {
+  float s = r * ((float)o + 0.5f) - 0.5f;
+  s = s < 0.f ? 0.f : s;
+  i0 = (int)s;
+  i1 = i0 + (i0 < n_in - 1 ? 1 : 0);
+  l1 = s - (float)i0;
+  l0 = 1.f - l1;
+}
+
 __device__ __forceinline__ float lss_wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);

@@ -46,17 +46,54 @@ BEV_ENCODER_CALLS = {"native": 0, "composition": 0}
 _BEV_ENCODER_NATIVE_DEFAULT = "1"
 
 
+# which form each 3x3 conv-BN-ReLU unit of the depth heads / v2's fusion tail took when `get_voxels` had to be
+# differentiable: "native" = `modules._train_conv_bn_act` with the bias absorbed (bf16 autocast) / `_DepthFuseFn`
+HEAD_UNIT_CALLS = {"native": 0, "composition": 0}
+FUSE_TAIL_CALLS = {"native": 0, "composition": 0}
+# LSS_DEPTH_HEADS_NATIVE / LSS_DEPTH_TAIL_NATIVE unset: see DESIGN.md 4b for the measurements that decide these
+_DEPTH_HEADS_NATIVE_DEFAULT = "1"
+_DEPTH_TAIL_NATIVE_DEFAULT = "1"
+
+
+def _nhwc_bf16_rows(hidden):
+    """The (BN,fH,fW,Cd) bf16 rows behind `hidden` when it is a bf16 NCHW view over contiguous NHWC memory (what the
+    native 3x3 unit returns), else None."""
+    if hidden.dtype != torch.bfloat16 or hidden.dim() != 4:
+        return None
+    rows = hidden.permute(0, 2, 3, 1)
+    return rows if rows.is_contiguous() else None
+
+
 class _HeadProjFn(torch.autograd.Function):
     """The 1x1 convs behind the depth heads' hidden map (BN,Cd,fH,fW) and (optionally, same launch) `feat_proj`
     over C3.
     forward = K2v without softmax, fp32 math: logits (BN,D,fH,fW) [, context rows (BN,fH,fW,C)];
-    backward = K10 once per projection, reading the gradients where K7 left them."""
+    backward = K10 once per projection, reading the gradients where K7 left them.
+    A hidden map that arrives as a bf16 NCHW view over NHWC memory (the native 3x3 unit's output) is read where it
+    lies in both directions - K2v takes bf16 rows, K10 has a bf16 NHWC mode - and its gradient goes back the same
+    way; an fp32 NCHW map takes the fp32 copies."""
 
     @staticmethod
-    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, hidden, w_depth, b_depth, c3, w_feat, b_feat):
-        hidden = hidden.contiguous()  # (BN,Cd,fH,fW): kept for K10 as it is (the tensor the ReLU's backward holds)
-        rows = hidden.permute(0, 2, 3, 1).contiguous()  # the NHWC rows K2v reads; freed when the node returns
+        # (no `custom_fwd(cast_inputs=...)`: it would turn the bf16 rows into an fp32 copy; the casts it would make
+        # are made here, for everything else)
+        rows16 = _nhwc_bf16_rows(hidden)
+        with torch.autocast("cuda", enabled=False):
+            w_depth, b_depth = w_depth.float(), b_depth.float()
+            if c3 is not None:
+                c3, w_feat, b_feat = c3.float(), w_feat.float(), b_feat.float()
+            if rows16 is None:
+                hidden = hidden.float()
+            return _HeadProjFn._forward(ctx, hidden, rows16, w_depth, b_depth, c3, w_feat, b_feat)
+
+    @staticmethod
+    def _forward(ctx, hidden, rows16, w_depth, b_depth, c3, w_feat, b_feat):
+        ctx.nhwc = rows16 is not None
+        if ctx.nhwc:
+            hidden = rows = rows16  # kept for K10 as it lies
+        else:
+            hidden = hidden.contiguous()  # (BN,Cd,fH,fW): kept for K10 as it is (the tensor the ReLU's backward holds)
+            rows = hidden.permute(0, 2, 3, 1).contiguous()  # the NHWC rows K2v reads; freed when the node returns
         with_feat = c3 is not None
         if with_feat:
             c3 = c3.contiguous()
@@ -69,14 +106,21 @@ class _HeadProjFn(torch.autograd.Function):
 
     @staticmethod
     @once_differentiable
-    @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, g_logits, g_feat=None):
+        with torch.autocast("cuda", enabled=False):
+            return _HeadProjFn._backward(ctx, g_logits, g_feat)
+
+    @staticmethod
+    def _backward(ctx, g_logits, g_feat):
         hidden, w_depth, c3, w_feat = ctx.saved_tensors
         need = ctx.needs_input_grad
         out = [None] * 6
         if need[0] or need[1] or need[2]:
-            out[0], out[1], out[2] = ops.pointwise_conv_bwd(g_logits, hidden, w_depth.contiguous(), layout="nchw",
+            out[0], out[1], out[2] = ops.pointwise_conv_bwd(g_logits, hidden, w_depth.contiguous(),
+                                                            layout="nhwc" if ctx.nhwc else "nchw",
                                                             want_dx=need[0], want_dw=need[1], want_db=need[2])
+            if ctx.nhwc and out[0] is not None:
+                out[0] = out[0].permute(0, 3, 1, 2)  # bf16 NHWC dx, handed back as the NCHW view it came as
         if ctx.with_feat and (need[3] or need[4] or need[5]):
             # (BN,fH,fW,C) rows as autograd sees them; K7 wrote them channel-major, and that is how K10 reads them
             out[3], out[4], out[5] = ops.pointwise_conv_bwd(g_feat.permute(0, 3, 1, 2), c3, w_feat.contiguous(),
@@ -113,6 +157,86 @@ class _HeadsLiftSplatFn(torch.autograd.Function):
         return g[:, :D], g[:, D:].permute(0, 2, 3, 1), None, None, None, None, None, None
 
 
+class _DepthFuseFn(torch.autograd.Function):
+    """v2's fusion tail in training mode as one node (csrc/depth_fuse_train.hip): (d3 (BN,D,H,W), d4 (BN,D,H4,W4)
+    logits) -> relu(BatchNorm_train(fusion([d3, bilinear(d4)]))) (BN,D,H,W), the softmax's input.  fp32 math, three
+    launches forward and four backward; the upsampled and the concatenated tensor exist in neither direction.  The
+    conv bias stays in the pre-activation (running_mean is the biased conv's), its gradient is the exact zero it is
+    in exact arithmetic (`modules._AbsorbedBiasFn`'s convention)."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, d3, d4, weight, bias, gamma, beta, running_mean, running_var, momentum, eps):
+        d3, d4 = d3.contiguous(), d4.contiguous()
+        w, g32 = weight.detach().contiguous(), gamma.detach().contiguous()
+        z, u, mean, invstd = ops.depth_fuse_train_fwd(d3, d4, w, bias.detach().contiguous(), g32,
+                                                      beta.detach().contiguous(), running_mean, running_var, momentum,
+                                                      eps)
+        ctx.save_for_backward(d3, d4, w, g32, z, u, mean, invstd)
+        ctx.bias_meta = (bias.shape, bias.dtype)
+        return u
+
+    @staticmethod
+    @once_differentiable
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, du):
+        d3, d4, w, g32, z, u, mean, invstd = ctx.saved_tensors
+        if du.dtype != torch.float32:
+            du = du.float()
+        dd3, dd4, dw, dgamma, dbeta = ops.depth_fuse_train_bwd(du.contiguous(), u, z, d3, d4, w, g32, mean, invstd)
+        need = ctx.needs_input_grad
+        shape, dtype = ctx.bias_meta
+        db = torch.zeros(shape, dtype=dtype, device=du.device) if need[3] else None
+        return (dd3 if need[0] else None, dd4 if need[1] else None, dw if need[2] else None, db,
+                dgamma if need[4] else None, dbeta if need[5] else None, None, None, None, None)
+
+
+def _fuse_tail_native_ok(fusion, d3):
+    """Does v2's fusion tail take `_DepthFuseFn`?  (The caller is on the lift's native route already - GPU tensors,
+    fp32 modules.)  A plain 1x1 conv 2D -> D with D <= 64 and a bias, and a BatchNorm in training mode that is affine,
+    tracks running statistics with a numeric momentum, is fp32 and is not synchronised over ranks; LSS_DEPTH_TAIL_NATIVE=0
+    keeps the torch composition.  With or without autocast: the node's math is fp32 either way."""
+    if os.environ.get("LSS_DEPTH_TAIL_NATIVE", _DEPTH_TAIL_NATIVE_DEFAULT) == "0":
+        return False
+    conv, bn = fusion[0], fusion[1]
+    D = conv.out_channels
+    if not (isinstance(conv, nn.Conv2d) and isinstance(bn, nn.BatchNorm2d) and d3.is_cuda and d3.dim() == 4):
+        return False
+    if not (bn.training and bn.affine and bn.track_running_stats and bn.momentum is not None
+            and bn.weight.dtype == torch.float32 and bn.num_features == D and "_lss_sync" not in bn.__dict__):
+        return False
+    return (conv.kernel_size == (1, 1) and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.dilation == (1, 1)
+            and conv.groups == 1 and conv.bias is not None and conv.in_channels == 2 * D and D <= 64
+            and d3.shape[1] == D and conv.weight.dtype == torch.float32
+            and d3.shape[0] * d3.shape[2] * d3.shape[3] < 2 ** 31)
+
+
+def _head_hidden(head, c):
+    """The 3x3 conv-BN-ReLU in front of a depth head's 1x1 on the autograd path: the bias-absorbing HIP unit under bf16
+    autocast (`modules._biased_conv3x3_unit_ok`; LSS_DEPTH_HEADS_NATIVE=0 switches it off), else the stock modules."""
+    if (os.environ.get("LSS_DEPTH_HEADS_NATIVE", _DEPTH_HEADS_NATIVE_DEFAULT) != "0"
+            and modules._biased_conv3x3_unit_ok(head[0], head[1], c.is_cuda, c.shape[1])):
+        HEAD_UNIT_CALLS["native"] += 1
+        return modules._train_conv_bn_act(head[0], head[1], c, relu=True)
+    HEAD_UNIT_CALLS["composition"] += 1
+    return head[2](head[1](head[0](c)))
+
+
+def _fuse_tail(fusion, d3, d4):
+    """v2's tail on the autograd path: relu(bn(conv1x1(cat([d3, bilinear(d4)])))), the softmax's input - `_DepthFuseFn`
+    where `_fuse_tail_native_ok` holds, the five torch ops otherwise."""
+    if _fuse_tail_native_ok(fusion, d3):
+        FUSE_TAIL_CALLS["native"] += 1
+        conv, bn = fusion[0], fusion[1]
+        u = _DepthFuseFn.apply(d3, d4, conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                               float(bn.momentum), float(bn.eps))
+        modules._count_batch(bn)
+        return u
+    FUSE_TAIL_CALLS["composition"] += 1
+    d4 = F.interpolate(d4, size=d3.shape[2:], mode="bilinear", align_corners=False)
+    return fusion(torch.cat([d3, d4], dim=1))
+
+
 def _conv_bn_relu_head(cin, D):
     return nn.Sequential(nn.Conv2d(cin, 256, 3, padding=1), nn.BatchNorm2d(256), nn.ReLU(inplace=True),
                          nn.Conv2d(256, D, 1))
@@ -144,10 +268,11 @@ class StandardDepthNet(nn.Module):
                                 cam_encode.feat_proj.bias.detach())
 
     def pre_softmax_and_context(self, c3, c4, cam_encode):
-        """Differentiable: logits (BN,D,fH,fW) + context rows (BN,fH,fW,C); the 3x3 conv-BN-ReLU is torch autograd
-        (a biased conv), the two 1x1 convs are one `_HeadProjFn` node."""
+        """Differentiable: logits (BN,D,fH,fW) + context rows (BN,fH,fW,C); the 3x3 conv-BN-ReLU is the HIP unit with
+        the bias absorbed under bf16 autocast and torch autograd otherwise (`_head_hidden`), the two 1x1 convs are one
+        `_HeadProjFn` node."""
         last, fp = self.depth_head[3], cam_encode.feat_proj
-        h = self.depth_head[2](self.depth_head[1](self.depth_head[0](c3)))
+        h = _head_hidden(self.depth_head, c3)
         return _HeadProjFn.apply(h, last.weight, last.bias, c3, fp.weight, fp.bias)
 
     def forward(self, c3, c4=None):
@@ -192,16 +317,16 @@ class MultiScaleDepthNet(nn.Module):
         return self._fuse(d3, d4), feat
 
     def pre_softmax_and_context(self, c3, c4, cam_encode):
-        """Differentiable: the fusion conv-BN-ReLU output (the softmax's input) + context rows.  The 3x3 convs, the
-        bilinear upsample of the C4 logits and the fusion tail are torch autograd; the three 1x1 projections are two
-        `_HeadProjFn` nodes."""
+        """Differentiable: the fusion conv-BN-ReLU output (the softmax's input) + context rows.  The 3x3 conv-BN-ReLU
+        units are the HIP units with the bias absorbed under bf16 autocast (`_head_hidden`), the three 1x1 projections
+        two `_HeadProjFn` nodes, and the tail - bilinear upsample of the C4 logits, concat, fusion conv, train-mode
+        BatchNorm, ReLU - one `_DepthFuseFn` node (`_fuse_tail_native_ok`); otherwise torch autograd."""
         l3, l4, fp = self.depth_c3[3], self.depth_c4[3], cam_encode.feat_proj
-        h3 = self.depth_c3[2](self.depth_c3[1](self.depth_c3[0](c3)))
-        h4 = self.depth_c4[2](self.depth_c4[1](self.depth_c4[0](c4)))
+        h3 = _head_hidden(self.depth_c3, c3)
+        h4 = _head_hidden(self.depth_c4, c4)
         d3, feat = _HeadProjFn.apply(h3, l3.weight, l3.bias, c3, fp.weight, fp.bias)
         d4 = _HeadProjFn.apply(h4, l4.weight, l4.bias, None, None, None)
-        d4 = F.interpolate(d4, size=d3.shape[2:], mode="bilinear", align_corners=False)
-        return self.fusion(torch.cat([d3, d4], dim=1)), feat
+        return _fuse_tail(self.fusion, d3, d4), feat
 
     def forward(self, c3, c4):
         if _needs_autograd(self, c3, c4):

@@ -394,6 +394,76 @@ def depth_fuse_softmax(d3, d4, w_fusion, scale, shift):
     return depth
 
 
+_fuse_train_ws = {}
+
+
+def _depth_fuse_train_args(d3, d4, w_fusion):
+    """Shape checks shared by both directions of the training tail; returns (dims, w (D, 2D), cached workspace)."""
+    if d3.dim() != 4 or d4.dim() != 4:
+        raise ValueError("d3 and d4 must be (BN, D, H, W) logits, got %s and %s" % (tuple(d3.shape), tuple(d4.shape)))
+    BN, D, H, W = d3.shape
+    _f32c(d3, "d3")
+    _f32c(d4, "d4")
+    if d4.shape[0] != BN or d4.shape[1] != D:
+        raise ValueError("d4 %s does not match d3 %s" % (tuple(d4.shape), tuple(d3.shape)))
+    if BN * H * W < 2:  # nn.BatchNorm2d's own refusal, in its words
+        raise ValueError("Expected more than 1 value per channel when training, got input size %s"
+                         % (torch.Size((BN, D, H, W)),))
+    w2 = w_fusion.reshape(w_fusion.shape[0], -1)
+    _f32c(w2, "w_fusion", (D, 2 * D))
+    key = (BN, D, H, W, str(d3.device))
+    ws = _fuse_train_ws.get(key)
+    if ws is None:
+        nbytes = N.lib().lss_depth_fuse_train_workspace_bytes(BN, D, H, W)
+        if nbytes == 0:
+            raise ValueError("the training tail takes D <= 64 and fewer than 2^31 pixels (got BN=%d D=%d H=%d W=%d)"
+                             % (BN, D, H, W))
+        ws = _fuse_train_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=d3.device)
+    return (BN, D, H, W, d4.shape[2], d4.shape[3]), w2, ws
+
+
+def depth_fuse_train_fwd(d3, d4, w_fusion, bias, gamma, beta, running_mean, running_var, momentum, eps):
+    """MultiScaleDepthNet's tail in training mode (lss_depth_fuse_train_fwd): d3 (BN,D,H,W), d4 (BN,D,H4,W4) fp32
+    logits -> z = fusion([d3, up(d4)]) + bias, u = relu(BatchNorm_train(z)) (both (BN,D,H,W) fp32), save_mean,
+    save_invstd (D); running_mean / running_var are updated in place like nn.BatchNorm2d's."""
+    dims, w2, ws = _depth_fuse_train_args(d3, d4, w_fusion)
+    D = dims[1]
+    for t, nm in ((bias, "bias"), (gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"),
+                  (running_var, "running_var")):
+        _f32c(t, nm, (D,))
+    z, u = torch.empty_like(d3), torch.empty_like(d3)
+    mean = torch.empty(D, dtype=torch.float32, device=d3.device)
+    invstd = torch.empty(D, dtype=torch.float32, device=d3.device)
+    with _timed("depth_fuse_train_fwd"):
+        N.check(N.lib().lss_depth_fuse_train_fwd(N.ptr(d3), N.ptr(d4), N.ptr(w2), N.ptr(bias), N.ptr(gamma),
+                                                 N.ptr(beta), N.ptr(running_mean), N.ptr(running_var),
+                                                 float(momentum), float(eps), *dims, N.ptr(ws), ws.numel(), N.ptr(z),
+                                                 N.ptr(u), N.ptr(mean), N.ptr(invstd), N.stream()),
+                "lss_depth_fuse_train_fwd")
+    return z, u, mean, invstd
+
+
+def depth_fuse_train_bwd(du, u, z, d3, d4, w_fusion, gamma, mean, invstd):
+    """Backward of `depth_fuse_train_fwd` (lss_depth_fuse_train_bwd): returns (d(d3), d(d4), dW like w_fusion, dgamma,
+    dbeta), all fp32 and bit-reproducible; the conv bias in front of the BatchNorm has gradient zero."""
+    dims, w2, ws = _depth_fuse_train_args(d3, d4, w_fusion)
+    D = dims[1]
+    for t, nm in ((du, "du"), (u, "u"), (z, "z")):
+        _f32c(t, nm, d3.shape)
+    for t, nm in ((gamma, "gamma"), (mean, "mean"), (invstd, "invstd")):
+        _f32c(t, nm, (D,))
+    dd3, dd4 = torch.empty_like(d3), torch.empty_like(d4)
+    dw = torch.empty(w_fusion.shape, dtype=torch.float32, device=d3.device)
+    dgamma = torch.empty(D, dtype=torch.float32, device=d3.device)
+    dbeta = torch.empty(D, dtype=torch.float32, device=d3.device)
+    with _timed("depth_fuse_train_bwd"):
+        N.check(N.lib().lss_depth_fuse_train_bwd(N.ptr(du), N.ptr(u), N.ptr(z), N.ptr(d3), N.ptr(d4), N.ptr(w2),
+                                                 N.ptr(gamma), N.ptr(mean), N.ptr(invstd), *dims, N.ptr(ws),
+                                                 ws.numel(), N.ptr(dd3), N.ptr(dd4), N.ptr(dw), N.ptr(dgamma),
+                                                 N.ptr(dbeta), N.stream()), "lss_depth_fuse_train_bwd")
+    return dd3, dd4, dw, dgamma, dbeta
+
+
 def lift_splat_fwd(feat, ws, dims, nx, layout=BEV_NCHW_F32, tag="lift_splat_fwd"):
     """K5/K6 on a bucketed workspace (depth weights already sit in ws.entries).
     dims = (B,N,D,fH,fW,C).  Returns the BEV tensor with LOGICAL shape
