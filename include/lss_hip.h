@@ -337,7 +337,8 @@ int lss_layernorm_fwd(const void* x, int x_dt, const float* gamma, const float* 
                       long long rows, int C, float eps, void* y, int y_dt, void* stream);
 
 /* ---------------------------------------------------------------------------
- * K11  training gradients of the BEV transformer's linears and LayerNorms (csrc/linear_grad.hip).
+ * K11  training gradients of the BEV transformer's linears (csrc/linear_grad.hip) and LayerNorms (the row kernels of
+ * csrc/transformer_pointwise.hip).
  * replaces: the autograd nodes (AddmmBackward, NativeLayerNormBackward) that `loss.backward()`,
  *           train_vovnet_transformer.py:210, runs for the nn.Linear / nn.LayerNorm defined and used in
  *           src/transformer_modules.py:77-84 (sampling_offsets, attention_weights, value_proj, output_proj),
@@ -358,7 +359,7 @@ int lss_layernorm_fwd(const void* x, int x_dt, const float* gamma, const float* 
  *
  * lss_layernorm_bwd: backward of lss_layernorm_fwd.  x (rows, C) in x_dt, dy (rows, C) in dy_dt, gamma (C) fp32 ->
  *   dx (rows, C) in dx_dt, dgamma (C), dbeta (C) fp32, all fully written (dtypes LSS_DT_F32 | LSS_DT_BF16).  Mean and
- *   1 / sigma are recomputed from x with the forward kernel's arithmetic:
+ *   1 / sigma are recomputed from x by the forward's two-pass formula:
  *        xhat = (x - mean) / sigma,  a = dy gamma,  dx = (a - mean(a) - xhat mean(a xhat)) / sigma,
  *        dgamma = sum_rows dy xhat,  dbeta = sum_rows dy.
  *   Each workgroup writes one partial (2, C) vector of its row range to `workspace`
@@ -395,9 +396,10 @@ int lss_layernorm_bwd(const void* x, int x_dt, const void* dy, int dy_dt, const 
  * lss_gelu_dropout_bwd: dh = bf16(dy m (Phi(h) + h phi(h))) in fp32; finite for every finite bf16 h.
  *   lss_gelu_dropout_ok: 1 for n % 8 == 0, 8 <= n <= 2^32; else LSS_E_SHAPE.  The output must not be an input
  *   (LSS_E_LAYOUT).  16-B alignment (LSS_E_ALIGN).
- * lss_add_dropout_ln_fwd: s = res + a m (one fp32 multiply, one add), y = LayerNorm(s) with the arithmetic of
- *   lss_layernorm_fwd.  res in res_dt, a in a_dt (LSS_DT_F32 | LSS_DT_BF16), s and y fp32, all (rows, C);
- *   e = row * 256 + c.
+ * lss_add_dropout_ln_fwd: s = res + a m (one fp32 multiply, one add), y = LayerNorm(s) by the two-pass formula of
+ *   lss_layernorm_fwd.  The training rows (this entry and both backwards, which share mean and 1 / sigma bit for bit)
+ *   never round the mean, lss_layernorm_fwd does: y agrees with lss_layernorm_fwd(s) within rounding, not in every
+ *   bit.  res in res_dt, a in a_dt (LSS_DT_F32 | LSS_DT_BF16), s and y fp32, all (rows, C); e = row * 256 + c.
  * lss_add_dropout_ln_bwd: lss_layernorm_bwd on s - the same formula, the same partials in `workspace`
  *   (>= lss_add_dropout_ln_bwd_workspace_bytes(rows) bytes), the same fixed-order second stage - with ds fp32 (the
  *   gradient of res) and a second output da = ds m in da_dt.

@@ -31,9 +31,7 @@ SOURCES = {
     "deform_grad.hip": [],
     "pointwise_grad.hip": [],
     "linear_grad.hip": ["-fno-slp-vectorize"],  # no v_pk_*_f32 next to MFMAs, as conv_ring.hip
-    # as linear_grad.hip: the shared LayerNorm-backward rows (layernorm_bwd_row.h) must contract to the same FMAs in
-    # both files - SLP packing changes which products fuse, and with it the bits
-    "transformer_pointwise.hip": ["-fno-slp-vectorize"],
+    "transformer_pointwise.hip": ["-fno-slp-vectorize"],  # scalar row arithmetic, as the kernels were measured
     "linear_mfma.hip": [],
     "ffn_fused.hip": [],
     "conv_grad.hip": [],

@@ -1,7 +1,7 @@
-// K11: the training gradients of the BEV transformer's linears and LayerNorms that no existing kernel covers
-// (replaces the AddmmBackward / NativeLayerNormBackward nodes that `loss.backward()`, ref train_vovnet_transformer.py:210,
-// runs for the nn.Linear / nn.LayerNorm of ref src/transformer_modules.py:77-84, 170-215).  The input gradient of a
-// linear is the forward GEMM on the transposed weight (linear_mfma.hip) and needs nothing here.
+// K11: the weight gradient of the BEV transformer's linears (replaces the AddmmBackward nodes that `loss.backward()`,
+// ref train_vovnet_transformer.py:210, runs for the nn.Linear of ref src/transformer_modules.py:77-84, 170-215).  The
+// input gradient of a linear is the forward GEMM on the transposed weight (linear_mfma.hip) and needs nothing here; the
+// LayerNorm backward of K11 lies with the other training row kernels in transformer_pointwise.hip.
 //
 // lss_linear_wgrad      dw[n, k] = sum_t dy[t, n] x[t, k],  db[n] = sum_t dy[t, n]     (y = x W^T + b, bf16 operands)
 //   The contraction index is the TOKEN index, the slow dimension of both operands.  As in K9w (conv_wgrad.hip) both
@@ -23,17 +23,8 @@
 //   per column, added in a fixed order through LDS at the end: db costs no second pass over dy.
 //   Split rule (a function of (T, N, K) alone): stages = ceil(T / 128), tiles = (N / 64)(K / 64),
 //   want = clamp(512 / tiles, 1, stages), per = ceil(stages / want), splits = ceil(stages / per).  No float atomics.
-//
-// lss_layernorm_bwd     backward of lss_layernorm_fwd (C = 256), one wave per row, 4 channels per lane
-//   Recomputes mean and 1 / sigma with layernorm_kernel's own two-pass arithmetic (the forward saves only its input):
-//     xhat = (x - mean) / sigma,   a = g gamma,   dx = (a - mean(a) - xhat mean(a xhat)) / sigma
-//     dgamma = sum_rows g xhat,    dbeta = sum_rows g
-//   A workgroup walks a row range (wave w: rows r0 + w, r0 + w + 4, ..), its four waves' (2, 256) sums are added in wave
-//   order and written as one partial vector; layernorm_bwd_reduce_kernel adds the workgroups' partials in order.
-//   Row ranges: groups = min(ceil(rows / 4), 1024), rows per group = ceil(rows / groups).
 #include <algorithm>
 
-#include "layernorm_bwd_row.h"  // the LayerNorm backward's row arithmetic, lg_sum_splits, ln_split
 #include "lss_device.h"
 
 namespace {
@@ -208,25 +199,6 @@ inline LinSplit lin_split(int T, int N, int K) {
   return sp;
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-template <typename TX, typename TG, typename TO>
-__global__ __launch_bounds__(256) void layernorm_bwd_kernel(const TX* __restrict__ x, const TG* __restrict__ dy,
-                                                            const float* __restrict__ gamma, long long rows,
-                                                            long long rpg, float eps, TO* __restrict__ dx,
-                                                            float* __restrict__ part) {
-  __shared__ float red[4][2 * LN_C];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const long long r0 = (long long)blockIdx.x * rpg, r1 = min(rows, r0 + rpg);
-  const f32x4 gm = *reinterpret_cast<const f32x4*>(gamma + 4 * lane);
-  f32x4 dg = (f32x4){0.f, 0.f, 0.f, 0.f}, dbt = (f32x4){0.f, 0.f, 0.f, 0.f};
-  for (long long row = r0 + wave; row < r1; row += 4) {  // whole waves: the shuffles of ln_bwd_row see all 64 lanes
-    const f32x4 v = lss_load4<TX>(x + row * LN_C + 4 * lane);
-    const f32x4 gr = lss_load4<TG>(dy + row * LN_C + 4 * lane);
-    lss_store4(dx + row * LN_C + 4 * lane, ln_bwd_row(v, gr, gm, eps, dg, dbt));
-  }
-  ln_bwd_write_partial(red, dg, dbt, part);
-}
-
 }  // namespace
 
 extern "C" int lss_linear_wgrad_ok(int T, int N, int K) {
@@ -271,51 +243,5 @@ extern "C" int lss_linear_wgrad(const void* x, const void* dy, int T, int N, int
   const int n = std::max(dw != nullptr ? N * K : 0, N);
   hipLaunchKernelGGL(linear_wgrad_reduce_kernel, dim3(lss_cdiv(n, 256)), dim3(256), 0, st, a.part, a.dbp, sp.S, N * K,
                      N, dw, db);
-  return lss_launch_status();
-}
-
-extern "C" int lss_layernorm_bwd_ok(long long rows, int C) {
-  return rows >= 1 && rows < (1LL << 31) && C == LN_C;
-}
-
-extern "C" size_t lss_layernorm_bwd_workspace_bytes(long long rows) {
-  if (!lss_layernorm_bwd_ok(rows, LN_C)) return 0;
-  return (size_t)ln_split(rows).G * 2 * LN_C * sizeof(float);
-}
-
-extern "C" int lss_layernorm_bwd(const void* x, int x_dt, const void* dy, int dy_dt, const float* gamma,
-                                 long long rows, int C, float eps, void* workspace, size_t workspace_bytes, void* dx,
-                                 int dx_dt, float* dgamma, float* dbeta, void* stream) {
-  LSS_CHECK_PTR(x); LSS_CHECK_PTR(dy); LSS_CHECK_PTR(gamma); LSS_CHECK_PTR(workspace);
-  LSS_CHECK_PTR(dx); LSS_CHECK_PTR(dgamma); LSS_CHECK_PTR(dbeta);
-  if (!lss_layernorm_bwd_ok(rows, C)) return LSS_E_SHAPE;
-  for (int dt : {x_dt, dy_dt, dx_dt})
-    if (dt != LSS_DT_F32 && dt != LSS_DT_BF16) return LSS_E_LAYOUT;
-  if (!lss_aligned(x, 16) || !lss_aligned(dy, 16) || !lss_aligned(gamma, 16) || !lss_aligned(dx, 16) ||
-      !lss_aligned(workspace, 16) || !lss_aligned(dgamma, 4) || !lss_aligned(dbeta, 4))
-    return LSS_E_ALIGN;
-  if (workspace_bytes < lss_layernorm_bwd_workspace_bytes(rows)) return LSS_E_WORKSPACE;
-  const LnSplit sp = ln_split(rows);
-  float* part = static_cast<float*>(workspace);
-  hipStream_t st = lss_stream(stream);
-  const int code = (x_dt == LSS_DT_BF16 ? 4 : 0) | (dy_dt == LSS_DT_BF16 ? 2 : 0) | (dx_dt == LSS_DT_BF16 ? 1 : 0);
-#define LSS_LNB(TX, TG, TO)                                                                                     \
-  hipLaunchKernelGGL((layernorm_bwd_kernel<TX, TG, TO>), dim3(sp.G), dim3(256), 0, st, static_cast<const TX*>(x), \
-                     static_cast<const TG*>(dy), gamma, rows, sp.rpg, eps, static_cast<TO*>(dx), part)
-  typedef unsigned short bf;
-  switch (code) {
-    case 0: LSS_LNB(float, float, float); break;
-    case 1: LSS_LNB(float, float, bf); break;
-    case 2: LSS_LNB(float, bf, float); break;
-    case 3: LSS_LNB(float, bf, bf); break;
-    case 4: LSS_LNB(bf, float, float); break;
-    case 5: LSS_LNB(bf, float, bf); break;
-    case 6: LSS_LNB(bf, bf, float); break;
-    default: LSS_LNB(bf, bf, bf); break;
-  }
-#undef LSS_LNB
-  int rc = lss_launch_status();
-  if (rc != 0) return rc;
-  hipLaunchKernelGGL(layernorm_bwd_reduce_kernel, dim3(2), dim3(256), 0, st, part, sp.G, dgamma, dbeta);
   return lss_launch_status();
 }

@@ -81,7 +81,24 @@ __device__ __forceinline__ void lss_store4(unsigned short* p, f32x4 v) {
   *reinterpret_cast<uint2*>(p) = o;
 }
 
-// ---- erf and GELU.  The GEMM epilogue (linear_mfma.hip), the fused FFN (ffn_fused.hip) and the training forward and
+// ---- fixed-order sum of split partials (the second stages of linear_grad.hip and of the LayerNorm backward in
+// transformer_pointwise.hip)
+
+// x[i] = the S partials of element i added in split order (four interleaved chains, fixed final tree)
+__device__ __forceinline__ float lg_sum_splits(const float* __restrict__ p, int S, size_t stride) {
+  float s[4] = {0.f, 0.f, 0.f, 0.f};
+  int k = 0;
+  for (; k + 4 <= S; k += 4) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) s[i] += p[(size_t)(k + i) * stride];
+  }
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+    if (k + i < S) s[i] += p[(size_t)(k + i) * stride];
+  return (s[0] + s[1]) + (s[2] + s[3]);
+}
+
+// ---- erf and GELU. The GEMM epilogue (linear_mfma.hip), the fused FFN (ffn_fused.hip) and the training forward and
 // backward (transformer_pointwise.hip) all take the polynomial from here: the fp64 tests rely on their agreement.
 // (conv_mfma.hip's conv_act keeps libm's erff: the fp32 parity path.)
 

@@ -25,6 +25,17 @@ def _f32c(t, name, shape=None):
     return t
 
 
+_DT = {torch.float32: DT_F32, torch.bfloat16: DT_BF16}
+
+
+def _cached_ws(cache, key, nbytes, device):
+    """The uint8 workspace of `nbytes` bytes that `cache` holds under `key`, allocated at the first call."""
+    ws = cache.get(key)
+    if ws is None:
+        ws = cache[key] = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return ws
+
+
 class KernelTimer:
     """Optional HIP-event brackets around native launches (bench.py uses it for
     the roofline numbers).  Events are recorded on torch's current stream - the
@@ -411,14 +422,11 @@ def _depth_fuse_train_args(d3, d4, w_fusion):
                          % (torch.Size((BN, D, H, W)),))
     w2 = w_fusion.reshape(w_fusion.shape[0], -1)
     _f32c(w2, "w_fusion", (D, 2 * D))
-    key = (BN, D, H, W, str(d3.device))
-    ws = _fuse_train_ws.get(key)
-    if ws is None:
-        nbytes = N.lib().lss_depth_fuse_train_workspace_bytes(BN, D, H, W)
-        if nbytes == 0:
-            raise ValueError("the training tail takes D <= 64 and fewer than 2^31 pixels (got BN=%d D=%d H=%d W=%d)"
-                             % (BN, D, H, W))
-        ws = _fuse_train_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=d3.device)
+    nbytes = N.lib().lss_depth_fuse_train_workspace_bytes(BN, D, H, W)
+    if nbytes == 0:
+        raise ValueError("the training tail takes D <= 64 and fewer than 2^31 pixels (got BN=%d D=%d H=%d W=%d)"
+                         % (BN, D, H, W))
+    ws = _cached_ws(_fuse_train_ws, (BN, D, H, W, str(d3.device)), nbytes, d3.device)
     return (BN, D, H, W, d4.shape[2], d4.shape[3]), w2, ws
 
 
@@ -697,7 +705,7 @@ _TORCH_DT = {DT_F32: torch.float32, DT_BF16: torch.bfloat16}
 
 def add_pos(x, pos):
     """q = x + pos: x (B, ..., 256) token rows in fp32|bf16, pos (T, 256) fp32 with T = tokens per sample."""
-    if not x.is_contiguous() or x.dtype not in (torch.float32, torch.bfloat16):
+    if not x.is_contiguous() or x.dtype not in _DT:
         raise ValueError("x must be contiguous fp32/bf16")
     _f32c(pos, "pos")
     B, C = x.shape[0], x.shape[-1]
@@ -706,8 +714,7 @@ def add_pos(x, pos):
         raise ValueError("pos %s does not match %d tokens x %d channels" % (tuple(pos.shape), T, C))
     q = torch.empty_like(x)
     with _timed("add_pos"):
-        N.check(N.lib().lss_add_pos_fwd(N.ptr(x), N.ptr(pos), B, T, C, DT_F32 if x.dtype == torch.float32 else DT_BF16,
-                                        N.ptr(q), N.stream()), "lss_add_pos_fwd")
+        N.check(N.lib().lss_add_pos_fwd(N.ptr(x), N.ptr(pos), B, T, C, _DT[x.dtype], N.ptr(q), N.stream()), "lss_add_pos_fwd")
     return q
 
 
@@ -723,7 +730,7 @@ def deform_attn(value, offsets_logits, ref_x, ref_y, n_heads=8, n_points=8, toke
         layout = VALUE_HEAD_MAJOR
     else:
         raise ValueError("value %s is neither (B,H,W,%d) nor (B,%d,H*W,32)" % (tuple(value.shape), C, n_heads))
-    if not value.is_contiguous() or value.dtype not in (torch.float32, torch.bfloat16):
+    if not value.is_contiguous() or value.dtype not in _DT:
         raise ValueError("value must be contiguous fp32/bf16")
     _f32c(offsets_logits, "offsets_logits", (B, H, W, n_heads * n_points * 3))
     _f32c(ref_x, "ref_x", (W,))
@@ -733,8 +740,7 @@ def deform_attn(value, offsets_logits, ref_x, ref_y, n_heads=8, n_points=8, toke
     out = torch.empty(B, H, W, C, dtype=value.dtype, device=value.device)
     with _timed("deform_attn"):
         N.check(N.lib().lss_deform_attn_fwd(N.ptr(value), layout, N.ptr(offsets_logits), N.ptr(token_bias), N.ptr(ref_x),
-                                            N.ptr(ref_y), B, H, W,
-                                            n_heads, n_points, C, DT_F32 if value.dtype == torch.float32 else DT_BF16,
+                                            N.ptr(ref_y), B, H, W, n_heads, n_points, C, _DT[value.dtype],
                                             N.ptr(out), N.stream()), "lss_deform_attn_fwd")
     return out
 
@@ -787,16 +793,15 @@ def deform_attn_bwd(value, offsets_logits, ref_pts, d_out, H, W):
 
 def layernorm(x, gamma, beta, eps, out_dtype):
     """nn.LayerNorm over the last (256-wide) dim of contiguous fp32|bf16 rows."""
-    if not x.is_contiguous() or x.dtype not in (torch.float32, torch.bfloat16):
+    if not x.is_contiguous() or x.dtype not in _DT:
         raise ValueError("x must be contiguous fp32/bf16")
     C = x.shape[-1]
     _f32c(gamma, "gamma", (C,))
     _f32c(beta, "beta", (C,))
     y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
-    code = {torch.float32: DT_F32, torch.bfloat16: DT_BF16}
     with _timed("layernorm"):
-        N.check(N.lib().lss_layernorm_fwd(N.ptr(x), code[x.dtype], N.ptr(gamma), N.ptr(beta), x.numel() // C, C,
-                                          float(eps), N.ptr(y), code[out_dtype], N.stream()), "lss_layernorm_fwd")
+        N.check(N.lib().lss_layernorm_fwd(N.ptr(x), _DT[x.dtype], N.ptr(gamma), N.ptr(beta), x.numel() // C, C,
+                                          float(eps), N.ptr(y), _DT[out_dtype], N.stream()), "lss_layernorm_fwd")
     return y
 
 
@@ -969,10 +974,7 @@ def conv3x3_wgrad(x, dy):
     if tuple(dy.shape[:3]) != (B, H, W):
         raise ValueError("dy %s does not match x %s" % (tuple(dy.shape), tuple(x.shape)))
     nbytes = N.lib().lss_conv2d_wgrad_workspace_bytes(B, H, W, Cin, Cout)
-    key = (B, H, W, Cin, Cout, str(x.device))
-    ws = _wgrad_ws.get(key)
-    if ws is None:
-        ws = _wgrad_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    ws = _cached_ws(_wgrad_ws, (B, H, W, Cin, Cout, str(x.device)), nbytes, x.device)
     dw = torch.empty(Cout, Cin, 3, 3, dtype=torch.float32, device=x.device)
     with _timed("conv2d_wgrad"):
         N.check(N.lib().lss_conv2d_wgrad(N.ptr(x), N.ptr(dy), B, H, W, Cin, Cout, N.ptr(ws), nbytes, N.ptr(dw),
@@ -1004,10 +1006,7 @@ def linear_wgrad(x, dy, want_dw=True, want_db=True):
     if not (x.is_cuda and dy.is_cuda):
         raise ValueError("x and dy must be GPU tensors")
     nbytes = N.lib().lss_linear_wgrad_workspace_bytes(T, Nout, K)
-    key = ("linear", T, Nout, K, str(x.device))
-    ws = _wgrad_ws.get(key)
-    if ws is None:
-        ws = _wgrad_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+    ws = _cached_ws(_wgrad_ws, ("linear", T, Nout, K, str(x.device)), nbytes, x.device)
     dw = torch.empty(Nout, K, dtype=torch.float32, device=x.device) if want_dw else None
     db = torch.empty(Nout, dtype=torch.float32, device=x.device) if want_db else None
     with _timed("linear_wgrad"):
@@ -1016,36 +1015,54 @@ def linear_wgrad(x, dy, want_dw=True, want_db=True):
     return dw, db
 
 
+def _ln_bwd(fused, x, dy, gamma, eps, out_dtype, thr=0, scale=1.0, seed=None):
+    """What `layernorm_bwd` (fused False: x in fp32 | bf16, dx in out_dtype) and `add_dropout_layernorm_bwd` (fused True:
+    x = s fp32, ds fp32, da in out_dtype) share once their first operand is checked: the checks on dy, gamma, rows and
+    devices, the workspace cached per row count and device, the (2, C) dgamma / dbeta buffer and the call.
+    Returns (dx, da | None, dgamma, dbeta)."""
+    name, xn, on = ("add_dropout_layernorm_bwd", "s", "da_dtype") if fused else ("layernorm_bwd", "x", "dx_dtype")
+    if not dy.is_contiguous() or dy.dtype not in _DT:
+        raise ValueError("dy must be contiguous fp32/bf16")
+    if out_dtype not in _DT:
+        raise ValueError("%s must be fp32 or bf16" % on)
+    if tuple(dy.shape) != tuple(x.shape) or (not fused and x.numel() == 0):
+        raise ValueError("dy %s does not match %s %s" % (tuple(dy.shape), xn, tuple(x.shape)))
+    lib = N.lib()
+    if fused:
+        rows = _add_dropout_ln_rows(x, name)
+    else:
+        rows = x.numel() // x.shape[-1]
+        if not lib.lss_layernorm_bwd_ok(rows, x.shape[-1]):
+            raise ValueError("layernorm_bwd needs rows of 256 (got %s)" % (tuple(x.shape),))
+    C = x.shape[-1]
+    _f32c(gamma, "gamma", (C,))
+    if not (x.is_cuda and dy.is_cuda):
+        raise ValueError("%s and dy must be GPU tensors" % xn)
+    nbytes = (lib.lss_add_dropout_ln_bwd_workspace_bytes if fused else lib.lss_layernorm_bwd_workspace_bytes)(rows)
+    ws = _cached_ws(_wgrad_ws, ("add_dropout_ln" if fused else "layernorm", rows, str(x.device)), nbytes, x.device)
+    dx = torch.empty(x.shape, dtype=torch.float32 if fused else out_dtype, device=x.device)
+    da = torch.empty(x.shape, dtype=out_dtype, device=x.device) if fused else None
+    dgb = torch.empty(2, C, dtype=torch.float32, device=x.device)
+    with _timed(name):
+        if fused:
+            rc = lib.lss_add_dropout_ln_bwd(N.ptr(x), N.ptr(dy), _DT[dy.dtype], N.ptr(gamma), rows, C, float(eps), thr,
+                                            scale, N.ptr(seed), N.ptr(ws), nbytes, N.ptr(dx), N.ptr(da), _DT[out_dtype],
+                                            N.ptr(dgb[0]), N.ptr(dgb[1]), N.stream())
+        else:
+            rc = lib.lss_layernorm_bwd(N.ptr(x), _DT[x.dtype], N.ptr(dy), _DT[dy.dtype], N.ptr(gamma), rows, C,
+                                       float(eps), N.ptr(ws), nbytes, N.ptr(dx), _DT[out_dtype], N.ptr(dgb[0]),
+                                       N.ptr(dgb[1]), N.stream())
+        N.check(rc, "lss_add_dropout_ln_bwd" if fused else "lss_layernorm_bwd")
+    return dx, da, dgb[0], dgb[1]
+
+
 def layernorm_bwd(x, dy, gamma, eps, dx_dtype):
     """K11: backward of `layernorm` (lss_layernorm_bwd).  x, dy contiguous fp32 | bf16 rows of 256, gamma (256) fp32 ->
     (dx like x in dx_dtype, dgamma (256), dbeta (256) fp32).  Mean and 1 / sigma are recomputed from x."""
-    code = {torch.float32: DT_F32, torch.bfloat16: DT_BF16}
-    for t, nm in ((x, "x"), (dy, "dy")):
-        if not t.is_contiguous() or t.dtype not in code:
-            raise ValueError("%s must be contiguous fp32/bf16" % nm)
-    if dx_dtype not in code:
-        raise ValueError("dx_dtype must be fp32 or bf16")
-    C = x.shape[-1]
-    if tuple(dy.shape) != tuple(x.shape) or x.numel() == 0:
-        raise ValueError("dy %s does not match x %s" % (tuple(dy.shape), tuple(x.shape)))
-    _f32c(gamma, "gamma", (C,))
-    rows = x.numel() // C
-    if not N.lib().lss_layernorm_bwd_ok(rows, C):
-        raise ValueError("layernorm_bwd needs rows of 256 (got %s)" % (tuple(x.shape),))
-    if not (x.is_cuda and dy.is_cuda):
-        raise ValueError("x and dy must be GPU tensors")
-    nbytes = N.lib().lss_layernorm_bwd_workspace_bytes(rows)
-    key = ("layernorm", rows, str(x.device))
-    ws = _wgrad_ws.get(key)
-    if ws is None:
-        ws = _wgrad_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
-    dx = torch.empty(x.shape, dtype=dx_dtype, device=x.device)
-    dgb = torch.empty(2, C, dtype=torch.float32, device=x.device)
-    with _timed("layernorm_bwd"):
-        N.check(N.lib().lss_layernorm_bwd(N.ptr(x), code[x.dtype], N.ptr(dy), code[dy.dtype], N.ptr(gamma), rows, C,
-                                          float(eps), N.ptr(ws), nbytes, N.ptr(dx), code[dx_dtype], N.ptr(dgb[0]),
-                                          N.ptr(dgb[1]), N.stream()), "lss_layernorm_bwd")
-    return dx, dgb[0], dgb[1]
+    if not x.is_contiguous() or x.dtype not in _DT:
+        raise ValueError("x must be contiguous fp32/bf16")
+    dx, _, dgamma, dbeta = _ln_bwd(False, x, dy, gamma, eps, dx_dtype)
+    return dx, dgamma, dbeta
 
 
 def dropout_seed(device):
@@ -1115,9 +1132,6 @@ def gelu_dropout_bwd(h, dy, p=0.0, seed=None):
     return dh
 
 
-_PW_DT = {torch.float32: DT_F32, torch.bfloat16: DT_BF16}
-
-
 def _add_dropout_ln_rows(x, name):
     if x.dim() < 1 or x.numel() == 0 or not N.lib().lss_add_dropout_ln_ok(x.numel() // x.shape[-1], x.shape[-1]):
         raise ValueError("%s needs rows of 256, 1 <= rows <= 2^22 (got %s)" % (name, tuple(x.shape)))
@@ -1128,7 +1142,7 @@ def add_dropout_layernorm(res, a, gamma, beta, eps, p=0.0, seed=None):
     """K12: s = res + dropout(a), y = LayerNorm(s) in one pass (lss_add_dropout_ln_fwd).  res, a contiguous fp32 | bf16
     rows of 256 of one shape -> (s, y), both fp32.  seed None = no dropout."""
     for t, nm in ((res, "res"), (a, "a")):
-        if not t.is_contiguous() or t.dtype not in _PW_DT:
+        if not t.is_contiguous() or t.dtype not in _DT:
             raise ValueError("%s must be contiguous fp32/bf16" % nm)
     if tuple(a.shape) != tuple(res.shape):
         raise ValueError("a %s does not match res %s" % (tuple(a.shape), tuple(res.shape)))
@@ -1142,7 +1156,7 @@ def add_dropout_layernorm(res, a, gamma, beta, eps, p=0.0, seed=None):
     s = torch.empty(res.shape, dtype=torch.float32, device=res.device)
     y = torch.empty_like(s)
     with _timed("add_dropout_layernorm"):
-        N.check(N.lib().lss_add_dropout_ln_fwd(N.ptr(res), _PW_DT[res.dtype], N.ptr(a), _PW_DT[a.dtype], rows, C, thr,
+        N.check(N.lib().lss_add_dropout_ln_fwd(N.ptr(res), _DT[res.dtype], N.ptr(a), _DT[a.dtype], rows, C, thr,
                                                scale, N.ptr(seed), N.ptr(gamma), N.ptr(beta), float(eps), N.ptr(s), N.ptr(y),
                                                N.stream()), "lss_add_dropout_ln_fwd")
     return s, y
@@ -1154,32 +1168,7 @@ def add_dropout_layernorm_bwd(s, dy, gamma, eps, da_dtype, p=0.0, seed=None):
     count and device, as `layernorm_bwd`'s."""
     if not s.is_contiguous() or s.dtype != torch.float32:
         raise ValueError("s must be contiguous fp32")
-    if not dy.is_contiguous() or dy.dtype not in _PW_DT:
-        raise ValueError("dy must be contiguous fp32/bf16")
-    if da_dtype not in _PW_DT:
-        raise ValueError("da_dtype must be fp32 or bf16")
-    if tuple(dy.shape) != tuple(s.shape):
-        raise ValueError("dy %s does not match s %s" % (tuple(dy.shape), tuple(s.shape)))
-    rows = _add_dropout_ln_rows(s, "add_dropout_layernorm_bwd")
-    C = s.shape[-1]
-    _f32c(gamma, "gamma", (C,))
-    thr, scale = _mask_args(p, seed, s.device)
-    if not (s.is_cuda and dy.is_cuda):
-        raise ValueError("s and dy must be GPU tensors")
-    nbytes = N.lib().lss_add_dropout_ln_bwd_workspace_bytes(rows)
-    key = ("add_dropout_ln", rows, str(s.device))
-    ws = _wgrad_ws.get(key)
-    if ws is None:
-        ws = _wgrad_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=s.device)
-    ds = torch.empty_like(s)
-    da = torch.empty(s.shape, dtype=da_dtype, device=s.device)
-    dgb = torch.empty(2, C, dtype=torch.float32, device=s.device)
-    with _timed("add_dropout_layernorm_bwd"):
-        N.check(N.lib().lss_add_dropout_ln_bwd(N.ptr(s), N.ptr(dy), _PW_DT[dy.dtype], N.ptr(gamma), rows, C, float(eps),
-                                               thr, scale, N.ptr(seed), N.ptr(ws), nbytes, N.ptr(ds), N.ptr(da),
-                                               _PW_DT[da_dtype], N.ptr(dgb[0]), N.ptr(dgb[1]), N.stream()),
-                "lss_add_dropout_ln_bwd")
-    return ds, da, dgb[0], dgb[1]
+    return _ln_bwd(True, s, dy, gamma, eps, da_dtype, *_mask_args(p, seed, s.device), seed)
 
 
 def pack_conv_weight_s2_dgrad(w_oihw, pad):
@@ -1209,10 +1198,7 @@ def conv4x4_wgrad(xs, dy):
     nbytes = N.lib().lss_conv2d_wgrad4x4_workspace_bytes(B, H, W, Cin, Cout)
     if nbytes == 0:
         raise ValueError("conv4x4_wgrad: channel counts must be multiples of 64 and 8 <= W <= 224")
-    key = ("4x4", B, H, W, Cin, Cout, str(xs.device))
-    ws = _wgrad_ws.get(key)
-    if ws is None:
-        ws = _wgrad_ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=xs.device)
+    ws = _cached_ws(_wgrad_ws, ("4x4", B, H, W, Cin, Cout, str(xs.device)), nbytes, xs.device)
     dw = torch.empty(Cout, Cin, 4, 4, dtype=torch.float32, device=xs.device)
     with _timed("conv2d_wgrad"):
         N.check(N.lib().lss_conv2d_wgrad4x4(N.ptr(xs), N.ptr(dy), B, H, W, Cin, Cout, N.ptr(ws), nbytes, N.ptr(dw),
@@ -1528,10 +1514,7 @@ def conv_bn_act_train_bwd(gyn, y, z, x1n, x2n, weight, gamma, stat, relu, up, wa
         if not plain:
             xcat = torch.empty(B, Hh, Wh, Ct, dtype=torch.bfloat16, device=dev)
         nws = N.lib().lss_conv2d_wgrad_workspace_bytes(B, Hh, Wh, Ct, Cout)
-        key = (B, Hh, Wh, Ct, Cout, str(dev))
-        wws = _wgrad_ws.get(key)
-        if wws is None:
-            wws = _wgrad_ws[key] = torch.empty(nws, dtype=torch.uint8, device=dev)
+        wws = _cached_ws(_wgrad_ws, (B, Hh, Wh, Ct, Cout, str(dev)), nws, dev)
     ws = _bn_workspace(B * Hh * Wh, Cout, dev)
     with _timed("conv_bn_act_train_bwd"):
         N.check(N.lib().lss_conv_bn_act_train_bwd(
@@ -1664,9 +1647,6 @@ def head1x1_bwd(y, head_w, head_b, grad_logits):
 
 _seg_eval_ws = {}
 SEG_EVAL_MAXC = 16
-_SEG_EVAL_DT = {torch.float32: DT_F32, torch.bfloat16: DT_BF16}
-
-
 def _seg_eval_workspace(C, device):
     key = (C, str(device))
     ws = _seg_eval_ws.get(key)
@@ -1690,7 +1670,7 @@ def seg_eval_update(logits, target, confmat, class_weight=None, loss_acc=None, i
     batch's weighted cross-entropy, returned as a 0-d fp32 tensor, and `loss_acc` (1 double) += loss * B.  logits
     (B, C, ...) contiguous fp32 or bf16, target (B, ...) contiguous int64.  Two launches, no host synchronisation.
     `invalid` (1 int64) is only checked: an argmax is always a class, so this form never adds to it."""
-    if logits.dtype not in _SEG_EVAL_DT or not logits.is_cuda or not logits.is_contiguous() or logits.dim() < 2:
+    if logits.dtype not in _DT or not logits.is_cuda or not logits.is_contiguous() or logits.dim() < 2:
         raise ValueError("logits must be a contiguous fp32 or bf16 GPU tensor of shape (B, C, ...)")
     B, C = logits.shape[:2]
     if not 1 <= C <= SEG_EVAL_MAXC or logits.numel() == 0:
@@ -1715,7 +1695,7 @@ def seg_eval_update(logits, target, confmat, class_weight=None, loss_acc=None, i
         raise ValueError("loss_acc needs class_weight")
     ws = _seg_eval_workspace(C, logits.device)
     with _timed("seg_eval_update"):
-        N.check(N.lib().lss_seg_eval_update(N.ptr(logits), _SEG_EVAL_DT[logits.dtype], N.ptr(target), N.ptr(class_weight),
+        N.check(N.lib().lss_seg_eval_update(N.ptr(logits), _DT[logits.dtype], N.ptr(target), N.ptr(class_weight),
                                             B, C, HW, N.ptr(ws), ws.numel() * 4, N.ptr(confmat), N.ptr(loss),
                                             N.ptr(loss_acc), N.stream()), "lss_seg_eval_update")
     return None if loss is None else loss.view(())

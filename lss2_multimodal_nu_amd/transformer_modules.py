@@ -10,7 +10,8 @@ LayerNorm one row kernel).  Training / autograd: under bf16 autocast on the GPU
 (`_transformer_native_ok`) the encoder layer's five linears and both LayerNorms
 are native autograd nodes too (`_LinearFn`: the MFMA GEMM forward, the same GEMM
 on the transposed weight for the input gradient, csrc/linear_grad.hip for the
-weight and bias gradient; `_LayerNormFn`: the row kernel and its backward), next
+weight and bias gradient; `_LayerNormFn`: the row kernel and its backward in
+csrc/transformer_pointwise.hip), next
 to the deformable-attention sampling core (`_DeformAttnFn`: HIP forward and
 backward); GELU + dropout on the hidden and dropout + residual add + LayerNorm
 are native nodes as well (`_GeluDropoutFn`, `_AddDropoutLayerNormFn`:

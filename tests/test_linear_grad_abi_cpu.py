@@ -177,7 +177,7 @@ def test_kernels_use_no_scratch(tmp_path):
                           + build_native.SOURCES["linear_grad.hip"], stderr=subprocess.DEVNULL)
     text = asm.read_text()
     kernels = [k for k in re.findall(r"\.name:\s+(\S+_kernel\S*)\n", text) if not k.endswith(".kd")]
-    assert len(kernels) == 11, kernels   # wgrad + its reduce, 8 LayerNorm-backward dtype forms + their reduce
+    assert len(kernels) == 2, kernels   # wgrad + its reduce (the LayerNorm backward is in transformer_pointwise.hip)
     assert all(int(v) == 0 for v in re.findall(r"\.private_segment_fixed_size:\s*(\d+)", text))
     assert all(int(v) == 0 for v in re.findall(r"\.vgpr_spill_count:\s*(\d+)", text))
     assert all(int(v) <= 64 * 1024 for v in re.findall(r"\.group_segment_fixed_size:\s*(\d+)", text))

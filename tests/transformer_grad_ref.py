@@ -26,8 +26,10 @@ LayerNorm backward (C = 256).  r = the input row (fp32 or bf16, exact in the ker
 (exact), gamma fp32.  With m, d, sigma, xhat = d / sigma of the forward,
     a = g gamma,   m1 = mean a,   m2 = mean(a xhat),   dx = (a - m1 - xhat m2) / sigma,
     dgamma = sum_rows g xhat,   dbeta = sum_rows g.
-The kernel recomputes mean, d and inv = 1 / sigma' with the forward kernel's arithmetic; transformer_gemm_ref documents
-their errors (with E = 0):  dm = (C + 1) u mean|r|,  dd_i = dm + u (|d_i| + dm),  dsigma = rms(dd) + (C / 2 + 4) u sigma,
+The kernel (csrc/transformer_pointwise.hip) recomputes mean, d and inv = 1 / sigma' by the forward's two-pass formula
+(it never rounds the mean, the forward kernel does: one rounding fewer); transformer_gemm_ref documents the forward's
+errors, which bound these too (with E = 0):  dm = (C + 1) u mean|r|,  dd_i = dm + u (|d_i| + dm),
+dsigma = rms(dd) + (C / 2 + 4) u sigma,
 |d'_i / sigma' - xhat_i| <= e_i = (dd_i + |xhat_i| dsigma) / (sigma - dsigma).  From there, counting operations:
     xhat'   one multiply d' inv':                                 ex_i = e_i + u (|xhat_i| + e_i)
     inv'    |inv' - 1 / sigma| <= dinv = dsigma / (sigma (sigma - dsigma))

@@ -5,7 +5,7 @@ tests/test_transformer_pointwise_ref_cpu.py for this helper itself):
   GELU + dropout           gelu_dropout_kernel<., false>    ops.gelu_dropout                ref_gelu_dropout
   its backward             gelu_dropout_kernel<., true>     ops.gelu_dropout_bwd            ref_gelu_dropout_bwd
   add + dropout + LN       add_dropout_ln_fwd_kernel        ops.add_dropout_layernorm       ref_add_dropout_ln
-  its backward             add_dropout_ln_bwd_kernel        ops.add_dropout_layernorm_bwd   ref_add_dropout_ln_bwd
+  its backward             layernorm_bwd_kernel (fused)     ops.add_dropout_layernorm_bwd   ref_add_dropout_ln_bwd
 
 Everything is fp64 on the CPU, u = 2^-24, with the conventions of transformer_gemm_ref / transformer_grad_ref
 (rounding points, `check`, `NotExercised`).  No bound is measured on a kernel.
