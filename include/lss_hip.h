@@ -874,6 +874,63 @@ int lss_rccl_comm_init(const void* id_host, int nranks, int rank, void** comm);
 int lss_allreduce_bucket(void* comm, float* buf, long long n, void* stream);
 int lss_rccl_comm_destroy(void* comm);
 
+/* ---------------------------------------------------------------------------
+ * K13  the camera branch of the vovnet model at inference: c3 -> scene tokens (csrc/camera_branch.hip).
+ * replaces: src/model_vovnet_transformer.py:176-214, 612-620 (AdaptiveFeaturePyramid, `scene_features`' pyramid ->
+ *           sceneunder -> mean over pixels) and src/modules.py:147-207 (ASPPConv, ASPPPooling, ASPP, SceneUnder), in
+ *           eval mode without autograd.
+ *
+ * lss_tapconv_fwd: up to four conv BRANCHES over one input, each an implicit GEMM on v_mfma_f32_16x16x32_bf16,
+ *        y[img, h, w, ch_off_b + o] = act(scale_b[o] * (sum_{live taps t, c} x[img, h + ky_t d_b, w + kx_t d_b, c]
+ *                                                        * w_b[t][o][c] + img_bias[img, o]) + shift_b[o])
+ *   x (BN, H, W, Cin) bf16 NHWC, contiguous.  A branch is (w, ksize 1 | 3, dilation d, scale, shift, ch_off): w is the
+ *   [tap][Cout][Cin] bf16 image of lss_conv2d_pack_weights (9 taps for ksize 3, padding = dilation; 1 tap for ksize
+ *   1), scale / shift (Cout) fp32 or NULL (1 / 0).  Tap (ky, kx) in {-1, 0, 1}^2 is LIVE when |ky d| < H and
+ *   |kx d| < W; the other taps read zero padding only and are skipped.  A live tap zero-fills where it leaves the map
+ *   and never reads another image.
+ *   y      (BN, H, W, y_stride) bf16 or NULL: branch b writes channels ch_off_b .. ch_off_b + Cout - 1 of every pixel
+ *          and nothing else (the concatenation of the branches is never a separate tensor).
+ *   img_bias (BN, Cout) fp32 or NULL: added in front of the folded BatchNorm.  One branch only.
+ *   means  (BN, Cout) fp32 or NULL: the mean over the image's H W pixels of the values as stored (the bf16-rounded
+ *          ones when y is given, the unrounded fp32 ones when y is NULL - then the map is never written).  One branch
+ *          only.  At least one of y, means is required.
+ *   Rounding: x and w are bf16 as given, products are exact, accumulation is fp32 (K is walked tap-major, 64 channels
+ *   at a time, in list order); scale / shift / relu in fp32; ONE round-to-nearest-even to bf16 at the store.  A mean
+ *   adds the pixels in row-major order, one thread per channel, and divides by H W: no float atomics, and no tile
+ *   shape depends on BN, so it is bit-identical run to run and independent of the batch an image sits in.
+ *   Workgroup = one image x one branch x 64 output channels, no workspace.
+ *   lss_tapconv_ok: 1 for 1 <= BN <= 65535, 1 <= H, W <= 1024, H W <= 65536, Cin % 64 == 0, 64 <= Cin <= 4096,
+ *   Cout % 64 == 0, 64 <= Cout <= 1024; else LSS_E_SHAPE.
+ *   Argument checks, all before any HIP call: LSS_E_NULL (desc, x, a branch's w, y and means both NULL), LSS_E_SHAPE
+ *   (lss_tapconv_ok, nbranch outside 1..4, dilation outside 1..1024, img_bias or means with more than one branch,
+ *   y_stride < Cout or not a multiple of 4, ch_off negative, not a multiple of 4 or ch_off + Cout > y_stride),
+ *   LSS_E_LAYOUT (ksize not 1 or 3, relu not 0 or 1), LSS_E_ALIGN (16 B for x, w, scale, shift, img_bias; 8 B for y;
+ *   4 B for means).  Nothing is written when a check fails.
+ *
+ * lss_camera_pool_bias_fwd: the ASPP pooling branch as a per-image bias of the projection.  The bilinear upsample of
+ *   a 1 x 1 map is constant over the image, so
+ *        g[img, c] = relu(scale[c] * (wg[c, :] . mean[img, :]) + shift[c])        bias[img, o] = wj[o, :] . g[img, :]
+ *   mean (BN, C), wg (Cg, C), scale / shift (Cg) or NULL, wj (Cout, Cg), g (BN, Cg) or NULL, bias (BN, Cout): all fp32
+ *   (fp32 weights, fp32 FMA chains of one lane per 64th of K, butterfly sum: fixed order).  LSS_E_NULL (mean, wg, wj,
+ *   bias), LSS_E_SHAPE (BN outside 1..65535, C or Cg outside 1..1024, Cout outside 1..4096), LSS_E_ALIGN (4 B). */
+typedef struct lss_tapconv_branch {
+  const void* w;
+  const float *scale, *shift;
+  int32_t ksize, dilation, ch_off, reserved;
+} lss_tapconv_branch_t;
+typedef struct lss_tapconv_desc {
+  const void* x;
+  void* y;
+  const float* img_bias;
+  float* means;
+  lss_tapconv_branch_t branch[4];
+  int32_t BN, H, W, Cin, Cout, nbranch, y_stride, relu;
+} lss_tapconv_desc_t;
+int lss_tapconv_ok(int BN, int H, int W, int Cin, int Cout);
+int lss_tapconv_fwd(const lss_tapconv_desc_t* desc, void* stream);
+int lss_camera_pool_bias_fwd(const float* mean, const float* wg, const float* scale, const float* shift,
+                             const float* wj, int BN, int C, int Cg, int Cout, float* g, float* bias, void* stream);
+
 /* Layout / dtype conversion helpers between the reference's NCHW fp32 tensors
  * and the conv path's NHWC tensors. */
 int lss_nchw_f32_to_nhwc(const float* src, void* dst, int B, int C, int H, int W, int dt,

@@ -134,6 +134,9 @@ SIGNATURES = {
     "lss_rccl_comm_init": (_i, [_vp, _i, _i, _vp]),
     "lss_allreduce_bucket": (_i, [_vp, _vp, ctypes.c_longlong, _vp]),
     "lss_rccl_comm_destroy": (_i, [_vp]),
+    "lss_tapconv_ok": (_i, [_i] * 5),
+    "lss_tapconv_fwd": (_i, [_vp, _vp]),
+    "lss_camera_pool_bias_fwd": (_i, [_vp] * 5 + [_i] * 4 + [_vp] * 3),
     "lss_nchw_f32_to_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lss_nhwc_to_nchw_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }
@@ -156,6 +159,18 @@ class LiftSplatDesc(ctypes.Structure):
                [("direct_bytes", ctypes.c_ulonglong)] + \
                [(n, _vp) for n in ("depth", "feat", "bev")] + \
                [(n, ctypes.c_int32) for n in ("B", "N", "D", "fH", "fW", "Cin", "C", "X", "Y", "Z", "layout", "math")]
+
+
+class TapconvBranch(ctypes.Structure):
+    """lss_tapconv_branch_t of include/lss_hip.h."""
+    _fields_ = [(n, _vp) for n in ("w", "scale", "shift")] + \
+               [(n, ctypes.c_int32) for n in ("ksize", "dilation", "ch_off", "reserved")]
+
+
+class TapconvDesc(ctypes.Structure):
+    """lss_tapconv_desc_t of include/lss_hip.h."""
+    _fields_ = [(n, _vp) for n in ("x", "y", "img_bias", "means")] + [("branch", TapconvBranch * 4)] + \
+               [(n, ctypes.c_int32) for n in ("BN", "H", "W", "Cin", "Cout", "nbranch", "y_stride", "relu")]
 
 
 _lib = None

@@ -33,6 +33,7 @@ SOURCES = {
     "linear_grad.hip": ["-fno-slp-vectorize"],  # no v_pk_*_f32 next to MFMAs, as conv_ring.hip
     "transformer_pointwise.hip": ["-fno-slp-vectorize"],  # scalar row arithmetic, as the kernels were measured
     "linear_mfma.hip": [],
+    "camera_branch.hip": [],
     "ffn_fused.hip": [],
     "conv_grad.hip": [],
     "conv_wgrad.hip": [],

@@ -2,7 +2,9 @@
 
 OUT OF THE HOT PATH (<1 % of the FLOPs, "stays stock
 PyTorch on ROCm").  They exist here only so that `BEV_TXT` is constructible with
-the reference's `state_dict` layout; nothing in csrc/ touches them.
+the reference's `state_dict` layout; nothing in csrc/ touches them there.
+(`SceneUnder(in_channels=256)` inside `VoVNetBEVTransformer` is another matter: at
+inference its parameters are read by K13, model_vovnet_transformer._CameraBranchPlan.)
 """
 import torch
 from torch import nn

@@ -15,8 +15,11 @@ camera->BEV half runs on the HIP kernels of csrc/ (C = 128 context channels):
 What is NOT here: the VoVNet trunk (`timm`, third-party weights, a by-name
 network fetch in the reference, src/vovnet_timm.py:48-53).  `backbone=` accepts
 any module returning {'c3': (B*N,768,H/16,W/16), 'c4': (B*N,1024,H/32,W/32)};
-the default passes such feature maps straight through.  The TXT branch is stock
-PyTorch (outside the hot path).
+the default passes such feature maps straight through.
+
+The TXT branch: c3 -> feature pyramid -> ASPP -> per-camera scene tokens is about a seventh of the step's FLOPs and
+runs at inference on K13 (csrc/camera_branch.hip, `VoVNetBEVTransformer.scene_tokens`); the six-token tail behind it
+(camera transformer, BEV fusion, predictor) is stock PyTorch.
 """
 import os
 
@@ -53,6 +56,11 @@ FUSE_TAIL_CALLS = {"native": 0, "composition": 0}
 # LSS_DEPTH_HEADS_NATIVE / LSS_DEPTH_TAIL_NATIVE unset: see DESIGN.md 4b for the measurements that decide these
 _DEPTH_HEADS_NATIVE_DEFAULT = "1"
 _DEPTH_TAIL_NATIVE_DEFAULT = "1"
+# which form `VoVNetBEVTransformer.scene_tokens` took: "native" = K13 (eval, no autograd, bf16, GPU), "composition" =
+# sceneunder(feature_pyramid(c3)).mean((2, 3)) on library ops
+CAMERA_BRANCH_CALLS = {"native": 0, "composition": 0}
+# LSS_CAMERA_BRANCH_NATIVE unset: see DESIGN.md 4b for the measurement that decides this
+_CAMERA_BRANCH_NATIVE_DEFAULT = "1"
 
 
 def _nhwc_bf16_rows(hidden):
@@ -446,7 +454,8 @@ class BEVEncoderTransformer(nn.Module):
 
 
 # ----------------------------------------------------------------------------
-# TXT branch (stock PyTorch; outside the hot path)
+# TXT branch.  The modules below are stock PyTorch and define the state_dict; at inference the pyramid and the ASPP
+# (about a seventh of the step's FLOPs) run on K13 through `_CameraBranchPlan`, the six-token tail stays on library ops.
 # ----------------------------------------------------------------------------
 class AdaptiveFeaturePyramid(nn.Module):
     """Two dilated 3x3 branches (d=1, d=2) fused by a 1x1 conv."""
@@ -465,6 +474,97 @@ class AdaptiveFeaturePyramid(nn.Module):
 
     def forward(self, x):
         return self.fusion(torch.cat([self.scale1(x), self.scale2(x)], dim=1))
+
+
+def _conv_is(conv, k, cin=None, cout=None, bias=None):
+    """Is `conv` a plain k x k / stride 1 conv with padding = dilation * (k // 2) (any dilation)?"""
+    if not isinstance(conv, nn.Conv2d) or conv.kernel_size != (k, k) or conv.stride != (1, 1) or conv.groups != 1:
+        return False
+    d = conv.dilation
+    if d[0] != d[1] or conv.padding != (d[0] * (k // 2), d[0] * (k // 2)) or conv.padding_mode != "zeros":
+        return False
+    if (cin is not None and conv.in_channels != cin) or (cout is not None and conv.out_channels != cout):
+        return False
+    return bias is None or (conv.bias is not None) == bias
+
+
+def _bn_is(bn, c):
+    return isinstance(bn, nn.BatchNorm2d) and bn.num_features == c and bn.affine and bn.running_mean is not None
+
+
+class _CameraBranchPlan:
+    """The folded operands of c3 -> scene tokens for K13: one `_FoldedConv` per conv of `feature_pyramid` and
+    `sceneunder` (packed bf16 weights, BatchNorm folded to (scale, shift); rebuilt when a source tensor changes)."""
+
+    MID = 256
+
+    def __init__(self, pyramid, sceneunder):
+        aspp = sceneunder[0]
+        self.modules = self.convs_of(pyramid, sceneunder)
+        self.pyr = [_FoldedConv(b[0], b[1]) for b in (pyramid.scale1, pyramid.scale2)]
+        self.fusion = _FoldedConv(pyramid.fusion[0], pyramid.fusion[1])
+        self.aspp = [_FoldedConv(c[0], c[1]) for c in list(aspp.convs)[:4]]
+        self.pool = _FoldedConv(aspp.convs[4][1], aspp.convs[4][2], pack=False)
+        self.project = _FoldedConv(aspp.project[0], aspp.project[1], pack=False)
+
+    @staticmethod
+    def convs_of(pyramid, sceneunder):
+        """The conv / BN modules the plan reads, or None when the two modules do not have the reference's structure
+        (256 mid channels, two dilated pyramid branches, an ASPP with three atrous rates of any value)."""
+        M = _CameraBranchPlan.MID
+        try:
+            aspp = sceneunder[0]
+            s1, s2, fu = pyramid.scale1, pyramid.scale2, pyramid.fusion
+            convs, proj = list(aspp.convs), aspp.project
+            if len(sceneunder) != 1 or len(convs) != 5 or not isinstance(convs[4][0], nn.AdaptiveAvgPool2d):
+                return None
+            cin = s1[0].in_channels
+            ok = (_conv_is(s1[0], 3, cin, M, True) and _conv_is(s2[0], 3, cin, M, True) and _conv_is(fu[0], 1, 2 * M, M, True)
+                  and _conv_is(convs[0][0], 1, M, M, False) and all(_conv_is(c[0], 3, M, M, False) for c in convs[1:4])
+                  and _conv_is(convs[4][1], 1, M, M, False) and _conv_is(proj[0], 1, 5 * M, M, False)
+                  and convs[4][0].output_size in (1, (1, 1)))
+            pairs = [(s1[0], s1[1]), (s2[0], s2[1]), (fu[0], fu[1])] + [(c[0], c[1]) for c in convs[:4]] + \
+                    [(convs[4][1], convs[4][2]), (proj[0], proj[1])]
+            relus = [s1[2], s2[2], fu[2]] + [c[2] for c in convs[:4]] + [convs[4][3], proj[2]]
+            if not ok or not all(_bn_is(bn, M) for _, bn in pairs) or not all(isinstance(r, nn.ReLU) for r in relus):
+                return None
+            return [m for pair in pairs for m in pair]
+        except (AttributeError, IndexError, TypeError):
+            return None
+
+    def current(self, pyramid, sceneunder):
+        mods = self.convs_of(pyramid, sceneunder)
+        return mods is not None and len(mods) == len(self.modules) and all(a is b for a, b in zip(mods, self.modules))
+
+    def tokens(self, c3):
+        """(BN, Cin, H, W) fp32 -> (BN, 256) fp32 in six launches; no map wider than the 1024-channel ASPP buffer."""
+        dt = ops.DT_BF16
+        M = self.MID
+        x = _to_nhwc(c3, dt)                                                         # L0
+        BN, H, W, _ = x.shape
+        dev = x.device
+        pyr = torch.empty(BN, H, W, 2 * M, dtype=torch.bfloat16, device=dev)
+        branches = []
+        for i, f in enumerate(self.pyr):
+            w, sc, sh = f.get(dt)
+            branches.append((w, 3, f.conv.dilation[0], sc, sh, i * M))
+        ops.tapconv(x, branches, y=pyr)                                              # L1: both pyramid branches
+        w, sc, sh = self.fusion.get(dt)
+        p = torch.empty(BN, H, W, M, dtype=torch.bfloat16, device=dev)
+        p_mean = ops.tapconv(pyr, [(w, 1, 1, sc, sh, 0)], y=p, means=True)           # L2: fusion 1x1 + mean of p
+        cat = torch.empty(BN, H, W, 4 * M, dtype=torch.bfloat16, device=dev)
+        branches = []
+        for i, f in enumerate(self.aspp):
+            w, sc, sh = f.get(dt)
+            branches.append((w, f.conv.kernel_size[0], f.conv.dilation[0], sc, sh, i * M))
+        ops.tapconv(p, branches, y=cat)                                              # L3: the four conv branches
+        _, gsc, gsh = self.pool.get(dt)
+        _, jsc, jsh = self.project.get(dt)
+        wg = self.pool.image("f32", lambda w32: w32[:, :, 0, 0].contiguous())
+        wj = self.project.image("main", lambda w32: ops.pack_conv_weight(w32[:, :4 * M].contiguous(), dt))
+        wjp = self.project.image("pool", lambda w32: w32[:, 4 * M:, 0, 0].contiguous())
+        bias = ops.camera_pool_bias(p_mean, wg, gsc, gsh, wjp)                       # L3': pooled branch -> bias
+        return ops.tapconv(cat, [(wj, 1, 1, jsc, jsh, 0)], img_bias=bias, means=True)  # L4: project + mean
 
 
 class LightweightCameraTransformer(nn.Module):
@@ -629,6 +729,41 @@ class VoVNetBEVTransformer(_LiftSplatMixin, nn.Module):
         return (all(ops.pointwise_conv_bwd_ok(BN, Cd, self.D, hw) for hw in hws)
                 and ops.pointwise_conv_bwd_ok(BN, Cf, self.C, fH * fW))
 
+    def _camera_branch_native_ok(self, c3):
+        """Does `scene_tokens` take K13?  Eval without autograd, a GPU fp32 map, bf16 precision, the reference's module
+        structure, a shape `lss_tapconv_ok` accepts; LSS_CAMERA_BRANCH_NATIVE=0 keeps the library composition."""
+        if os.environ.get("LSS_CAMERA_BRANCH_NATIVE", _CAMERA_BRANCH_NATIVE_DEFAULT) == "0":
+            return False
+        if not (torch.is_tensor(c3) and c3.is_cuda and c3.dim() == 4 and c3.dtype == torch.float32):
+            return False
+        if _dt(self.precision) != ops.DT_BF16:
+            return False
+        fp, su = self.feature_pyramid, self.sceneunder
+        if fp.training or su.training or _needs_autograd(fp, c3) or _needs_autograd(su):
+            return False
+        plan = self.__dict__.get("_camera_plan")
+        if plan is None or not plan.current(fp, su):
+            if _CameraBranchPlan.convs_of(fp, su) is None:
+                return False
+            plan = self.__dict__["_camera_plan"] = _CameraBranchPlan(fp, su)
+        if any(m.weight.device != c3.device or m.weight.dtype != torch.float32 for m in plan.modules):
+            return False
+        BN, Cin, H, W = c3.shape
+        return Cin == plan.pyr[0].conv.in_channels and all(
+            ops.tapconv_ok(BN, H, W, ci, _CameraBranchPlan.MID) for ci in (Cin, 256, 512, 1024))
+
+    def scene_tokens(self, c3):
+        """c3 (B*N, C, fH, fW) -> the per-camera scene tokens (B*N, 256) fp32: feature pyramid, ASPP, mean over the map
+        (ref :612-620).  At inference in bf16 on the GPU this is K13 (six launches, the scene map is never written);
+        every other call - fp32 precision, CPU, training, foreign modules - is the library composition."""
+        if self._camera_branch_native_ok(c3):
+            CAMERA_BRANCH_CALLS["native"] += 1
+            with ops.region("camera_branch"):
+                return self._camera_plan.tokens(c3)
+        CAMERA_BRANCH_CALLS["composition"] += 1
+        scene = self.sceneunder(self.feature_pyramid(c3))
+        return scene.mean(dim=(2, 3))
+
     def forward(self, imgs, rots, trans, intrins, post_rots, post_trans):
         """imgs: (B*N,3,H,W) / (B,N,3,H,W) camera images for a real trunk, or the
         trunk's {'c3','c4'} maps for the default pass-through.  Returns
@@ -651,8 +786,7 @@ class VoVNetBEVTransformer(_LiftSplatMixin, nn.Module):
             bev_seg, refined = be.forward_nhwc(grid.permute(0, 2, 3, 1), dt)
             bev_pooled = refined.float().mean(dim=(1, 2))
 
-        scene = self.sceneunder(self.feature_pyramid(c3))
-        tokens = scene.mean(dim=(2, 3)).view(B, N, -1)
+        tokens = self.scene_tokens(c3).view(B, N, -1)
         if self.camera_transformer is not None:
             tokens = self.camera_transformer(tokens, self.camera_ids.unsqueeze(0).expand(B, -1))
         if self.bev_fusion is not None:

@@ -1892,3 +1892,97 @@ def nhwc_to_nchw(x, dt):
     y = torch.empty(B, C, H, W, dtype=torch.float32, device=x.device)
     N.check(N.lib().lss_nhwc_to_nchw_f32(N.ptr(x), N.ptr(y), B, C, H, W, dt, N.stream()), "lss_nhwc_to_nchw_f32")
     return y
+
+
+# --- K13: the camera branch of the vovnet model at inference (csrc/camera_branch.hip) --------------------------------
+def tapconv_ok(BN, H, W, Cin, Cout):
+    """Does the tap-list conv kernel take (BN, H, W, Cin) -> Cout?  (lss_tapconv_ok)"""
+    return N.lib().lss_tapconv_ok(int(BN), int(H), int(W), int(Cin), int(Cout)) == 1
+
+
+def live_taps(H, W, ksize, dilation):
+    """The taps ky * 3 + kx of a 3x3 conv with `dilation` (padding = dilation) that can reach an (H, W) map: tap
+    (ky, kx) reads zero padding only when |ky d| >= H or |kx d| >= W.  A 1x1 conv has the single tap 0."""
+    if ksize == 1:
+        return [0]
+    return [t for t in range(9) if abs((t // 3 - 1) * dilation) < H and abs((t % 3 - 1) * dilation) < W]
+
+
+def tapconv(x, branches, y=None, img_bias=None, means=False, relu=True, tag="tapconv"):
+    """Up to four conv branches over one NHWC bf16 input in ONE launch (lss_tapconv_fwd).
+
+    x         (BN, H, W, Cin) bf16 contiguous
+    branches  sequence of (w_packed, ksize, dilation, scale, shift, ch_off): w_packed the [tap][Cout][Cin] bf16 image of
+              `pack_conv_weight` (9 taps for ksize 3, 1 for ksize 1), scale / shift (Cout) fp32 or None
+    y         (BN, H, W, Cy) bf16 contiguous or None: branch b writes channels ch_off .. ch_off + Cout - 1 of it
+    img_bias  (BN, Cout) fp32 or None, added in front of the folded BN (one branch only)
+    means     True: also return the (BN, Cout) fp32 per-image channel means of the stored values (one branch only); with
+              y = None the map itself is never written
+    Returns `means` (or None)."""
+    if x.dim() != 4 or x.dtype != torch.bfloat16 or not x.is_contiguous() or not x.is_cuda:
+        raise ValueError("x must be a contiguous (BN, H, W, Cin) bf16 GPU tensor")
+    BN, H, W, Cin = x.shape
+    branches = list(branches)
+    if not 1 <= len(branches) <= 4:
+        raise ValueError("1 to 4 branches per launch, got %d" % len(branches))
+    Cout = branches[0][0].shape[1] if branches[0][0].dim() == 3 else -1
+    if y is None and not means:
+        raise ValueError("nothing to write: give y or ask for the means")
+    if (img_bias is not None or means) and len(branches) != 1:
+        raise ValueError("img_bias and means belong to a single branch")
+    d = N.TapconvDesc()
+    for b, (w, ksize, dilation, scale, shift, ch_off) in enumerate(branches):
+        if ksize not in (1, 3):
+            raise ValueError("branch %d: ksize must be 1 or 3" % b)
+        if (w.dtype != torch.bfloat16 or not w.is_contiguous() or not w.is_cuda
+                or tuple(w.shape) != (ksize * ksize, Cout, Cin)):
+            raise ValueError("branch %d: weights must be a contiguous bf16 GPU [%d][%d][%d] image, got %s %s"
+                             % (b, ksize * ksize, Cout, Cin, w.dtype, tuple(w.shape)))
+        if int(dilation) < 1:
+            raise ValueError("branch %d: dilation must be >= 1" % b)
+        for name, t in (("scale", scale), ("shift", shift)):
+            if t is not None:
+                _f32c(t, "branch %d %s" % (b, name), (Cout,))
+        if y is not None and not (0 <= ch_off and ch_off % 4 == 0 and ch_off + Cout <= y.shape[-1]):
+            raise ValueError("branch %d: channels %d..%d do not fit the output" % (b, ch_off, ch_off + Cout - 1))
+        br = d.branch[b]
+        br.w, br.scale, br.shift = w.data_ptr(), N.ptr(scale), N.ptr(shift)
+        br.ksize, br.dilation, br.ch_off = ksize, int(dilation), int(ch_off)
+    if not tapconv_ok(BN, H, W, Cin, Cout):
+        raise ValueError("lss_tapconv_ok refuses BN=%d H=%d W=%d Cin=%d Cout=%d" % (BN, H, W, Cin, Cout))
+    if y is not None:
+        if (y.dim() != 4 or y.dtype != torch.bfloat16 or not y.is_contiguous() or not y.is_cuda
+                or tuple(y.shape[:3]) != (BN, H, W) or y.shape[3] % 4 != 0):
+            raise ValueError("y must be a contiguous (BN, H, W, Cy) bf16 GPU tensor with Cy % 4 == 0")
+    if img_bias is not None:
+        _f32c(img_bias, "img_bias", (BN, Cout))
+    out = torch.empty(BN, Cout, dtype=torch.float32, device=x.device) if means else None
+    d.x, d.y, d.img_bias, d.means = x.data_ptr(), N.ptr(y), N.ptr(img_bias), N.ptr(out)
+    d.BN, d.H, d.W, d.Cin, d.Cout, d.nbranch = BN, H, W, Cin, Cout, len(branches)
+    d.y_stride, d.relu = (y.shape[3] if y is not None else 0), 1 if relu else 0
+    with _timed(tag):
+        N.check(N.lib().lss_tapconv_fwd(ctypes.byref(d), N.stream()), "lss_tapconv_fwd")
+    return out
+
+
+def camera_pool_bias(mean, wg, scale, shift, wj, want_g=False):
+    """The ASPP pooling branch as a per-image bias of the projection (lss_camera_pool_bias_fwd):
+    g = relu(scale * (wg . mean) + shift) (BN, Cg), bias = wj . g (BN, Cout), all fp32.  Returns bias, or (g, bias)."""
+    if mean.dim() != 2 or wg.dim() != 2 or wj.dim() != 2:
+        raise ValueError("mean (BN, C), wg (Cg, C) and wj (Cout, Cg) must be matrices")
+    BN, C = mean.shape
+    Cg, Cout = wg.shape[0], wj.shape[0]
+    _f32c(mean, "mean")
+    _f32c(wg, "wg", (Cg, C))
+    _f32c(wj, "wj", (Cout, Cg))
+    for name, t in (("scale", scale), ("shift", shift)):
+        if t is not None:
+            _f32c(t, name, (Cg,))
+    if not (1 <= BN <= 65535 and 1 <= C <= 1024 and 1 <= Cg <= 1024 and 1 <= Cout <= 4096):
+        raise ValueError("camera_pool_bias: BN=%d C=%d Cg=%d Cout=%d outside the kernel's limits" % (BN, C, Cg, Cout))
+    g = torch.empty(BN, Cg, dtype=torch.float32, device=mean.device) if want_g else None
+    bias = torch.empty(BN, Cout, dtype=torch.float32, device=mean.device)
+    with _timed("camera_pool_bias"):
+        N.check(N.lib().lss_camera_pool_bias_fwd(N.ptr(mean), N.ptr(wg), N.ptr(scale), N.ptr(shift), N.ptr(wj), BN, C, Cg,
+                                                 Cout, N.ptr(g), N.ptr(bias), N.stream()), "lss_camera_pool_bias_fwd")
+    return (g, bias) if want_g else bias
