@@ -38,6 +38,23 @@ constexpr int KS_ROWS = 7;        // patch rows: the <= 5 image rows a pixel blo
 constexpr int KS_POSB = 64;       // bytes per patch position and chunk (32 channels bf16)
 constexpr int KS_LDS_MAX = 160 * 1024;
 
+// Where the B-fragment reads of k-step s + 1 go (all three kernels).  Interleaved: tile j's read behind tile j's MFMAs
+// of k-step s - it issues while the matrix pipe works, PXT - 1 reads are outstanding at every MFMA group and the counted
+// lgkmcnt fits the 4-bit counter.  Clustered (-DKS_READS_CLUSTER, tools/build_diag_libs.sh KS_CLUSTER: the form the
+// kernels had first, kept for same-box A/B): all PXT reads in front of the MFMAs of k-step s - at one wave per SIMD
+// nothing issues MFMAs while the cluster issues, and the four waves' clusters hit the LDS array at the same moment, so
+// its 128 B / clk and the matrix pipe take turns instead of overlapping ("Reads between the MFMAs").
+#ifdef KS_READS_CLUSTER
+constexpr bool KS_READS_INTERLEAVED = false;
+#else
+constexpr bool KS_READS_INTERLEAVED = true;
+#endif
+#ifdef KS_DIAG_NOREAD   // timing-only diagnostic build: the fragments are read once
+constexpr bool KS_READS = false;
+#else
+constexpr bool KS_READS = true;
+#endif
+
 __device__ __attribute__((aligned(128))) unsigned char lss_ks_zero_page[128];  // source of out-of-image patch pieces
 
 // Input patch -> LDS by LDS-DMA: [chunk][channel half][position][32 B]; a piece = 32 positions of one half; patch
@@ -277,7 +294,9 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(const KsArgs a) {
   // (two 1-KiB loads per 10-20 MFMAs: nothing next to the LDS-DMA burst of the prologue).  The prologue is a fill-rate
   // problem - every CU pulls its patch AND its 72-144 KiB of weights at once, ~70 GB/s per CU - so bytes that can
   // arrive during the MFMAs should: with everything requested up front (-DKS_WPRE_ALL, the first form of this kernel)
-  // kernel entry -> operands landed took 3.0-3.6 us of the 7-9.
+  // kernel entry -> operands landed took 3.0-3.6 us of the 7-9.  (Requesting the tail here WITHOUT waiting for it cannot be
+  // written with the LDS-DMA builtin - hipcc drains vmcnt(0) at the first use of any load while a piece is outstanding -
+  // and would buy 0.12-0.20 us of the main phase at most: DESIGN.md section 4e, profiles/r20_ks_tile2d_ab.txt.)
 #ifdef KS_WPRE_ALL
   constexpr int WPRE = KSW;
 #else
@@ -302,14 +321,22 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(const KsArgs a) {
   st.stamp(1);  // every request (weights, patch pieces) has been issued
   constexpr int NOWN = (PXT + NKW - 1) / NKW;   // tiles a wave finishes: j = kp, kp + NKW, ...
   const int ch = cb * 32 + kq * 8;             // this lane's 8 consecutive output channels
+  // (bounds-checked buffer loads, no branch: a null residual is an empty buffer, a dead tile or pixel an offset past
+  // its end - both read zeros.  A load under a branch made hipcc wait for it - vmcnt(0), the whole patch - on the spot.)
+  const __amdgpu_buffer_rsrc_t rrsrc = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<unsigned short*>(a.residual), 0, a.residual ? (int)((size_t)a.B * HW * a.Cout * 2) : 0, 0x00020000);
+  // ob[k]: byte offset of this lane's 8 channels of its pixel of finished tile k in y (and the residual), or KS_DEAD -
+  // a slot past the wave's tiles or a pixel past the block's end
+  constexpr int KS_DEAD = 0x7ffffff0;
+  int ob[NOWN];
   uint4 rres[NOWN];
 #pragma unroll
   for (int k = 0; k < NOWN; ++k) {
     const int j = kp + k * NKW;
     const int pl = (ph * PXT + j) * 16 + n;
-    rres[k] = make_uint4(0, 0, 0, 0);
-    if (a.residual != nullptr && j < PXT && pl < npx)
-      rres[k] = *reinterpret_cast<const uint4*>(a.residual + ((size_t)b * HW + p0 + pl) * a.Cout + ch);
+    ob[k] = j < PXT && pl < npx ? (int)((((size_t)b * HW + p0 + pl) * a.Cout + ch) * 2) : KS_DEAD;
+    const u32x4 rv = __builtin_amdgcn_raw_buffer_load_b128(rrsrc, ob[k], 0, 0);
+    rres[k] = make_uint4(rv[0], rv[1], rv[2], rv[3]);
   }
   // epilogue constants of this lane's 8 consecutive channels, requested with everything else: 16 registers through
   // the main phase.  Requested after it - between the two barriers of the exchange, where they used to be - their
@@ -327,26 +354,27 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(const KsArgs a) {
   st.stamp(2);
 
   // ---- main phase: KSW k-steps x PXT pixel tiles x 2 channel tiles, nothing but LDS reads and MFMAs ----
-  // ONE wave per SIMD: nobody else hides an LDS round trip, so the pixel fragments of k-step s + 1 are requested - all
-  // PXT of them - before the 2 PXT MFMAs of k-step s issue (two fragment sets by k-step parity; sched_barrier keeps
-  // hipcc from sinking the requests next to their use: left alone it waited with lgkmcnt(0) in front of every MFMA
-  // pair, i.e. one exposed LDS latency per 32 matrix cycles).
+  // ONE wave per SIMD: nobody else hides an LDS round trip, so the pixel fragments of k-step s + 1 are requested while
+  // k-step s computes (two fragment sets by k-step parity) - tile j's behind tile j's MFMA pair (KS_READS_INTERLEAVED,
+  // above).  The sched_barriers pin that order: left alone hipcc sinks the requests next to their use and waits with
+  // lgkmcnt(0) in front of every MFMA pair, i.e. one exposed LDS latency per 32 matrix cycles.
   bf16x8 fb[2][PXT];
-  auto load_frags = [&](int buf, int s) {
+  auto load_frag = [&](int buf, int s, int j) {
     const unsigned char* cbase = smem + (size_t)(kp * CPW + s / 9) * a.nposp * KS_POSB;
     const int tap = s % 9;
-    const int toff = ((tap / 3) * WP + (tap % 3)) * 32;
-#pragma unroll
-    for (int j = 0; j < PXT; ++j) fb[buf][j] = *reinterpret_cast<const bf16x8*>(cbase + ab[j] + toff);
+    fb[buf][j] = *reinterpret_cast<const bf16x8*>(cbase + ab[j] + ((tap / 3) * WP + (tap % 3)) * 32);
   };
   st.main_begin();
-  load_frags(0, 0);
+#pragma unroll
+  for (int j = 0; j < PXT; ++j) load_frag(0, 0, j);
 #pragma unroll
   for (int s = 0; s < KSW; ++s) {
     if (s + WPRE < KSW) load_w(s + WPRE);
-#ifndef KS_DIAG_NOREAD                                // timing-only diagnostic builds (tools/build_diag_libs.sh KS_NOREAD ..)
-    if (s + 1 < KSW) load_frags((s + 1) & 1, s + 1);
-#endif
+    if constexpr (KS_READS && !KS_READS_INTERLEAVED) {
+      if (s + 1 < KSW)
+#pragma unroll
+        for (int j = 0; j < PXT; ++j) load_frag((s + 1) & 1, s + 1, j);
+    }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int j = 0; j < PXT; ++j) {
@@ -356,6 +384,10 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(const KsArgs a) {
       acc[j][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s][0], fb[s & 1][j], acc[j][0], 0, 0, 0);
       acc[j][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s][1], fb[s & 1][j], acc[j][1], 0, 0, 0);
 #endif
+      if constexpr (KS_READS && KS_READS_INTERLEAVED) {
+        if (s + 1 < KSW) load_frag((s + 1) & 1, s + 1, j);
+        __builtin_amdgcn_sched_barrier(0);
+      }
     }
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -398,19 +430,15 @@ __global__ __launch_bounds__(256, 1) void conv_ks_kernel(const KsArgs a) {
   });
 #pragma unroll
   for (int k = 0; k < NOWN; ++k) {
-    const int j = kp + k * NKW;
-    const int pl = (ph * PXT + j) * 16 + n;
-    const bool live = j < PXT && pl < npx;               // dead tiles and pixels compute on a clamped address, no store
-    const size_t o = ((size_t)b * HW + p0 + (live ? pl : 0)) * a.Cout + ch;
     float v[8];
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
       for (int i = 0; i < 4; ++i) v[4 * ct + i] = sum[k][ct][i];
     const u32x4 ov = ks_finish8<true>(v, sc, sh, rres[k], a.relu != 0, false);
-    if (live) {
-      if (a.wt) __builtin_amdgcn_raw_buffer_store_b128(ov, yrsrc, (int)(o * 2), 0, 16);  // write-through
-      else *reinterpret_cast<u32x4*>(a.y + o) = ov;
+    if (ob[k] != KS_DEAD) {                              // dead tiles and pixels compute, no store
+      if (a.wt) __builtin_amdgcn_raw_buffer_store_b128(ov, yrsrc, ob[k], 0, 16);  // write-through
+      else *reinterpret_cast<u32x4*>(reinterpret_cast<unsigned char*>(a.y) + ob[k]) = ov;
     }
   }
   st.drain();
@@ -485,6 +513,8 @@ KsPlan ks_plan(int B, int H, int W, int Cin, int Cout) {
   else return pl;
   p.B = B; p.H = H; p.W = W; p.Cin = Cin; p.Cout = Cout;
   const long long HW = (long long)H * W;
+  // (a 2-D pixel tile instead of the flattened block - 25 x 13 at Cin 64, 52 KiB of patch against 92 - was built and
+  // measured 0.45 us per launch SLOWER: the fill is not priced per byte.  DESIGN.md section 4e)
   if (p.PB > 4 * W + 1) return pl;                   // a pixel block spans at most five image rows
   p.npb = (int)((HW + p.PB - 1) / p.PB);
   p.ncb = Cout / 32;
@@ -601,25 +631,34 @@ __global__ __launch_bounds__(256, 1) void conv_ks_s2_dual_kernel(const KsS2Args 
 
   // ---- main phase: 9 k-steps x PXT pixel tiles x 4 channel tiles, + the 1x1's 4 PXT MFMAs on the centre tap ----
   bf16x8 fb[2][PXT];
-  auto load_frags = [&](int buf, int s) {
+  auto load_frag = [&](int buf, int s, int j) {
     const unsigned char* cbase = smem + (size_t)kp * a.nposp * KS_POSB;
     const int ky = s / 3, kx = s % 3;
     const int toff = (ky * WP + (kx == 1 ? 0 : kx == 0 ? a.Wo : a.Wo + 1)) * 32;
-#pragma unroll
-    for (int j = 0; j < PXT; ++j) fb[buf][j] = *reinterpret_cast<const bf16x8*>(cbase + ab[j] + toff);
+    fb[buf][j] = *reinterpret_cast<const bf16x8*>(cbase + ab[j] + toff);
   };
   st.main_begin();
-  load_frags(0, 0);
+#pragma unroll
+  for (int j = 0; j < PXT; ++j) load_frag(0, 0, j);
 #pragma unroll
   for (int s = 0; s < 9; ++s) {
     if (s + WPRE < 9) load_w(s + WPRE);
-    if (s + 1 < 9) load_frags((s + 1) & 1, s + 1);
+    if constexpr (!KS_READS_INTERLEAVED) {
+      if (s + 1 < 9)
+#pragma unroll
+        for (int j = 0; j < PXT; ++j) load_frag((s + 1) & 1, s + 1, j);
+    }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-    for (int j = 0; j < PXT; ++j)
+    for (int j = 0; j < PXT; ++j) {
 #pragma unroll
       for (int ct = 0; ct < CT; ++ct)
         acc[j][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s][ct], fb[s & 1][j], acc[j][ct], 0, 0, 0);
+      if constexpr (KS_READS_INTERLEAVED) {
+        if (s + 1 < 9) load_frag((s + 1) & 1, s + 1, j);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
     if (s == 4) {
 #pragma unroll
       for (int j = 0; j < PXT; ++j)
@@ -885,24 +924,32 @@ __global__ __launch_bounds__(256, 1) void conv_ks_stem_kernel(const KsStemArgs a
 
   // ---- main phase: 98 k-steps x 6 row segments x 2 channel tiles, LDS reads, weight requests and MFMAs only ----
   bf16x8 fb[2][PXT];
-  auto load_frags = [&](int buf, int s) {
+  auto load_frag = [&](int buf, int s, int j) {
     const int tap = s >> 1, ky = tap / 7, kx = tap % 7;
     const int toff = (ky * ST_PW + ((kx & 1) ? ST_NE + (kx >> 1) : (kx >> 1))) * 32;
     const unsigned char* cbase = smem + (size_t)(s & 1) * 2 * ST_NPOSP * 32 + ab0 + toff;
-#pragma unroll
-    for (int j = 0; j < PXT; ++j) fb[buf][j] = *reinterpret_cast<const bf16x8*>(cbase + j * (2 * ST_PW * 32));
+    fb[buf][j] = *reinterpret_cast<const bf16x8*>(cbase + j * (2 * ST_PW * 32));
   };
   st.main_begin();
-  load_frags(0, 0);
+#pragma unroll
+  for (int j = 0; j < PXT; ++j) load_frag(0, 0, j);
 #pragma unroll
   for (int s = 0; s < ST_KS; ++s) {
     if (s + ST_WPRE < ST_KS) load_w(s + ST_WPRE);
-    if (s + 1 < ST_KS) load_frags((s + 1) & 1, s + 1);
+    if constexpr (!KS_READS_INTERLEAVED) {
+      if (s + 1 < ST_KS)
+#pragma unroll
+        for (int j = 0; j < PXT; ++j) load_frag((s + 1) & 1, s + 1, j);
+    }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int j = 0; j < PXT; ++j) {
       acc[j][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s][0], fb[s & 1][j], acc[j][0], 0, 0, 0);
       acc[j][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[s][1], fb[s & 1][j], acc[j][1], 0, 0, 0);
+      if constexpr (KS_READS_INTERLEAVED) {
+        if (s + 1 < ST_KS) load_frag((s + 1) & 1, s + 1, j);
+        __builtin_amdgcn_sched_barrier(0);
+      }
     }
     __builtin_amdgcn_sched_barrier(0);
   }

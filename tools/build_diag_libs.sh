@@ -9,8 +9,14 @@ python -m lss2_multimodal_nu_amd.build_native > /dev/null
 cd "$(dirname "$0")/../lss2_multimodal_nu_amd/csrc"
 mkdir -p ../../diag_libs /tmp/lss_diag
 for v in STATS NOBLEND NOWDMA "$@"; do
-  case "$v" in KS_*)   # timing-only builds of the K-split kernel: KS_NOREAD (fragments read once), KS_NOMFMA (reads only)
-    /opt/rocm/bin/hipcc -c conv_ks.hip -o /tmp/lss_diag/conv_ks_$v.o -O3 -fPIC -std=c++17 --offload-arch=gfx950 -fno-slp-vectorize -I../../include $([ "$v" = KS_WPRE_ALL ] && echo -DKS_WPRE_ALL || echo -DKS_DIAG_${v:3})
+  case "$v" in KS_*)   # timing-only builds of the K-split kernel: KS_NOREAD (fragments read once), KS_NOMFMA (reads only);
+    # same-box A/B builds with the shipped outputs: KS_CLUSTER (the fragment reads of a k-step in one cluster in front
+    # of the previous k-step's MFMAs instead of between them), KS_WPRE_ALL (all weights requested up front)
+    case "$v" in
+      KS_WPRE_ALL) kdef=-DKS_WPRE_ALL;; KS_CLUSTER) kdef=-DKS_READS_CLUSTER;; *) kdef=-DKS_DIAG_${v:3};;
+    esac
+    # (the flags of build_native.py for this file - no -fno-slp-vectorize: an A/B build must differ in its switch alone)
+    /opt/rocm/bin/hipcc -c conv_ks.hip -o /tmp/lss_diag/conv_ks_$v.o -O3 -fPIC -std=c++17 --offload-arch=gfx950 -I../../include $kdef
     /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../../diag_libs/liblss_$v.so $(ls build/*.o | grep -v conv_ks.o) /tmp/lss_diag/conv_ks_$v.o -ldl
     continue;;
   esac
