@@ -165,6 +165,17 @@ __device__ __forceinline__ uint4 load_in_piece(const ConvArgs& a, int b, int iy,
   return out;
 }
 
+// BN statistics of channel c (both kernels): the lane halves h = 0, 1 hold the sums s1 = sum raw, s2 = sum raw^2 over
+// different pixel rows of the same channel; half 0 adds the pair's totals to stats[c], stats[Cout + c]
+__device__ __forceinline__ void bn_stats_add(float* stats, int Cout, int c, int h, bool cok, float s1, float s2) {
+  s1 += __shfl_xor(s1, 32, 64);
+  s2 += __shfl_xor(s2, 32, 64);
+  if (h == 0 && cok) {
+    atomicAdd(stats + c, s1);
+    atomicAdd(stats + Cout + c, s2);
+  }
+}
+
 template <typename T, bool FUSED>
 __global__ __launch_bounds__(256) void conv_direct_kernel(ConvArgs a) {
   constexpr int PIECE = Frag<T>::PIECE;
@@ -260,14 +271,7 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(ConvArgs a) {
         else reinterpret_cast<float*>(y)[o] = v;
       }
     }
-    if (a.stats) {
-      s1 += __shfl_xor(s1, 32, 64);
-      s2 += __shfl_xor(s2, 32, 64);
-      if (h == 0 && cok) {
-        atomicAdd(a.stats + co, s1);
-        atomicAdd(a.stats + a.Cout + co, s2);
-      }
-    }
+    if (a.stats) bn_stats_add(a.stats, a.Cout, co, h, cok, s1, s2);
   }
 }
 
@@ -309,23 +313,14 @@ __global__ __launch_bounds__(256) void conv_direct_kernel(ConvArgs a) {
 // under the last taps' MFMAs, PSP = pixel-split pairs on one weight ring, 64-channel tall tiles, mixed full / half
 // height launches, s_setprio around the MFMA groups, a 3-slot ring for KC = 32.  The big layers now run on the
 // loader / consumer kernel of conv_ring.hip at the sizes it takes; this kernel keeps them at small batch.)
-// LDS bytes of one workgroup of the tile body below (same formulas; the body static_asserts the match)
 constexpr int LSS_CONV_RING32 = 4;  // ring slots of the KC = 32 kernels
-template <int RT, int BN, int MODE, int KH, int KW, int KC, int KSP, int TPS = 1>
-constexpr int conv_lds_smem_bytes() {
-  constexpr int TH = (4 / (BN / 64)) * RT * 2, IW = 16 + KW - 1, IH = TH + KH - 1, POSB = KC * 2 + 16;
-  constexpr int IROWB = (IW * POSB + 255) / 256 * 256, W_BYTES = TPS * BN * KC * 2, PPP = KC / 8;
-  constexpr int OUT_BYTES = (TH / (KC == 32 ? 2 : 1)) * 16 * (BN + 4) * 4;
-  constexpr int GROUP_BYTES = ((KC == 32 ? LSS_CONV_RING32 : 3) * W_BYTES + IH * IROWB + 1023) / 1024 * 1024;
-  constexpr int SRC_PIECES = (MODE == 1 && KC == 32) ? (((IH - 1) / 2 + 3) * ((IW - 1) / 2 + 3) * PPP + 63) / 64 : 0;
-  return (KSP * GROUP_BYTES > OUT_BYTES ? KSP * GROUP_BYTES : OUT_BYTES) + SRC_PIECES * 1024;
-}
 
-// The tile body: one workgroup's output tile.  bid / nwg: index of the tile in its class and the size of the class
-// (XCD-aware order), nblk_y: index of the BN-wide channel block, oy_base: first image row of the class (0).
-template <int RT, int BN, int MODE, int KH, int KW, int PAD, int KC = 64, int KSP = 1, bool HEAD = false, int TPS = 1>
-__device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int tilesY, int bid, int nwg, int nblk_y,
-                                              int oy_base, unsigned char* smem) {
+// Everything one instantiation of the tile kernel knows at compile time: the tile, its LDS images and their sizes,
+// the work per thread.  The kernel sizes its LDS from SMEM_BYTES; every phase below reads its constants here.
+template <int RT_, int BN_, int MODE_, int KH_, int KW_, int PAD_, int KC_ = 64, int KSP_ = 1, bool HEAD_ = false, int TPS_ = 1>
+struct TileCfg {
+  static constexpr int RT = RT_, BN = BN_, MODE = MODE_, KH = KH_, KW = KW_, PAD = PAD_, KC = KC_, KSP = KSP_, TPS = TPS_;
+  static constexpr bool HEAD = HEAD_;
   // KSP = 2: intra-workgroup split-K for grids that cannot fill the chip (layer2/layer3: 112-208
   // workgroups of 18-36 latency-bound steps on 256 CUs).  512 threads = two 4-wave groups, each
   // with its own weight ring and patch, each taking half of the input-channel chunks; the second
@@ -341,47 +336,206 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
   // (39 KB of LDS, <= 168 VGPRs) so THREE workgroups share a CU - used for the big stride-1 layers,
   // whose 728 / 1300 tiles then run in one / two full rounds instead of 1.4 / 2.5 on 512 slots.
   static_assert(KC == 64 || KC == 32, "KC");
-  constexpr int PPP = KC / 8;   // 16-B pieces per patch position
-  constexpr int KS = KC / 16;   // MFMA k-steps per tap
-  constexpr int PSH = KC == 64 ? 3 : 2;  // log2(PPP)
-  constexpr int TH = (4 / (BN / 64)) * RT * 2;  // image rows per workgroup
-  constexpr bool FUSED = MODE == 1;
-  constexpr int NT = KH * KW;
-  constexpr int NS = NT / TPS;  // steps per chunk
-  constexpr int TW = 16, IW = TW + KW - 1, IH = TH + KH - 1, POSB = KC * 2 + 16;
-  constexpr int IROWB = (IW * POSB + 255) / 256 * 256;  // 2816 (KC = 64), 1536 (KC = 32)
-  constexpr int IN_BYTES = IH * IROWB;
-  constexpr int W1_BYTES = BN * KC * 2;      // slab of one tap
-  constexpr int W_BYTES = TPS * W1_BYTES;    // slab of one step
-  constexpr int WPT = W_BYTES / 4096;  // LDS-DMA instructions per wave per step (1 KiB each)
-  constexpr int NWV = 4;               // waves that share one slab
-  constexpr int WCOLS = BN / 64;  // waves along the channel axis
-  constexpr int IPT = (IH * IW * PPP + 255) / 256;  // 16-B patch pieces per thread per chunk
-  constexpr int OLD = BN + 4;  // fp32 row stride of the epilogue's staged output tile
+  static constexpr int PPP = KC / 8;   // 16-B pieces per patch position
+  static constexpr int KS = KC / 16;   // MFMA k-steps per tap
+  static constexpr int PSH = KC == 64 ? 3 : 2;  // log2(PPP)
+  static constexpr int TH = (4 / (BN / 64)) * RT * 2;  // image rows per workgroup
+  static constexpr bool FUSED = MODE == 1;
+  static constexpr int NT = KH * KW;
+  static constexpr int NS = NT / TPS;  // steps per chunk
+  static constexpr int TW = 16, IW = TW + KW - 1, IH = TH + KH - 1, POSB = KC * 2 + 16;
+  static constexpr int IROWB = (IW * POSB + 255) / 256 * 256;  // 2816 (KC = 64), 1536 (KC = 32)
+  static constexpr int IN_BYTES = IH * IROWB;
+  static constexpr int NPIECE = IH * IW * PPP;  // 16-B pieces of the patch
+  static constexpr int W1_BYTES = BN * KC * 2;      // slab of one tap
+  static constexpr int W_BYTES = TPS * W1_BYTES;    // slab of one step
+  static constexpr int BPT = W1_BYTES / 1024;  // 1-KiB DMA blocks per tap
+  static constexpr int WPT = W_BYTES / 4096;  // LDS-DMA instructions per wave per step (1 KiB each)
+  static constexpr int NWV = 4;               // waves that share one slab
+  static constexpr int WCOLS = BN / 64;  // waves along the channel axis
+  static constexpr int IPT = (NPIECE + 255) / 256;  // 16-B patch pieces per thread per chunk
+  static constexpr int OLD = BN + 4;  // fp32 row stride of the epilogue's staged output tile
   // the epilogue stages the fp32 output tile in LDS: whole (KC = 64) or in two halves of TH/2 rows
-  constexpr int EPH = KC == 32 ? 2 : 1;
-  constexpr int OUT_BYTES = (TH / EPH) * 16 * OLD * 4;  // per pixel group
+  static constexpr int EPH = KC == 32 ? 2 : 1;
+  static constexpr int OUT_BYTES = (TH / EPH) * 16 * OLD * 4;  // per pixel group
   // Weight ring: 3 slots = slabs two steps ahead of the MFMAs; the KC = 32 kernels (half-length steps, three
   // workgroups per CU) keep 4 slots = three steps ahead: a timing build that re-read one L1-hot slab ran them 9-13 %
   // faster while the KC = 64 kernel did not move, i.e. their shorter steps exposed the L2 round trip of the slab.
-  constexpr int NSL = KC == 32 ? LSS_CONV_RING32 : 3, LA = NSL - 1;
-  constexpr int GROUP_BYTES = (NSL * W_BYTES + IN_BYTES + 1023) / 1024 * 1024;  // ring + patch of one K-split group
+  static constexpr int NSL = KC == 32 ? LSS_CONV_RING32 : 3, LA = NSL - 1;
+  static constexpr int WYOUNG = (LA - 1) * WPT;  // DMA instructions of the slabs younger than the next step's
+  static constexpr int PF_ST = NS >= 5 ? NS - 4 : 0;  // the step at which the next patch's loads are issued
+  static constexpr int GROUP_BYTES = (NSL * W_BYTES + IN_BYTES + 1023) / 1024 * 1024;  // ring + patch of one K-split group
   // SRC (fused upsample, KC = 32): the low-res pixels a chunk's patch is interpolated from - at most
   // SRC_H x SRC_W source positions for scale factors >= 2 - are copied ONCE per chunk into LDS by
   // LDS-DMA while the previous chunk's taps run, and the 4-corner blend then reads LDS: 2 DMA
   // instructions per wave instead of 12 scattered global loads per thread in the synchronous
   // chunk-boundary phase (measured: that phase was 17 % of the fused convs).
-  constexpr bool SRC = FUSED && KC == 32;
-  constexpr int SRC_H = (IH - 1) / 2 + 3, SRC_W = (IW - 1) / 2 + 3;  // 7 x 11 for the 10 x 18 patch
-  constexpr int SRC_PIECES = SRC ? (SRC_H * SRC_W * PPP + 63) / 64 : 0;  // 1-KiB DMA pieces per chunk (5)
-  constexpr int SRC_DMA = (SRC_PIECES + 3) / 4;  // DMA instructions per chunk of the wave that issues most (wave 0)
-  constexpr int SRC_BYTES = SRC_PIECES * 1024;
-  constexpr int MAIN_BYTES = KSP * GROUP_BYTES > OUT_BYTES ? KSP * GROUP_BYTES : OUT_BYTES;
-  constexpr int SMEM_BYTES = MAIN_BYTES + SRC_BYTES;
+  static constexpr bool SRC = FUSED && KC == 32;
+  static constexpr int SRC_H = (IH - 1) / 2 + 3, SRC_W = (IW - 1) / 2 + 3;  // 7 x 11 for the 10 x 18 patch
+  static constexpr int SRC_PIECES = SRC ? (SRC_H * SRC_W * PPP + 63) / 64 : 0;  // 1-KiB DMA pieces per chunk (5)
+  static constexpr int SRC_DMA = (SRC_PIECES + 3) / 4;  // DMA instructions per chunk of the wave that issues most (wave 0)
+  static constexpr int SRC_BYTES = SRC_PIECES * 1024;
+  static constexpr int NG = FUSED ? IPT : 1, NSRC = SRC ? SRC_DMA : 1;  // lengths of g_off / g_w and src_o (FusedPieces)
+  static constexpr int MAIN_BYTES = KSP * GROUP_BYTES > OUT_BYTES ? KSP * GROUP_BYTES : OUT_BYTES;
+  static constexpr int SMEM_BYTES = MAIN_BYTES + SRC_BYTES;
   static_assert(SMEM_BYTES <= (KSP == 2 ? 160 : (KC == 32 ? 53 : 80)) * 1024, "workgroups per CU vs 160 KiB of LDS");
   static_assert(!SRC || NS > LA, "the source copies retire at step LA");
   static_assert(KC == 64 || (RT == 2 && BN == 128 && MODE != 2), "KC = 32 is built for the RT = 2, BN = 128 stride-1 tiles");
-  static_assert(SMEM_BYTES == conv_lds_smem_bytes<RT, BN, MODE, KH, KW, KC, KSP, TPS>(), "conv_lds_smem_bytes out of sync");
+  // Output pieces.  A piece = 8 consecutive channels (16 B of bf16) of one pixel; 256 threads cover PPJ pixels x CG
+  // channel groups per pass, so a thread's pixel column, channel group and first row never change: every per-pass
+  // address is one base + a compile-time offset.
+  static constexpr int CG = BN / 8;              // 16-B channel groups per pixel
+  static constexpr int PPJ = 256 / CG;           // pixels per pass
+  static constexpr int RPJ = PPJ / 16;           // image rows per pass
+  static constexpr int HROWS = TH / EPH;         // image rows per staged half (EPH = 2: KC = 32, see OUT_BYTES)
+  static constexpr int HPIECES = HROWS * 16 * CG;
+  static constexpr int EPJ = HPIECES / 256;      // passes per half
+  static_assert(HPIECES % 256 == 0 && PPJ % 16 == 0, "half tiles split evenly over the threads");
+  // EARLY_RES: the residual rows of the launch-bound layers (RT = 1: 152-190 registers, room for 16 more) are
+  // requested at the top of the LAST chunk's taps instead of at the top of the epilogue: phase stamps put the store
+  // phase of the residual layers at 1.6-1.7 us against 1.0-1.1 us for the same tile without a residual - the loads,
+  // issued ~0.6 us before their first use, were still in flight when the store loop wanted them.
+  static constexpr bool EARLY_RES = RT == 1 && EPH == 1 && !HEAD;
+  static constexpr int NRES = HEAD ? 1 : EPJ;  // residual pieces a thread holds
+};
+
+// 16-B piece q of the patch -> its row, its column and its channel piece
+struct PatchPiece {
+  int py, px, part;
+};
+template <class C>
+__device__ __forceinline__ PatchPiece patch_piece(int q) {
+  const int pos = q >> C::PSH, part = q & (C::PPP - 1);
+  const int py = pos / C::IW, px = pos - py * C::IW;
+  return {py, px, part};
+}
+
+// the four corners at p00, +dx, +dy, +dy+dx (in units of P: bytes of the LDS source window, elements of x), blended
+// with the 16-bit fixed-point weights gw = lx | ly << 16
+template <typename P>
+__device__ __forceinline__ uint4 blend_corners(const P* p00, int dx, int dy, const unsigned int& gw) {
+  const uint4 q00 = *reinterpret_cast<const uint4*>(p00);
+  const uint4 q01 = *reinterpret_cast<const uint4*>(p00 + dx);
+  const uint4 q10 = *reinterpret_cast<const uint4*>(p00 + dy);
+  const uint4 q11 = *reinterpret_cast<const uint4*>(p00 + dy + dx);
+  return blend_bf16x8(q00, q01, q10, q11, (float)(gw & 0xffff) * (1.f / 65536.f), (float)(gw >> 16) * (1.f / 65536.f));
+}
+
+// Fused 1x1 head ON THE MATRIX PIPE (ref src/modules.py:115, up2[4]; at most 16 classes), on the HROWS image rows from
+// oyh of the staged fp32 tile: per image row one 16 x 16 x BN product
+// out[pixel][k] = sum_c relu(act[pixel][c]) * head_w[k][c]  on v_mfma_f32_16x16x32_bf16.
+// Both operands are split into bf16 hi + lo parts (x = hi + lo to 16 significant bits) and the three
+// products hi*hi, hi*lo, lo*hi are accumulated in fp32, so the result keeps the accuracy of the fp32
+// head it replaces (the dropped lo*lo term is 2^-16 relative) while the VALU work per pixel falls from
+// ~60 FMA / DPP instructions to ~12 conversions.  A: lane (r = pixel, q) <- 8 consecutive channels of the
+// fp32 tile in LDS (2 ds_read_b128); B: lane (k = lane & 15, q) <- 8 consecutive weights of class k from
+// global (L1-resident: 2 KiB); D: lane (k, q) holds pixels 4q..4q+3 of the row = ONE 16-B NCHW store.
+template <class C>
+__device__ __forceinline__ void head_mfma(const ConvArgs& a, const float* otile, int b, int oyh, int ox0, int lane,
+                                          int wave) {
+  constexpr int BN = C::BN;
+  const int hr = lane & 15, hq = lane >> 4;
+  for (int row = wave; row < C::HROWS; row += 4) {
+    const int oy = oyh + row;
+    f32x4 hacc = {0.f, 0.f, 0.f, 0.f};
+    const float* arow = otile + (row * 16 + hr) * C::OLD + hq * 8;
+    const float* wrow = a.head_w + (size_t)min(hr, a.head_n - 1) * BN + hq * 8;
+    // rolled: one k-step's 16 operand floats live at a time (the other half-tile's waves still hold their
+    // 64 accumulator registers here, and the 168-register budget of three workgroups per CU is what counts)
+#pragma unroll 1
+    for (int s = 0; s < BN / 32; ++s) {
+      bf16x8 xh, xl, wh, wl;
+      {
+        f32x4 w0 = *reinterpret_cast<const f32x4*>(wrow + s * 32);
+        f32x4 w1 = *reinterpret_cast<const f32x4*>(wrow + s * 32 + 4);
+        if (hr >= a.head_n) { w0 = (f32x4){0.f, 0.f, 0.f, 0.f}; w1 = w0; }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float wv = j < 4 ? w0[j & 3] : w1[j & 3];
+          const unsigned short whi = lss_f2bf(wv);
+          wh[j] = (short)whi;
+          wl[j] = (short)lss_f2bf(wv - lss_bf2f(whi));
+        }
+      }
+      {
+        const f32x4 x0 = *reinterpret_cast<const f32x4*>(arow + s * 32);
+        const f32x4 x1 = *reinterpret_cast<const f32x4*>(arow + s * 32 + 4);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          float xv = j < 4 ? x0[j & 3] : x1[j & 3];
+          if (a.relu) xv = fmaxf(xv, 0.f);
+          const unsigned short xhi = lss_f2bf(xv);
+          xh[j] = (short)xhi;
+          xl[j] = (short)lss_f2bf(xv - lss_bf2f(xhi));
+        }
+      }
+      hacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xl, wh, hacc, 0, 0, 0);
+      hacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh, wl, hacc, 0, 0, 0);
+      hacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh, wh, hacc, 0, 0, 0);
+    }
+    if (hr < a.head_n && oy < a.Ho) {
+      const float hb = a.head_b[hr];
+      float* op = a.head_out + (((size_t)b * a.head_n + hr) * a.Ho + oy) * a.Wo + ox0 + hq * 4;
+      if ((a.Wo & 3) == 0 && ox0 + hq * 4 + 4 <= a.Wo) {
+        *reinterpret_cast<f32x4*>(op) = (f32x4){hacc[0] + hb, hacc[1] + hb, hacc[2] + hb, hacc[3] + hb};
+      } else {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (ox0 + hq * 4 + i < a.Wo) op[i] = hacc[i] + hb;
+      }
+    }
+  }
+}
+
+// fused 1x1 head, VALU form (more than 16 classes): the CG = BN / 8 lanes that hold the channels of one pixel reduce
+// their partial dot products with DPP row operations; the activation itself is never stored
+template <class C>
+__device__ __forceinline__ void head_valu(const ConvArgs& a, const float* otile, int b, int oyh, int ox0, int tid) {
+  constexpr int CG = C::CG, OLD = C::OLD;
+  for (int e = tid; e < C::HROWS * 16 * CG; e += 256) {
+    const int pl = e / CG, hc8 = e % CG;
+    const int oy = oyh + (pl >> 4), hx = ox0 + (pl & 15);
+    const f32x4 v0 = *reinterpret_cast<const f32x4*>(otile + pl * OLD + hc8 * 8);
+    const f32x4 v1 = *reinterpret_cast<const f32x4*>(otile + pl * OLD + hc8 * 8 + 4);
+    float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+    if (a.relu) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) v[k] = fmaxf(v[k], 0.f);
+    }
+    for (int k = 0; k < a.head_n; ++k) {
+      const float* hw = a.head_w + k * C::BN + hc8 * 8;
+      float part = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) part = fmaf(v[j], hw[j], part);
+      // sum over the CG lanes of the pixel on DPP row operations (no LDS round trips): lane ^ 1,
+      // lane ^ 2, then - every quad now holding its sum - the other quad of the 8 (row_half_mirror)
+      // and the other half of the 16 (row_mirror)
+      part += lss_dpp_f32<0xB1>(part);
+      part += lss_dpp_f32<0x4E>(part);
+      part += lss_dpp_f32<0x141>(part);
+      if (CG == 16) part += lss_dpp_f32<0x140>(part);
+      if (hc8 == 0 && oy < a.Ho && hx < a.Wo)
+        a.head_out[(((size_t)b * a.head_n + k) * a.Ho + oy) * a.Wo + hx] = part + a.head_b[k];
+    }
+  }
+}
+
+// The tile body: one workgroup's output tile.  The phases that carry the accumulators, the parked patch registers and
+// the ring slot are lambdas of this ONE function, in the order they run: coordinates, fragment offsets, weight-slab
+// issue, fused-gather set-up, the gathers, output pieces, prologue, main loop, K-split hand-over, staging, statistics,
+// head or store.  (As separate functions taking that state by reference each is optimised on its own before it is
+// inlined; measured: accumulators re-formed as one 32-float vector, the last chunk peeled, 12-168 B of new scratch.)
+template <int RT, int BN, int MODE, int KH, int KW, int PAD, int KC = 64, int KSP = 1, bool HEAD = false, int TPS = 1>
+__device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int tilesY, unsigned char* smem) {
+  using C = TileCfg<RT, BN, MODE, KH, KW, PAD, KC, KSP, HEAD, TPS>;
+  constexpr int PPP = C::PPP, KS = C::KS, PSH = C::PSH, TH = C::TH, NS = C::NS, TW = C::TW, IW = C::IW, IH = C::IH;
+  constexpr int POSB = C::POSB, IROWB = C::IROWB, W1_BYTES = C::W1_BYTES, W_BYTES = C::W_BYTES, BPT = C::BPT, WPT = C::WPT;
+  constexpr int NWV = C::NWV, WCOLS = C::WCOLS, IPT = C::IPT, OLD = C::OLD, EPH = C::EPH, NSL = C::NSL, LA = C::LA;
+  constexpr int GROUP_BYTES = C::GROUP_BYTES, SRC_H = C::SRC_H, SRC_W = C::SRC_W, SRC_PIECES = C::SRC_PIECES;
+  constexpr int SRC_DMA = C::SRC_DMA, MAIN_BYTES = C::MAIN_BYTES, WYOUNG = C::WYOUNG, PF_ST = C::PF_ST;
+  constexpr int CG = C::CG, PPJ = C::PPJ, RPJ = C::RPJ, HROWS = C::HROWS, EPJ = C::EPJ;
+  constexpr bool FUSED = C::FUSED, SRC = C::SRC, EARLY_RES = C::EARLY_RES;
+  const int bid = blockIdx.x, nwg = gridDim.x, nblk_y = blockIdx.y;
   const int grp = KSP == 2 ? (int)(threadIdx.x >> 8) : 0;  // K-split group of this wave
   unsigned char* w_tile = smem + grp * GROUP_BYTES;
   unsigned char* in_tile = w_tile + NSL * W_BYTES;
@@ -398,8 +552,7 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
   const int tx = t % tilesX; t /= tilesX;
   const int ty = t % tilesY;
   const int b = t / tilesY;
-  const int oy0 = oy_base + ty * TH, ox0 = tx * TW, n0 = nblk_y * BN;
-  const int dwave = wave;  // index among the waves that share the weight ring
+  const int oy0 = ty * TH, ox0 = tx * TW, n0 = nblk_y * BN;
   const int wc = wave % WCOLS, wr = wave / WCOLS;
   const int prow0 = wr * (2 * RT);
   auto stamp = [&](int k) {
@@ -432,21 +585,21 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
   const int cbase = grp * nchunks;        // first chunk of this group
   const int nsteps = nchunks * NS;
   uint4 ireg[IPT];
-  // weight slab of `step` -> ring slot: lane l of DMA block k lands at byte k*1024 + l*16,
-  // i.e. row 8k + (l >> 3), 16-B slot l & 7, which must hold channel piece slot ^ swz(row)
-  constexpr int BPT = W1_BYTES / 1024;  // 1-KiB DMA blocks per tap
-  auto issue_w = [&](int step, int slot) {
-    const int tap0 = (step % NS) * TPS, chunk = cbase + step / NS;
+  // One 1-KiB LDS-DMA block (index i of this wave) of the weight slab of step `st` of chunk `chunk` -> ring slot:
+  // lane l of DMA block k lands at byte k*1024 + l*16, i.e. row 8k + (l >> 3), 16-B slot l & 7, which must hold
+  // channel piece slot ^ swz(row)
+  auto issue_w1 = [&](int st, int chunk, int slot, int i) {  // st = step inside the chunk
+    const int blk = i * NWV + wave;
+    const int tap = st * TPS + (TPS == 1 ? 0 : blk / BPT), rblk = TPS == 1 ? blk : blk % BPT;
+    const int row = KC == 64 ? rblk * 8 + (lane >> 3) : rblk * 16 + (lane >> 2);
+    const int part = KC == 64 ? (lane & 7) ^ ((row >> 1) & 7) : (lane & 3) ^ ((row >> 2) & 3);
+    const int co = min(n0 + row, a.Cout - 1);  // rows past Cout: any valid address (never stored)
+    lss_glds16(wg + ((size_t)tap * a.Cout + co) * a.Cin + (cbase + chunk) * KC + part * 8,
+           w_tile + slot * W_BYTES + blk * 1024);
+  };
+  auto issue_w = [&](int step, int slot) {  // the whole slab of `step`, counted over this group's chunks
 #pragma unroll
-    for (int i = 0; i < WPT; ++i) {
-      const int blk = i * NWV + dwave;
-      const int tap = tap0 + (TPS == 1 ? 0 : blk / BPT), rblk = TPS == 1 ? blk : blk % BPT;
-      const int row = KC == 64 ? rblk * 8 + (lane >> 3) : rblk * 16 + (lane >> 2);
-      const int part = KC == 64 ? (lane & 7) ^ ((row >> 1) & 7) : (lane & 3) ^ ((row >> 2) & 3);
-      const int co = min(n0 + row, a.Cout - 1);  // rows past Cout: any valid address (never stored)
-      lss_glds16(wg + ((size_t)tap * a.Cout + co) * a.Cin + chunk * KC + part * 8,
-             w_tile + slot * W_BYTES + blk * 1024);
-    }
+    for (int i = 0; i < WPT; ++i) issue_w1(step % NS, step / NS, slot, i);
   };
   // MODE 1: the bilinear source coordinates of a patch piece depend only on its position,
   // not on the chunk, so each thread resolves its IPT pieces ONCE (element offset of the
@@ -479,8 +632,7 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
       const int q = tid + i * 256;
       g_off[i] = 0; g_w[i] = 0;
       if (q < IH * IW * PPP) {
-        const int pos = q >> PSH, part = q & (PPP - 1);
-        const int py = pos / IW, px = pos - py * IW;
+        const auto [py, px, part] = patch_piece<C>(q);
         const int iy = oy0 - PAD + py, ix = ox0 - PAD + px;
         if (iy >= 0 && iy < a.Hin && ix >= 0 && ix < a.Win) {
           const float sy = a.ry * (float)iy, sx = a.rx * (float)ix;
@@ -505,31 +657,17 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
     for (int i = 0; i < IPT; ++i) {
       const int q = tid + i * 256;
       if (q >= IH * IW * PPP) continue;
-      const int pos = q >> PSH, part = q & (PPP - 1);
-      const int py = pos / IW, px = pos - py * IW;
+      const auto [py, px, part] = patch_piece<C>(q);
       uint4 v = make_uint4(0, 0, 0, 0);
       if (g_off[i] & 4) {
         if (skip) {
           const int iy = oy0 - PAD + py, ix = ox0 - PAD + px;
           v = *reinterpret_cast<const uint4*>(x2p + ((b * a.Hin + iy) * a.Win + ix) * a.C2 + c0 + part * 8);
-        } else if (use_src) {
-          const unsigned char* p00 = src_tile + (g_off[i] & ~15);
-          const int dx = (g_off[i] & 1) ? PPP * 16 : 0, dy = (g_off[i] & 2) ? SRC_W * PPP * 16 : 0;
-          const uint4 q00 = *reinterpret_cast<const uint4*>(p00);
-          const uint4 q01 = *reinterpret_cast<const uint4*>(p00 + dx);
-          const uint4 q10 = *reinterpret_cast<const uint4*>(p00 + dy);
-          const uint4 q11 = *reinterpret_cast<const uint4*>(p00 + dy + dx);
-          v = blend_bf16x8(q00, q01, q10, q11, (float)(g_w[i] & 0xffff) * (1.f / 65536.f),
-                           (float)(g_w[i] >> 16) * (1.f / 65536.f));
-        } else {
-          const unsigned short* p00 = xp + (g_off[i] & ~7) + (c0 - a.C2);
-          const int dx = (g_off[i] & 1) ? dxs : 0, dy = (g_off[i] & 2) ? dys : 0;
-          const uint4 q00 = *reinterpret_cast<const uint4*>(p00);
-          const uint4 q01 = *reinterpret_cast<const uint4*>(p00 + dx);
-          const uint4 q10 = *reinterpret_cast<const uint4*>(p00 + dy);
-          const uint4 q11 = *reinterpret_cast<const uint4*>(p00 + dy + dx);
-          v = blend_bf16x8(q00, q01, q10, q11, (float)(g_w[i] & 0xffff) * (1.f / 65536.f),
-                           (float)(g_w[i] >> 16) * (1.f / 65536.f));
+        } else if (use_src) {  // corners from the LDS source window: byte strides
+          v = blend_corners(src_tile + (g_off[i] & ~15), (g_off[i] & 1) ? PPP * 16 : 0,
+                            (g_off[i] & 2) ? SRC_W * PPP * 16 : 0, g_w[i]);
+        } else {  // corners from global memory: element strides
+          v = blend_corners(xp + (g_off[i] & ~7) + (c0 - a.C2), (g_off[i] & 1) ? dxs : 0, (g_off[i] & 2) ? dys : 0, g_w[i]);
         }
       }
       *reinterpret_cast<uint4*>(in_tile + py * IROWB + px * POSB + part * 16) = v;
@@ -546,43 +684,28 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
   // does `chunk` read the upsampled tensor through src_tile?
   auto src_chunk = [&](int chunk) { return use_src && chunk < nchunks && (cbase + chunk) * KC >= a.C2; };
 
-  // input patch of one 64-channel chunk.  !FUSED: plain 16-B loads, unrolled so they
-  // can be parked in registers (prefetch).  FUSED: the 4-corner bilinear gather goes
-  // straight to LDS piece by piece (rolled loop: keeps the live set small).
+  // input patch of one 64-channel chunk of a plain (or phase-plane) input: 16-B loads, unrolled so they can be parked
+  // in registers (prefetch)
   auto gather_in = [&](int chunk, bool to_lds) {
-    if (FUSED) {
-#pragma unroll 1
-      for (int q = tid; q < IH * IW * PPP; q += 256) {
-        const int pos = q >> PSH, part = q & (PPP - 1);
-        const int py = pos / IW, px = pos - py * IW;
-        const int iy = oy0 - PAD + py, ix = ox0 - PAD + px;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (iy >= 0 && iy < a.Hin && ix >= 0 && ix < a.Win)
-          v = load_in_piece<unsigned short, true>(a, b, iy, ix, (cbase + chunk) * KC + part * 8);
-        *reinterpret_cast<uint4*>(in_tile + py * IROWB + px * POSB + part * 16) = v;
-      }
-    } else {
 #pragma unroll
-      for (int i = 0; i < IPT; ++i) {
-        const int q = tid + i * 256;
-        uint4 v = make_uint4(0, 0, 0, 0);
-        if (q < IH * IW * PPP) {
-          const int pos = q >> PSH, part = q & (PPP - 1);
-          const int py = pos / IW, px = pos - py * IW;
-          int iy = oy0 - PAD + py, ix = ox0 - PAD + px, cc = cbase + chunk;
-          if (MODE == 2) {  // (iy, ix) are phase-plane coordinates; chunk -> (phase, channel block)
-            const int nblk = a.Cx / KC;
-            const int ph = cc / nblk;
-            cc = cc - ph * nblk;
-            iy = 2 * iy + (ph >> 1);
-            ix = 2 * ix + (ph & 1);
-          }
-          if (iy >= 0 && iy < a.Hin && ix >= 0 && ix < a.Win)
-            v = load_in_piece<unsigned short, false>(a, b, iy, ix, cc * KC + part * 8);
-          if (to_lds) *reinterpret_cast<uint4*>(in_tile + py * IROWB + px * POSB + part * 16) = v;
+    for (int i = 0; i < IPT; ++i) {
+      const int q = tid + i * 256;
+      uint4 v = make_uint4(0, 0, 0, 0);
+      if (q < IH * IW * PPP) {
+        const auto [py, px, part] = patch_piece<C>(q);
+        int iy = oy0 - PAD + py, ix = ox0 - PAD + px, cc = cbase + chunk;
+        if (MODE == 2) {  // (iy, ix) are phase-plane coordinates; chunk -> (phase, channel block)
+          const int nblk = a.Cx / KC;
+          const int ph = cc / nblk;
+          cc = cc - ph * nblk;
+          iy = 2 * iy + (ph >> 1);
+          ix = 2 * ix + (ph & 1);
         }
-        if (!to_lds) ireg[i] = v;
+        if (iy >= 0 && iy < a.Hin && ix >= 0 && ix < a.Win)
+          v = load_in_piece<unsigned short, false>(a, b, iy, ix, cc * KC + part * 8);
+        if (to_lds) *reinterpret_cast<uint4*>(in_tile + py * IROWB + px * POSB + part * 16) = v;
       }
+      if (!to_lds) ireg[i] = v;
     }
   };
   auto store_in = [&]() {
@@ -590,22 +713,10 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
     for (int i = 0; i < IPT; ++i) {
       const int q = tid + i * 256;
       if (q < IH * IW * PPP) {
-        const int pos = q >> PSH, part = q & (PPP - 1);
-        const int py = pos / IW, px = pos - py * IW;
+        const auto [py, px, part] = patch_piece<C>(q);
         *reinterpret_cast<uint4*>(in_tile + py * IROWB + px * POSB + part * 16) = ireg[i];
       }
     }
-  };
-
-  // one 1-KiB LDS-DMA block of the slab of `step` (block index i of this wave)
-  auto issue_w1 = [&](int st, int chunk, int slot, int i) {  // st = step inside the chunk
-    const int blk = i * NWV + dwave;
-    const int tap = st * TPS + (TPS == 1 ? 0 : blk / BPT), rblk = TPS == 1 ? blk : blk % BPT;
-    const int row = KC == 64 ? rblk * 8 + (lane >> 3) : rblk * 16 + (lane >> 2);
-    const int part = KC == 64 ? (lane & 7) ^ ((row >> 1) & 7) : (lane & 3) ^ ((row >> 2) & 3);
-    const int co = min(n0 + row, a.Cout - 1);
-    lss_glds16(wg + ((size_t)tap * a.Cout + co) * a.Cin + (cbase + chunk) * KC + part * 8,
-           w_tile + slot * W_BYTES + blk * 1024);
   };
 
   // per-lane epilogue constants, fetched now so their latency is long gone by the epilogue
@@ -618,17 +729,8 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
     esh[ct] = (cok && a.shift) ? a.shift[co] : 0.f;
   }
 
-  // Output pieces of this thread (used by the epilogue; computed here because the residual rows of the launch-bound
-  // layers are requested from inside the main loop, see EARLY_RES).  A piece = 8 consecutive channels (16 B of bf16) of
-  // one pixel; 256 threads cover PPJ pixels x CG channel groups per pass, so a thread's pixel column, channel group and
-  // first row never change: every per-pass address is one base + a compile-time offset.
-  constexpr int CG = BN / 8;              // 16-B channel groups per pixel
-  constexpr int PPJ = 256 / CG;           // pixels per pass
-  constexpr int RPJ = PPJ / 16;           // image rows per pass
-  constexpr int HROWS = TH / EPH;         // image rows per staged half (EPH = 2: KC = 32, see OUT_BYTES)
-  constexpr int HPIECES = HROWS * 16 * CG;
-  constexpr int EPJ = HPIECES / 256;      // passes per half
-  static_assert(HPIECES % 256 == 0 && PPJ % 16 == 0, "half tiles split evenly over the threads");
+  // Output pieces of this thread (TileCfg::CG), used by the epilogue; computed here because the residual rows of the
+  // launch-bound layers are requested from inside the main loop, see EARLY_RES.
   const int pix0 = tid / CG, c8 = tid % CG;
   const int ox = ox0 + (pix0 & 15), oyb = oy0 + (pix0 >> 4);
   const int co = n0 + c8 * 8;
@@ -637,11 +739,6 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
   const int rstep = a.Wo * a.Cout;                            // residual elements per image row
   const unsigned short* res = reinterpret_cast<const unsigned short*>(a.residual);
   const bool res_vec = !HEAD && res != nullptr && col_ok && (a.Cout & 7) == 0 && co + 8 <= a.Cout;
-  // EARLY_RES: the residual rows of the launch-bound layers (RT = 1: 152-190 registers, room for 16 more) are
-  // requested at the top of the LAST chunk's taps instead of at the top of the epilogue: phase stamps put the store
-  // phase of the residual layers at 1.6-1.7 us against 1.0-1.1 us for the same tile without a residual - the loads,
-  // issued ~0.6 us before their first use, were still in flight when the store loop wanted them.
-  constexpr bool EARLY_RES = RT == 1 && EPH == 1 && !HEAD;
   uint4 rres[HEAD ? 1 : EPJ];
   auto load_residual = [&](int half) {
     if (!HEAD) {
@@ -677,7 +774,6 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
   // are already in flight (32 fragment VGPRs in total), and one DMA block of the slab
   // two steps ahead is issued per k-step, so LDS latency and DMA issue hide behind
   // MFMAs.
-  constexpr int PF_ST = NS >= 5 ? NS - 4 : 0;  // the step at which the next patch's loads are issued
   bf16x8 fa[2][RT], fb[2][2];  // [k-step parity][tile]
   auto read_a = [&](int buf, int tap, int s4) {
     const int toff = (tap / KW) * IROWB + (tap % KW) * POSB + s4 * 16;
@@ -736,7 +832,6 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
       // DMA (and patch loads) issued during THIS step may stay in flight
       // (younger than W(step+1): the slabs of steps step+2 .. step+LA, and - in steps 0 .. LA-1 of a chunk - the source
       // copies issued in its step 0: one per wave, two for the waves that carry the pieces past the fourth)
-      constexpr int WYOUNG = (LA - 1) * WPT;
       if (prefetch) lss_wait_vmcnt<WYOUNG + IPT>();
       else if (SRC && st < LA && srcq && more) {
         if (SRC_DMA == 2 && wave + 4 < SRC_PIECES) lss_wait_vmcnt<WYOUNG + 2>();
@@ -761,30 +856,25 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
   if (KSP == 2) {
     // split-K: the second group's partial sums meet the first group's through LDS (same lane ->
     // same element in both groups, so only the group hand-over needs barriers)
-    if (grp == 1) {
+    auto part_at = [&](int ct, int rt, int i) -> float& {  // where accumulator (ct, rt, i) of this lane meets its twin
+      const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
+      return otile[((prow0 + 2 * rt + (row >> 4)) * 16 + (row & 15)) * OLD + wc * 64 + ct * 32 + r];
+    };
 #pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
+    for (int g = 1; g >= 0; --g) {  // group 1 writes, then group 0 adds
+      if (grp == g) {
 #pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
+        for (int ct = 0; ct < 2; ++ct)
 #pragma unroll
-          for (int i = 0; i < 16; ++i) {
-            const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
-            otile[((prow0 + 2 * rt + (row >> 4)) * 16 + (row & 15)) * OLD + wc * 64 + ct * 32 + r] = acc[rt][ct][i];
-          }
+          for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+              if (g == 1) part_at(ct, rt, i) = acc[rt][ct][i];
+              else acc[rt][ct][i] += part_at(ct, rt, i);
+            }
+      }
+      lss_lds_barrier();  // g == 0: the partials are consumed before group 0 restages the tile below
     }
-    lss_lds_barrier();
-    if (grp == 0) {
-#pragma unroll
-      for (int ct = 0; ct < 2; ++ct)
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-          for (int i = 0; i < 16; ++i) {
-            const int row = (i & 3) + 8 * (i >> 2) + 4 * h;
-            acc[rt][ct][i] += otile[((prow0 + 2 * rt + (row >> 4)) * 16 + (row & 15)) * OLD + wc * 64 + ct * 32 + r];
-          }
-    }
-    lss_lds_barrier();  // the partials are consumed before group 0 restages the tile below
   }
   // (the epilogue of the launch-bound layers is instruction-issue time, not bandwidth)
   // dual-output launches: this workgroup's channel block belongs to y (columns [0, split)) or y2
@@ -839,12 +929,7 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
                 s2 += raw * raw;
               }
             }
-          s1 += __shfl_xor(s1, 32, 64);
-          s2 += __shfl_xor(s2, 32, 64);
-          if (h == 0 && cok) {
-            atomicAdd(a.stats + cs, s1);
-            atomicAdd(a.stats + a.Cout + cs, s2);
-          }
+          bn_stats_add(a.stats, a.Cout, cs, h, cok, s1, s2);
         }
       }
     }
@@ -853,97 +938,9 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
     if (grp != 0) {
       // second K-split group: its sums were handed over above; it only keeps the barriers company
     } else if (HEAD && a.head_n <= 16) {
-      // Fused 1x1 head ON THE MATRIX PIPE (ref src/modules.py:115, up2[4]): per image row of the staged tile one
-      // 16 x 16 x BN product  out[pixel][k] = sum_c relu(act[pixel][c]) * head_w[k][c]  on v_mfma_f32_16x16x32_bf16.
-      // Both operands are split into bf16 hi + lo parts (x = hi + lo to 16 significant bits) and the three
-      // products hi*hi, hi*lo, lo*hi are accumulated in fp32, so the result keeps the accuracy of the fp32
-      // head it replaces (the dropped lo*lo term is 2^-16 relative) while the VALU work per pixel falls from
-      // ~60 FMA / DPP instructions to ~12 conversions.  A: lane (r = pixel, q) <- 8 consecutive channels of the
-      // fp32 tile in LDS (2 ds_read_b128); B: lane (k = lane & 15, q) <- 8 consecutive weights of class k from
-      // global (L1-resident: 2 KiB); D: lane (k, q) holds pixels 4q..4q+3 of the row = ONE 16-B NCHW store.
-      const int hr = lane & 15, hq = lane >> 4;
-      for (int row = wave; row < HROWS; row += 4) {
-        const int oy = oy0 + half * HROWS + row;
-        f32x4 hacc = {0.f, 0.f, 0.f, 0.f};
-        const float* arow = otile + (row * 16 + hr) * OLD + hq * 8;
-        const float* wrow = a.head_w + (size_t)min(hr, a.head_n - 1) * BN + hq * 8;
-        // rolled: one k-step's 16 operand floats live at a time (the other half-tile's waves still hold their
-        // 64 accumulator registers here, and the 168-register budget of three workgroups per CU is what counts)
-#pragma unroll 1
-        for (int s = 0; s < BN / 32; ++s) {
-          bf16x8 xh, xl, wh, wl;
-          {
-            f32x4 w0 = *reinterpret_cast<const f32x4*>(wrow + s * 32);
-            f32x4 w1 = *reinterpret_cast<const f32x4*>(wrow + s * 32 + 4);
-            if (hr >= a.head_n) { w0 = (f32x4){0.f, 0.f, 0.f, 0.f}; w1 = w0; }
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-              const float wv = j < 4 ? w0[j & 3] : w1[j & 3];
-              const unsigned short whi = lss_f2bf(wv);
-              wh[j] = (short)whi;
-              wl[j] = (short)lss_f2bf(wv - lss_bf2f(whi));
-            }
-          }
-          {
-            const f32x4 x0 = *reinterpret_cast<const f32x4*>(arow + s * 32);
-            const f32x4 x1 = *reinterpret_cast<const f32x4*>(arow + s * 32 + 4);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-              float xv = j < 4 ? x0[j & 3] : x1[j & 3];
-              if (a.relu) xv = fmaxf(xv, 0.f);
-              const unsigned short xhi = lss_f2bf(xv);
-              xh[j] = (short)xhi;
-              xl[j] = (short)lss_f2bf(xv - lss_bf2f(xhi));
-            }
-          }
-          hacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xl, wh, hacc, 0, 0, 0);
-          hacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh, wl, hacc, 0, 0, 0);
-          hacc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xh, wh, hacc, 0, 0, 0);
-        }
-        if (hr < a.head_n && oy < a.Ho) {
-          const float hb = a.head_b[hr];
-          float* op = a.head_out + (((size_t)b * a.head_n + hr) * a.Ho + oy) * a.Wo + ox0 + hq * 4;
-          if ((a.Wo & 3) == 0 && ox0 + hq * 4 + 4 <= a.Wo) {
-            *reinterpret_cast<f32x4*>(op) = (f32x4){hacc[0] + hb, hacc[1] + hb, hacc[2] + hb, hacc[3] + hb};
-          } else {
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-              if (ox0 + hq * 4 + i < a.Wo) op[i] = hacc[i] + hb;
-          }
-        }
-      }
+      head_mfma<C>(a, otile, b, oy0 + half * HROWS, ox0, lane, wave);
     } else if (HEAD) {
-      // fused 1x1 head, VALU form (more than 16 classes): the CG = BN / 8 lanes
-      // that hold the channels of one pixel reduce their partial dot products with DPP row operations; the
-      // activation itself is never stored
-      {
-        for (int e = tid; e < HROWS * 16 * CG; e += 256) {
-          const int pl = e / CG, hc8 = e % CG;
-          const int oy = oy0 + half * HROWS + (pl >> 4), hx = ox0 + (pl & 15);
-          const f32x4 v0 = *reinterpret_cast<const f32x4*>(otile + pl * OLD + hc8 * 8);
-          const f32x4 v1 = *reinterpret_cast<const f32x4*>(otile + pl * OLD + hc8 * 8 + 4);
-          float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-          if (a.relu) {
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = fmaxf(v[k], 0.f);
-          }
-          for (int k = 0; k < a.head_n; ++k) {
-            const float* hw = a.head_w + k * BN + hc8 * 8;
-            float part = 0.f;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) part = fmaf(v[j], hw[j], part);
-            // sum over the CG lanes of the pixel on DPP row operations (no LDS round trips): lane ^ 1,
-            // lane ^ 2, then - every quad now holding its sum - the other quad of the 8 (row_half_mirror)
-            // and the other half of the 16 (row_mirror)
-            part += lss_dpp_f32<0xB1>(part);
-            part += lss_dpp_f32<0x4E>(part);
-            part += lss_dpp_f32<0x141>(part);
-            if (CG == 16) part += lss_dpp_f32<0x140>(part);
-            if (hc8 == 0 && oy < a.Ho && hx < a.Wo)
-              a.head_out[(((size_t)b * a.head_n + k) * a.Ho + oy) * a.Wo + hx] = part + a.head_b[k];
-          }
-        }
-      }
+      head_valu<C>(a, otile, b, oy0 + half * HROWS, ox0, tid);
     } else if (col_ok) {
       const float* const ord = otile + pix0 * OLD + c8 * 8;
 #pragma unroll
@@ -1016,8 +1013,8 @@ __device__ __forceinline__ void conv_lds_tile(const ConvArgs& a, int tilesX, int
 template <int RT, int BN, int MODE, int KH, int KW, int PAD, int KC = 64, int KSP = 1, bool HEAD = false, int TPS = 1>
 __global__ __launch_bounds__(256 * KSP, KSP == 2 ? 1 : (KC == 32 ? 3 : 2)) void conv_lds_kernel(ConvArgs a, int tilesX,
                                                                                                   int tilesY) {
-  __shared__ __attribute__((aligned(1024))) unsigned char smem[conv_lds_smem_bytes<RT, BN, MODE, KH, KW, KC, KSP, TPS>()];
-  conv_lds_tile<RT, BN, MODE, KH, KW, PAD, KC, KSP, HEAD, TPS>(a, tilesX, tilesY, blockIdx.x, gridDim.x, blockIdx.y, 0, smem);
+  __shared__ __attribute__((aligned(1024))) unsigned char smem[TileCfg<RT, BN, MODE, KH, KW, PAD, KC, KSP, HEAD, TPS>::SMEM_BYTES];
+  conv_lds_tile<RT, BN, MODE, KH, KW, PAD, KC, KSP, HEAD, TPS>(a, tilesX, tilesY, smem);
 }
 
 // OIHW fp32 -> [tap][co][ci] in T
@@ -1069,68 +1066,79 @@ inline int conv_src_lds_ok(const ConvArgs& a) {
   return a.up >= 2 && a.ry * 9.f < 4.99f && a.rx * 17.f < 8.99f;
 }
 
-// Tile selection + launch of conv_lds_kernel.  BN = 64 for narrow layers, else 128; RT = 2
-// (throughput shape) unless that grid would leave the 256 CUs under-filled, in which case
-// half-height workgroups (RT = 1) shorten the per-workgroup critical path instead.
-template <int MODE, int KH, int KW, int PAD>
-void launch_conv_lds(const ConvArgs& a, hipStream_t st) {
-  const int tilesX = lss_cdiv(a.Wo, 16);
+// Which conv_lds_kernel a conv takes and on what grid: decided here for launch_conv_lds and for the fused head (whose
+// tile is always RT = 2).  BN = 64 for narrow layers, else 128; RT = 2 (throughput shape) unless that grid would leave
+// the 256 CUs under-filled, in which case half-height workgroups (RT = 1) shorten the per-workgroup critical path
+// instead.  Every switch is read on every call.
+struct TilePlan {
+  int rt, kc, ksp, tps, src_lds;
+  int tilesX, tilesY;
+  dim3 grid;
+};
+TilePlan conv_tile_plan(const ConvArgs& a, int MODE, int KH, bool head) {
+  TilePlan p = {2, 64, 1, 1, 0};
   const bool narrow = a.Cout <= 64;
   const int th2 = narrow ? 16 : 8;
   const int nblk = lss_cdiv(a.Cout, narrow ? 64 : 128);
-  const long long nwg2 = (long long)tilesX * lss_cdiv(a.Ho, th2) * a.B * nblk;
-  int rt = nwg2 < 384 ? 1 : 2;
-  if (const char* e = getenv("LSS_CONV_RT")) rt = atoi(e) == 1 ? 1 : 2;
-  const int th = rt == 2 ? th2 : th2 / 2;
-  const int tilesY = lss_cdiv(a.Ho, th);
-  dim3 g(tilesX * tilesY * a.B, nblk);
-  if (narrow) {
-    if (rt == 2) hipLaunchKernelGGL((conv_lds_kernel<2, 64, MODE, KH, KW, PAD>), g, dim3(256), 0, st, a, tilesX, tilesY);
-    else {
-      if constexpr (MODE == 2 && KH == 4) {
-        // the 7x7 / 2 stem: two taps per step (LSS_CONV_TPS=1 = one, for A/B)
-        static const bool tps2 = getenv("LSS_CONV_TPS") == nullptr || atoi(getenv("LSS_CONV_TPS")) != 1;
-        if (tps2) {
-          hipLaunchKernelGGL((conv_lds_kernel<1, 64, MODE, KH, KW, PAD, 64, 1, false, 2>), g, dim3(256), 0, st, a, tilesX,
-                             tilesY);
-          return;
-        }
-      }
-      hipLaunchKernelGGL((conv_lds_kernel<1, 64, MODE, KH, KW, PAD>), g, dim3(256), 0, st, a, tilesX, tilesY);
-    }
-  } else {
-    // Half-depth steps, three workgroups per CU.  Measured (same box, B = 4): the fused
-    // upsample/concat convs gain (up1.conv0 100 -> 83 us, up2.1 141 -> 133 us: the third workgroup
-    // fills the synchronous gather phases), the plain 3x3 loses 5 % (half-depth steps double the
-    // barriers per MFMA) - so MODE 1 takes KC = 32 by default, MODE 0 keeps 64 (LSS_CONV_KC overrides).
-    bool kc32 = MODE == 1;
-    if (const char* e = getenv("LSS_CONV_KC")) kc32 = atoi(e) == 32;
-    kc32 = kc32 && MODE != 2 && KH == 3 && rt == 2 && a.Cx % 32 == 0 && a.C2 % 32 == 0;
-    if (rt == 2) {
-      if constexpr (MODE != 2 && KH == 3) {
-        if (kc32) {
-          ConvArgs a32 = a;
-          a32.src_lds = MODE == 1 ? conv_src_lds_ok(a) : 0;
-          hipLaunchKernelGGL((conv_lds_kernel<2, 128, MODE, KH, KW, PAD, 32>), g, dim3(256), 0, st, a32, tilesX, tilesY);
-          return;
-        }
-      }
-      hipLaunchKernelGGL((conv_lds_kernel<2, 128, MODE, KH, KW, PAD>), g, dim3(256), 0, st, a, tilesX, tilesY);
-    } else {
-      // Grids that cannot even give every CU one workgroup (layer2 / layer3 at batch 4): split the
-      // K loop over two 4-wave groups inside the workgroup - half the latency-bound steps each.
-      const long long nwg1 = (long long)g.x * g.y;
-      bool ksplit = MODE != 1 && nwg1 <= 256 && (a.Cin / 64) % 2 == 0 && a.Cin >= 128;
-      ksplit = ksplit && lss_env_on("LSS_CONV_KSPLIT");
-      if constexpr (MODE != 1) {
-        if (ksplit) {
-          hipLaunchKernelGGL((conv_lds_kernel<1, 128, MODE, KH, KW, PAD, 64, 2>), g, dim3(512), 0, st, a, tilesX, tilesY);
-          return;
-        }
-      }
-      hipLaunchKernelGGL((conv_lds_kernel<1, 128, MODE, KH, KW, PAD>), g, dim3(256), 0, st, a, tilesX, tilesY);
-    }
+  p.tilesX = lss_cdiv(a.Wo, 16);
+  if (!head) {
+    const long long nwg2 = (long long)p.tilesX * lss_cdiv(a.Ho, th2) * a.B * nblk;
+    p.rt = nwg2 < 384 ? 1 : 2;
+    if (const char* e = getenv("LSS_CONV_RT")) p.rt = atoi(e) == 1 ? 1 : 2;
   }
+  p.tilesY = lss_cdiv(a.Ho, p.rt == 2 ? th2 : th2 / 2);
+  p.grid = dim3(p.tilesX * p.tilesY * a.B, nblk);
+  if (narrow) {
+    if (p.rt == 1 && MODE == 2 && KH == 4) p.tps = 2;  // the 7x7 / 2 stem: two taps per step
+    return p;
+  }
+  // Half-depth steps, three workgroups per CU.  Measured (same box, B = 4): the fused
+  // upsample/concat convs gain (up1.conv0 100 -> 83 us, up2.1 141 -> 133 us: the third workgroup
+  // fills the synchronous gather phases), the plain 3x3 loses 5 % (half-depth steps double the
+  // barriers per MFMA) - so MODE 1 takes KC = 32 by default, MODE 0 keeps 64.  LSS_CONV_KC overrides; the head has
+  // no plain KC = 32 form, so there the switch can only take KC = 32 away.
+  bool kc32 = MODE == 1;
+  if (const char* e = getenv("LSS_CONV_KC")) kc32 = (kc32 || !head) && atoi(e) == 32;
+  if (kc32 && MODE != 2 && KH == 3 && p.rt == 2 && a.Cx % 32 == 0 && a.C2 % 32 == 0) {
+    p.kc = 32;
+    p.src_lds = MODE == 1 ? conv_src_lds_ok(a) : 0;
+  } else if (p.rt == 1) {
+    // Grids that cannot even give every CU one workgroup (layer2 / layer3 at batch 4): split the
+    // K loop over two 4-wave groups inside the workgroup - half the latency-bound steps each.
+    const long long nwg1 = (long long)p.grid.x * p.grid.y;
+    const bool ksplit = MODE != 1 && nwg1 <= 256 && (a.Cin / 64) % 2 == 0 && a.Cin >= 128;
+    if (ksplit && lss_env_on("LSS_CONV_KSPLIT")) p.ksp = 2;
+  }
+  return p;
+}
+
+template <int RT, int BN, int MODE, int KH, int KW, int PAD, int KC = 64, int KSP = 1, bool HEAD = false, int TPS = 1>
+void launch_tile(ConvArgs a, const TilePlan& p, hipStream_t st) {
+  a.src_lds = p.src_lds;
+  hipLaunchKernelGGL((conv_lds_kernel<RT, BN, MODE, KH, KW, PAD, KC, KSP, HEAD, TPS>), p.grid, dim3(256 * KSP), 0, st, a,
+                     p.tilesX, p.tilesY);
+}
+
+// the plan's instantiation, among those this (MODE, taps) has
+template <int MODE, int KH, int KW, int PAD>
+void launch_conv_lds(const ConvArgs& a, hipStream_t st) {
+  const TilePlan p = conv_tile_plan(a, MODE, KH, false);
+  if (a.Cout <= 64) {
+    if constexpr (MODE == 2 && KH == 4) {
+      if (p.tps == 2) return launch_tile<1, 64, MODE, KH, KW, PAD, 64, 1, false, 2>(a, p, st);
+    } else if (p.rt == 1) {
+      return launch_tile<1, 64, MODE, KH, KW, PAD>(a, p, st);
+    }
+    return launch_tile<2, 64, MODE, KH, KW, PAD>(a, p, st);
+  }
+  if constexpr (MODE != 2 && KH == 3) {
+    if (p.kc == 32) return launch_tile<2, 128, MODE, KH, KW, PAD, 32>(a, p, st);
+  }
+  if constexpr (MODE != 1) {
+    if (p.ksp == 2) return launch_tile<1, 128, MODE, KH, KW, PAD, 64, 2>(a, p, st);
+  }
+  if (p.rt == 2) launch_tile<2, 128, MODE, KH, KW, PAD>(a, p, st);
+  else launch_tile<1, 128, MODE, KH, KW, PAD>(a, p, st);
 }
 
 // LSS_CONV_WT=0: write-back epilogue stores.  Read on every call, like every switch here: tests flip them in-process
@@ -1367,22 +1375,13 @@ extern "C" int lss_conv2d_head_fwd(const void* x, const void* x2, const void* w_
   ConvArgs& a = f.a;
   a.head_w = head_w; a.head_b = head_b; a.head_out = out; a.head_n = head_n;
   const bool fused = (up > 1) || (C2 > 0);
-  const int tilesX = lss_cdiv(a.Wo, 16), tilesY = lss_cdiv(a.Ho, Cout == 64 ? 16 : 8);
-  dim3 g(tilesX * tilesY * B, 1);
   hipStream_t st = lss_stream(stream);
   // the fused-gather form takes the 32-channel steps (three workgroups per CU), as in launch_conv_lds
-  bool kc32 = fused && a.Cx % 32 == 0 && a.C2 % 32 == 0;
-  if (const char* e = getenv("LSS_CONV_KC")) kc32 = kc32 && atoi(e) == 32;
-  if (fused && kc32) {
-    a.src_lds = conv_src_lds_ok(a);
-    hipLaunchKernelGGL((conv_lds_kernel<2, 128, 1, 3, 3, 1, 32, 1, true>), g, dim3(256), 0, st, a, tilesX, tilesY);
-  }
-  else if (fused)
-    hipLaunchKernelGGL((conv_lds_kernel<2, 128, 1, 3, 3, 1, 64, 1, true>), g, dim3(256), 0, st, a, tilesX, tilesY);
-  else if (Cout == 64)
-    hipLaunchKernelGGL((conv_lds_kernel<2, 64, 0, 3, 3, 1, 64, 1, true>), g, dim3(256), 0, st, a, tilesX, tilesY);
-  else
-    hipLaunchKernelGGL((conv_lds_kernel<2, 128, 0, 3, 3, 1, 64, 1, true>), g, dim3(256), 0, st, a, tilesX, tilesY);
+  const TilePlan p = conv_tile_plan(a, fused ? 1 : 0, 3, true);
+  if (p.kc == 32) launch_tile<2, 128, 1, 3, 3, 1, 32, 1, true>(a, p, st);
+  else if (fused) launch_tile<2, 128, 1, 3, 3, 1, 64, 1, true>(a, p, st);
+  else if (Cout == 64) launch_tile<2, 64, 0, 3, 3, 1, 64, 1, true>(a, p, st);
+  else launch_tile<2, 128, 0, 3, 3, 1, 64, 1, true>(a, p, st);
   return lss_launch_status();
 }
 

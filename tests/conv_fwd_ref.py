@@ -31,7 +31,7 @@ BOUND cases (`kind == "bound"`): bf16-valued randn operands, scale in [0.5, 1.5]
                 without a residual):  E_pre = |scale| E_acc + 2 u (|scale| (|acc| + E_acc) + |shift|),
                 E_t = E_pre + u (|pre| + E_pre + |residual|); ReLU is 1-Lipschitz.  bf16 output: the exact half ulp
                 (`bf16_out_bound`).
-  head          tile kernel (conv_mfma.hip:855-913): the fp32 activation is NOT rounded to bf16; activation and head
+  head          tile kernel (conv_mfma.hip: head_mfma): the fp32 activation is NOT rounded to bf16; activation and head
                 weight are each split x = hi + lo (+ e_x), |lo| <= 2^-8 |x|, |e_x| <= 2^-8 |lo| <= 2^-16 |x|, and
                 hi hi + hi lo + lo hi is accumulated in fp32: the dropped lo lo and the two e terms are at most
                 3 * 2^-16 (1 + 2^-7) |x w| per product; 3 Cout products + bias:
@@ -75,9 +75,9 @@ inequality.
 Which kernel a case reaches.  `tile_inst` / `ring_inst` repeat the dispatch of launch_conv_lds, lss_conv2d_fwd,
 lss_conv2d_head_fwd, conv2d_s2_impl, lss_conv2d_ring_ok and lss_conv_ring_launch (workgroup counts, the T22 condition)
 and `make_inputs` asserts that the result is the instantiation named in the case table, so a case cannot drift onto
-another kernel silently.  The switches of a case (`env`) are read by the library on every call; LSS_CONV_TPS is read
-once per process (`static const`), so only its default is reachable: the one-tap stem form lds<1,64,2,4,64,1,0,1> is
-the one instantiation no case runs.
+another kernel silently.  The switches of a case (`env`) are read by the library on every call.  The narrow RT = 1
+7x7 / 2 stem always takes two taps per step: its one-tap form lds<1,64,2,4,64,1,0,1> is not built, so no case may name
+it.
 Instantiation names: lds<RT,BN,MODE,KH,KC,KSP,HEAD,TPS>[+src] = conv_lds_kernel<RT, BN, MODE, KH, KH, PAD, KC, KSP,
 HEAD, TPS> (+src: the low-res source window staged in LDS); direct<bf16|f32,fused|plain> = conv_direct_kernel;
 ring<MODE,HEAD,NSL,T22> = conv_ring_kernel.
@@ -174,6 +174,9 @@ CASES = [
     _c("h_c64_n1", "tile", "lds<2,64,0,3,64,1,1,1>", "head", E, 2, 19, 21, 64, 64, head_n=1, relu=True),
     # Wo % 4 == 0: 16-B stores
     _c("h_c128_n4", "tile", "lds<2,128,0,3,64,1,1,1>", "head", E, 1, 13, 36, 64, 128, head_n=4, relu=True),
+    # more than 16 classes: the VALU head (head_valu); Cout 64 = 8 lanes per pixel, the reduction without its last step
+    _c("h_c128_n17", "tile", "lds<2,128,0,3,64,1,1,1>", "head", E, 1, 9, 17, 64, 128, head_n=17, relu=True),
+    _c("h_c64_n20", "tile", "lds<2,64,0,3,64,1,1,1>", "head", E, 1, 9, 17, 64, 64, head_n=20, relu=True),
     # (a head splits its fp32 activation into 8 + 8 bits: integers below 2^16, so the fused head cases use
     # construction (b))
     _c("h_fused_kc32_n4", "tile", "lds<2,128,1,3,32,1,1,1>+src", "head", E, 1, 11, 11, 64, 128, C2=64, up=3, head_n=4,
@@ -454,7 +457,7 @@ def _axis64(n_in, n_out):
 
 
 def _axis32(n_in, n_out):
-    """The kernels' float32 coordinates and 16-bit fractions (conv_mfma.hip:486-490, conv_ring.hip:336-341)."""
+    """The kernels' float32 coordinates and 16-bit fractions (conv_mfma.hip: the g_w set-up of conv_lds_tile, conv_ring.hip:336-341)."""
     r = _ratio32(n_in, n_out)
     s = (r * np.arange(n_out).astype(np.float32)).astype(np.float32)
     i0 = s.astype(np.int64)
@@ -511,7 +514,7 @@ def _fma32(a, b, c):
 
 def blend_f32(x, up):
     """The kernels' blend of bf16-valued x (B,H,W,C), operation by operation in float32 (conv_ring.hip:113-135 =
-    conv_mfma.hip:97-115): 16-bit fractions, the four-weight form, a product and three FMAs.  NOT rounded to bf16."""
+    conv_mfma.hip: blend_bf16x8): 16-bit fractions, the four-weight form, a product and three FMAs.  NOT rounded to bf16."""
     B, H, W, C = x.shape
     y0, y1, ly = _axis32(H, H * up)
     x0, x1, lx = _axis32(W, W * up)

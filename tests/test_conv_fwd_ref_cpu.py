@@ -25,7 +25,7 @@ def test_case_table_reaches_what_it_names():
                  "lds<1,128,2,1,64,1,0,1>", "lds<1,64,2,2,64,1,0,1>", "lds<1,128,2,2,64,2,0,1>", "lds<2,128,2,2,64,1,0,1>",
                  "lds<1,64,2,4,64,1,0,2>", "lds<2,64,2,4,64,1,0,1>"):
         assert inst in exact, inst
-    assert "lds<1,64,2,4,64,1,0,1>" not in {c.inst for c in R.CASES}   # behind LSS_CONV_TPS, read once per process
+    assert "lds<1,64,2,4,64,1,0,1>" not in {c.inst for c in R.CASES}   # the one-tap stem form: not built
     # the image sizes of the tile cases are no multiples of the 16-wide, 8- or 16-high tiles
     for c in R.CASES:
         Ho, Wo = R.out_hw(c)
