@@ -931,6 +931,66 @@ int lss_tapconv_fwd(const lss_tapconv_desc_t* desc, void* stream);
 int lss_camera_pool_bias_fwd(const float* mean, const float* wg, const float* scale, const float* shift,
                              const float* wj, int BN, int C, int Cg, int Cout, float* g, float* bias, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * K14  the six-token tail of the vovnet model at inference (csrc/camera_tail.hip).
+ * replaces: src/model_vovnet_transformer.py:217-352, 621-637 (LightweightCameraTransformer, BEVCameraFusion,
+ *           UnifiedPredictor and the lines of `forward` that pool the BEV map and call them), in eval mode without
+ *           autograd.  fp32 arithmetic throughout, no atomics, no waiting between workgroups, fixed summation order:
+ *           bit-reproducible, and a sample's result does not depend on the batch it is in.
+ *
+ * lss_bev_pool_fwd: column sums of an NHWC map.  map (B, R, C = 256) bf16 (dt 1) or fp32 (dt 0), contiguous, R = H W;
+ *   partials (B, parts, 256) fp32: part p holds the sums over the contiguous rows [p R / parts, (p + 1) R / parts)
+ *   (zeros for an empty range).  16-byte loads, several rows in flight per thread, the row groups of a workgroup added
+ *   through LDS in a fixed order; the fp32 copy of the map is never made.  The mean is (sum over the parts) / R, which
+ *   lss_camera_tail_fwd takes in a fixed order.
+ *   lss_bev_pool_parts(B, R): the default number of parts - 1 when R < 128, R / 64 up to 256 (enough workgroups to
+ *   fill the chip at B = 1, few enough for the tail's sum); a function of R alone, so that a sample's sums do not
+ *   depend on B.  LSS_E_SHAPE for B outside 1..65535 or R outside 1..2^32.
+ *   Argument checks, all before any HIP call: LSS_E_NULL (map, partials), LSS_E_SHAPE (B, R as above, C != 256, parts
+ *   outside 1..256), LSS_E_LAYOUT (dt), LSS_E_ALIGN (16 B for map, 4 B for partials).
+ *
+ * lss_camera_tail_fwd: one workgroup per sample, one launch; every parameter is read in place from fp32 row-major
+ *   [out][in] tensors (the modules' own), tokens and activations stay in LDS.
+ *     1  x  = tokens + cam_embed[ids]                      tokens (B, N, 256); ids (B, N) int64 or NULL (= 0 .. N-1),
+ *                                                          clamped to 0 .. n_embed-1
+ *     2  x1 = LN1(x + out_proj(attention(in_proj x)))      sa_in_w (768, 256), 4 heads of 64, scale 1/8, softmax with
+ *                                                          the maximum subtracted over the N keys
+ *     3  x2 = LN2(x1 + W2 gelu(W1 x1 + b1) + b2)           ffn1_w (512, 256), ffn2_w (256, 512), erf GELU
+ *     4  x3 = LN3(x2 + c),  c = Wo (Wv bev + bv) + bo      cross-attention over ONE key: its softmax is exactly 1, so
+ *                                                          the attention output is the value row for every query and
+ *                                                          head; Wv = rows 512..767 of ca_in_w (768, 256), the q and k
+ *                                                          rows are never read.  Equal to the library for finite
+ *                                                          operands; a non-finite q . k makes the library's row NaN and
+ *                                                          this one not.
+ *          bev_token = bev_scale * sum_p bev[b, p, :] over bev_parts parts in a fixed order; bev_parts = 1 and
+ *          bev_scale = 1 takes an already pooled (B, 256) token as it is.
+ *     5  z0 = sum_n softmax(cam_w)_n x3[n];  z1 = gelu(LNa(enc1 z0));  z2 = gelu(LNb(enc2 z1));
+ *        action (B, n_action) = act z2;  description (B, n_desc) = desc z2       enc1_w (512, 256), enc2_w (256, 512)
+ *   Stages 1-3 are skipped when their 13 pointers (cam_embed .. norm2_b) are all NULL, stage 4 when its 7 (ca_in_w ..
+ *   norm3_b, bev) are; a stage given in part is LSS_E_NULL.  LayerNorm: biased variance, two passes; eps_cam for LN1
+ *   and LN2, eps_fuse for LN3, eps_pred for LNa and LNb.
+ *   lss_camera_tail_ok: 1 for 1 <= B <= 65535, 1 <= N <= 8, 1 <= n_action, n_desc <= 16; else LSS_E_SHAPE.
+ *   Argument checks, all before any HIP call: LSS_E_NULL (desc, tokens, the predictor's operands, the outputs, a stage
+ *   given in part), LSS_E_SHAPE (lss_camera_tail_ok; n_embed < 1, or < N without ids; bev_parts outside 1..256),
+ *   LSS_E_ALIGN (16 B for tokens and the weight matrices, whose rows are read 16 bytes at a time; 8 B for ids; 4 B for
+ *   every other fp32 operand).  Nothing is written when a check fails. */
+typedef struct lss_camera_tail_desc {
+  const float* tokens;
+  const long long* ids;
+  const float *cam_embed, *sa_in_w, *sa_in_b, *sa_out_w, *sa_out_b, *norm1_w, *norm1_b;
+  const float *ffn1_w, *ffn1_b, *ffn2_w, *ffn2_b, *norm2_w, *norm2_b;
+  const float *ca_in_w, *ca_in_b, *ca_out_w, *ca_out_b, *norm3_w, *norm3_b, *bev;
+  const float *cam_w, *enc1_w, *enc1_b, *ln1_w, *ln1_b, *enc2_w, *enc2_b, *ln2_w, *ln2_b;
+  const float *act_w, *act_b, *desc_w, *desc_b;
+  float *action, *description;
+  float eps_cam, eps_fuse, eps_pred, bev_scale;
+  int32_t B, N, n_embed, n_action, n_desc, bev_parts;
+} lss_camera_tail_desc_t;
+int lss_camera_tail_ok(int B, int N, int n_action, int n_desc);
+int lss_bev_pool_parts(int B, long long R);
+int lss_bev_pool_fwd(const void* map, int dt, int B, long long R, int C, int parts, float* partials, void* stream);
+int lss_camera_tail_fwd(const lss_camera_tail_desc_t* desc, void* stream);
+
 /* Layout / dtype conversion helpers between the reference's NCHW fp32 tensors
  * and the conv path's NHWC tensors. */
 int lss_nchw_f32_to_nhwc(const float* src, void* dst, int B, int C, int H, int W, int dt,

@@ -137,6 +137,10 @@ SIGNATURES = {
     "lss_tapconv_ok": (_i, [_i] * 5),
     "lss_tapconv_fwd": (_i, [_vp, _vp]),
     "lss_camera_pool_bias_fwd": (_i, [_vp] * 5 + [_i] * 4 + [_vp] * 3),
+    "lss_camera_tail_ok": (_i, [_i] * 4),
+    "lss_bev_pool_parts": (_i, [_i, ctypes.c_longlong]),
+    "lss_bev_pool_fwd": (_i, [_vp, _i, _i, ctypes.c_longlong, _i, _i, _vp, _vp]),
+    "lss_camera_tail_fwd": (_i, [_vp, _vp]),
     "lss_nchw_f32_to_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lss_nhwc_to_nchw_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }
@@ -171,6 +175,19 @@ class TapconvDesc(ctypes.Structure):
     """lss_tapconv_desc_t of include/lss_hip.h."""
     _fields_ = [(n, _vp) for n in ("x", "y", "img_bias", "means")] + [("branch", TapconvBranch * 4)] + \
                [(n, ctypes.c_int32) for n in ("BN", "H", "W", "Cin", "Cout", "nbranch", "y_stride", "relu")]
+
+
+class CameraTailDesc(ctypes.Structure):
+    """lss_camera_tail_desc_t of include/lss_hip.h."""
+    CAMERA = ("cam_embed", "sa_in_w", "sa_in_b", "sa_out_w", "sa_out_b", "norm1_w", "norm1_b",
+              "ffn1_w", "ffn1_b", "ffn2_w", "ffn2_b", "norm2_w", "norm2_b")
+    FUSION = ("ca_in_w", "ca_in_b", "ca_out_w", "ca_out_b", "norm3_w", "norm3_b")
+    PREDICTOR = ("cam_w", "enc1_w", "enc1_b", "ln1_w", "ln1_b", "enc2_w", "enc2_b", "ln2_w", "ln2_b",
+                 "act_w", "act_b", "desc_w", "desc_b")
+    _fields_ = [(n, _vp) for n in ("tokens", "ids") + CAMERA + FUSION + ("bev",) + PREDICTOR
+                + ("action", "description")] + \
+               [(n, ctypes.c_float) for n in ("eps_cam", "eps_fuse", "eps_pred", "bev_scale")] + \
+               [(n, ctypes.c_int32) for n in ("B", "N", "n_embed", "n_action", "n_desc", "bev_parts")]
 
 
 _lib = None

@@ -34,6 +34,7 @@ SOURCES = {
     "transformer_pointwise.hip": ["-fno-slp-vectorize"],  # scalar row arithmetic, as the kernels were measured
     "linear_mfma.hip": [],
     "camera_branch.hip": [],
+    "camera_tail.hip": [],
     "ffn_fused.hip": [],
     "conv_grad.hip": [],
     "conv_wgrad.hip": [],

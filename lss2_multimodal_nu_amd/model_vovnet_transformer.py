@@ -19,7 +19,8 @@ the default passes such feature maps straight through.
 
 The TXT branch: c3 -> feature pyramid -> ASPP -> per-camera scene tokens is about a seventh of the step's FLOPs and
 runs at inference on K13 (csrc/camera_branch.hip, `VoVNetBEVTransformer.scene_tokens`); the six-token tail behind it
-(camera transformer, BEV fusion, predictor) is stock PyTorch.
+(camera transformer, BEV fusion, predictor) and the pooled BEV token run at inference on K14 (csrc/camera_tail.hip, two
+launches) and are stock PyTorch everywhere else.
 """
 import os
 
@@ -61,6 +62,12 @@ _DEPTH_TAIL_NATIVE_DEFAULT = "1"
 CAMERA_BRANCH_CALLS = {"native": 0, "composition": 0}
 # LSS_CAMERA_BRANCH_NATIVE unset: see DESIGN.md 4b for the measurement that decides this
 _CAMERA_BRANCH_NATIVE_DEFAULT = "1"
+# which form the six-token tail of `VoVNetBEVTransformer.forward` took on the inference branch: "native" = K14 (bev_pool +
+# camera_tail: eval, no autograd, fp32 parameters, GPU, no forward hooks), "composition" = the pooled map through
+# camera_transformer, bev_fusion and unified_predictor on library ops
+CAMERA_TAIL_CALLS = {"native": 0, "composition": 0}
+# LSS_CAMERA_TAIL_NATIVE unset: see DESIGN.md 4b for the measurement that decides this
+_CAMERA_TAIL_NATIVE_DEFAULT = "1"
 
 
 def _nhwc_bf16_rows(hidden):
@@ -567,6 +574,112 @@ class _CameraBranchPlan:
         return ops.tapconv(cat, [(wj, 1, 1, jsc, jsh, 0)], img_bias=bias, means=True)  # L4: project + mean
 
 
+def _mha_is(m):
+    return (type(m) is nn.MultiheadAttention and m.embed_dim == 256 and m.num_heads == 4 and m.batch_first
+            and m._qkv_same_embed_dim and m.in_proj_bias is not None and m.out_proj.bias is not None
+            and m.bias_k is None and m.bias_v is None and not m.add_zero_attn)
+
+
+def _linear_is(m, cin, cout):
+    return (type(m) is nn.Linear and m.in_features == cin and m.bias is not None
+            and (cout is None or m.out_features == cout))
+
+
+def _ln_is(m, c):
+    return (type(m) is nn.LayerNorm and tuple(m.normalized_shape) == (c,) and m.elementwise_affine
+            and m.bias is not None)
+
+
+def _gelu_is(m):
+    return type(m) is nn.GELU and m.approximate == "none"
+
+
+class _CameraTailPlan:
+    """What K14 reads of camera_transformer, bev_fusion and unified_predictor: the modules whose structure, mode and
+    hooks decide the route, and the parameter tensors, handed to the kernel where they lie (no copies: an in-place edit,
+    a `load_state_dict` or a `.to()` is seen by the next call)."""
+
+    def __init__(self, model):
+        self.modules = self.modules_of(model)
+        self._ids_ok = None  # (camera_ids' storage and version) that was found equal to arange
+
+    @staticmethod
+    def modules_of(model):
+        """Every module the tail runs (the three and their submodules), or None when they do not have the reference's
+        structure: d_model 256, 4 heads, batch_first, one in_proj, biases, no bias_k / add_zero_attn; FFN 256 -> 512 ->
+        256 and predictor 256 -> 512 -> 256 with erf GELUs and affine LayerNorms."""
+        try:
+            ct, bf, up = model.camera_transformer, model.bev_fusion, model.unified_predictor
+            if type(up) is not UnifiedPredictor:
+                return None
+            enc = up.encoder
+            if not (len(enc) == 7 and _linear_is(enc[0], 256, 512) and _ln_is(enc[1], 512) and _gelu_is(enc[2])
+                    and type(enc[3]) is nn.Dropout and _linear_is(enc[4], 512, 256) and _ln_is(enc[5], 256)
+                    and _gelu_is(enc[6]) and enc[1].eps == enc[5].eps and _linear_is(up.action_head, 256, None)
+                    and _linear_is(up.desc_head, 256, None) and up.camera_weights.dim() == 1):
+                return None
+            if ct is not None:
+                f = ct.ffn
+                if not (type(ct) is LightweightCameraTransformer and _mha_is(ct.self_attn)
+                        and type(ct.cam_embed) is nn.Embedding and ct.cam_embed.embedding_dim == 256
+                        and ct.cam_embed.max_norm is None and _ln_is(ct.norm1, 256) and _ln_is(ct.norm2, 256)
+                        and ct.norm1.eps == ct.norm2.eps and len(f) == 4 and _linear_is(f[0], 256, 512)
+                        and _gelu_is(f[1]) and type(f[2]) is nn.Dropout and _linear_is(f[3], 512, 256)):
+                    return None
+            if bf is not None and not (type(bf) is BEVCameraFusion and _mha_is(bf.cross_attn) and _ln_is(bf.norm, 256)):
+                return None
+            return [m for top in (ct, bf, up) if top is not None for m in top.modules()]
+        except (AttributeError, TypeError, IndexError):
+            return None
+
+    def current(self, model):
+        mods = self.modules_of(model)
+        return mods is not None and len(mods) == len(self.modules) and all(a is b for a, b in zip(mods, self.modules))
+
+    def quiet(self):
+        """Eval mode everywhere and no forward (pre-)hook, on these modules or globally: a hook must keep seeing real
+        module calls."""
+        from torch.nn.modules import module as _m
+        if _m._global_forward_hooks or _m._global_forward_pre_hooks:
+            return False
+        return not any(m.training or m._forward_hooks or m._forward_pre_hooks for m in self.modules)
+
+    def ids_are_arange(self, ids, n):
+        """camera_ids == arange(n): compared once per buffer version (a device read), never per step."""
+        if ids.dim() != 1 or ids.numel() != n or ids.dtype != torch.long:
+            return False
+        key = (ids.data_ptr(), ids._version, ids.device)
+        if self._ids_ok != key:
+            if not torch.equal(ids.detach().cpu(), torch.arange(n)):
+                return False
+            self._ids_ok = key
+        return True
+
+    @staticmethod
+    def params(model):
+        """{field of lss_camera_tail_desc_t: the modules' own tensor}."""
+        ct, bf, up = model.camera_transformer, model.bev_fusion, model.unified_predictor
+        enc = up.encoder
+        p = {"cam_w": up.camera_weights, "enc1_w": enc[0].weight, "enc1_b": enc[0].bias, "ln1_w": enc[1].weight,
+             "ln1_b": enc[1].bias, "enc2_w": enc[4].weight, "enc2_b": enc[4].bias, "ln2_w": enc[5].weight,
+             "ln2_b": enc[5].bias, "act_w": up.action_head.weight, "act_b": up.action_head.bias,
+             "desc_w": up.desc_head.weight, "desc_b": up.desc_head.bias}
+        eps = {"eps_pred": enc[1].eps}
+        if ct is not None:
+            sa, f = ct.self_attn, ct.ffn
+            p.update(cam_embed=ct.cam_embed.weight, sa_in_w=sa.in_proj_weight, sa_in_b=sa.in_proj_bias,
+                     sa_out_w=sa.out_proj.weight, sa_out_b=sa.out_proj.bias, norm1_w=ct.norm1.weight,
+                     norm1_b=ct.norm1.bias, ffn1_w=f[0].weight, ffn1_b=f[0].bias, ffn2_w=f[3].weight, ffn2_b=f[3].bias,
+                     norm2_w=ct.norm2.weight, norm2_b=ct.norm2.bias)
+            eps["eps_cam"] = ct.norm1.eps
+        if bf is not None:
+            ca = bf.cross_attn
+            p.update(ca_in_w=ca.in_proj_weight, ca_in_b=ca.in_proj_bias, ca_out_w=ca.out_proj.weight,
+                     ca_out_b=ca.out_proj.bias, norm3_w=bf.norm.weight, norm3_b=bf.norm.bias)
+            eps["eps_fuse"] = bf.norm.eps
+        return p, eps
+
+
 class LightweightCameraTransformer(nn.Module):
     """One post-norm transformer layer over the N camera tokens of a sample."""
 
@@ -764,6 +877,48 @@ class VoVNetBEVTransformer(_LiftSplatMixin, nn.Module):
         scene = self.sceneunder(self.feature_pyramid(c3))
         return scene.mean(dim=(2, 3))
 
+    def _camera_tail_native_ok(self, tokens, refined):
+        """Does the inference branch of `forward` take K14 behind the scene tokens?  No autograd, every tail module in
+        eval mode and free of forward hooks (here and globally), the reference's structure, fp32 parameters on the
+        tokens' GPU, shapes `lss_camera_tail_ok` accepts; LSS_CAMERA_TAIL_NATIVE=0 keeps the library composition.
+        Returns the kernel's operands, or None."""
+        if os.environ.get("LSS_CAMERA_TAIL_NATIVE", _CAMERA_TAIL_NATIVE_DEFAULT) == "0":
+            return None
+        if not (torch.is_tensor(tokens) and tokens.is_cuda and tokens.dim() == 3 and tokens.dtype == torch.float32
+                and tokens.shape[2] == 256):
+            return None
+        ct, bf, up = self.camera_transformer, self.bev_fusion, self.unified_predictor
+        tops = [m for m in (ct, bf, up) if m is not None]
+        if any(m.training for m in tops) or _needs_autograd(tops[0], tokens, refined) or any(
+                _needs_autograd(m) for m in tops[1:]):
+            return None
+        plan = self.__dict__.get("_tail_plan")
+        if plan is None or not plan.current(self):
+            if _CameraTailPlan.modules_of(self) is None:
+                return None
+            plan = self.__dict__["_tail_plan"] = _CameraTailPlan(self)
+        if not plan.quiet():
+            return None
+        B, N = tokens.shape[:2]
+        if up.camera_weights.numel() != N:
+            return None
+        if ct is not None and not (ct.cam_embed.num_embeddings >= N and plan.ids_are_arange(self.camera_ids, N)):
+            return None
+        if bf is not None and not (torch.is_tensor(refined) and refined.device == tokens.device and refined.dim() == 4
+                                   and refined.shape[0] == B and refined.shape[3] == 256 and refined.is_contiguous()
+                                   and refined.dtype in (torch.bfloat16, torch.float32)):
+            return None
+        params, eps = plan.params(self)
+        for k, t in params.items():
+            if t.dtype != torch.float32 or t.device != tokens.device or not t.is_contiguous():
+                return None
+            if t.dim() == 2 and t.data_ptr() % 16:  # the kernel reads matrix rows 16 bytes at a time
+                return None
+        if not ops.camera_tail_ok(B, N, up.action_head.out_features, up.desc_head.out_features):
+            return None
+        params.update(eps)
+        return params
+
     def forward(self, imgs, rots, trans, intrins, post_rots, post_trans):
         """imgs: (B*N,3,H,W) / (B,N,3,H,W) camera images for a real trunk, or the
         trunk's {'c3','c4'} maps for the default pass-through.  Returns
@@ -784,15 +939,35 @@ class VoVNetBEVTransformer(_LiftSplatMixin, nn.Module):
             layout = ops.BEV_NHWC_BF16 if dt == ops.DT_BF16 else ops.BEV_NHWC_F32
             grid = self.get_voxels(c3, c4, rots, trans, intrins, post_rots, post_trans, layout)
             bev_seg, refined = be.forward_nhwc(grid.permute(0, 2, 3, 1), dt)
-            bev_pooled = refined.float().mean(dim=(1, 2))
+            return (bev_seg,) + self.scene_outputs(self.scene_tokens(c3).view(B, N, -1), refined)
 
         tokens = self.scene_tokens(c3).view(B, N, -1)
+        CAMERA_TAIL_CALLS["composition"] += 1
+        return (bev_seg,) + self._tail(tokens, bev_pooled)
+
+    def scene_outputs(self, tokens, refined):
+        """The inference branch behind the scene tokens: tokens (B, N, 256) fp32 and the refined BEV map (B, X, Y, 256),
+        channels-last in the conv dtype -> (action, description).  K14 when `_camera_tail_native_ok` (two launches:
+        `bev_pool` + `camera_tail`, no fp32 copy of the map), else the pooled map through the three modules."""
+        params = self._camera_tail_native_ok(tokens, refined)
+        if params is not None:
+            CAMERA_TAIL_CALLS["native"] += 1
+            with ops.region("six_token_tail"):
+                if self.bev_fusion is None:
+                    return ops.camera_tail(tokens.contiguous(), params)
+                R = refined.shape[1] * refined.shape[2]
+                return ops.camera_tail(tokens.contiguous(), params, ops.bev_pool(refined), 1.0 / R)
+        CAMERA_TAIL_CALLS["composition"] += 1
+        return self._tail(tokens, refined.float().mean(dim=(1, 2)))
+
+    def _tail(self, tokens, bev_pooled):
+        B = tokens.shape[0]
         if self.camera_transformer is not None:
             tokens = self.camera_transformer(tokens, self.camera_ids.unsqueeze(0).expand(B, -1))
         if self.bev_fusion is not None:
             tokens = self.bev_fusion(tokens, bev_pooled)
         action, description = self.unified_predictor(tokens)
-        return bev_seg, action, description
+        return action, description
 
 
 def _native_lift(model, c3, c4, calib, B, Ncam, layout):

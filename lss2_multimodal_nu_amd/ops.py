@@ -1986,3 +1986,115 @@ def camera_pool_bias(mean, wg, scale, shift, wj, want_g=False):
         N.check(N.lib().lss_camera_pool_bias_fwd(N.ptr(mean), N.ptr(wg), N.ptr(scale), N.ptr(shift), N.ptr(wj), BN, C, Cg,
                                                  Cout, N.ptr(g), N.ptr(bias), N.stream()), "lss_camera_pool_bias_fwd")
     return (g, bias) if want_g else bias
+
+
+# --- K14: the six-token tail of the vovnet model at inference (csrc/camera_tail.hip) ---------------------------------
+def camera_tail_ok(B, n_tok, n_action, n_desc):
+    """Does the tail kernel take B samples of n_tok tokens and these class counts?  (lss_camera_tail_ok)"""
+    return N.lib().lss_camera_tail_ok(int(B), int(n_tok), int(n_action), int(n_desc)) == 1
+
+
+def bev_pool_parts(B, R):
+    """The default number of row ranges `bev_pool` splits R rows into (lss_bev_pool_parts): a function of R alone."""
+    parts = N.lib().lss_bev_pool_parts(int(B), int(R))
+    if parts < 1:
+        raise ValueError("bev_pool: B=%d R=%d outside the kernel's limits" % (B, R))
+    return parts
+
+
+def bev_pool(map_nhwc, parts=None):
+    """Column sums of a channels-last map (lss_bev_pool_fwd): (B, ..., 256) bf16 or fp32 contiguous -> (B, P, 256) fp32,
+    part p the sums over the p-th contiguous range of the R = prod(...) rows.  `partials.sum(1) / R` is the mean over
+    the map; `camera_tail(..., bev=partials, bev_scale=1 / R)` takes it without another launch."""
+    if (not torch.is_tensor(map_nhwc) or not map_nhwc.is_cuda or map_nhwc.dtype not in _DT or map_nhwc.dim() < 3
+            or not map_nhwc.is_contiguous()):
+        raise ValueError("map must be a contiguous (B, ..., 256) bf16 or fp32 GPU tensor")
+    B, C = map_nhwc.shape[0], map_nhwc.shape[-1]
+    R = map_nhwc[0].numel() // C if C else 0
+    if C != 256 or B < 1 or R < 1:
+        raise ValueError("bev_pool takes (B >= 1, R >= 1, 256) maps, got %s" % (tuple(map_nhwc.shape),))
+    P = bev_pool_parts(B, R) if parts is None else int(parts)
+    if not 1 <= P <= 256:
+        raise ValueError("parts must be in 1..256, got %d" % P)
+    partials = torch.empty(B, P, 256, dtype=torch.float32, device=map_nhwc.device)
+    with _timed("bev_pool"):
+        N.check(N.lib().lss_bev_pool_fwd(N.ptr(map_nhwc), _DT[map_nhwc.dtype], B, R, C, P, N.ptr(partials), N.stream()),
+                "lss_bev_pool_fwd")
+    return partials
+
+
+def _camera_tail_shapes(n_embed, n_tok, n_action, n_desc):
+    d, ff = 256, 512
+    return {"cam_embed": (n_embed, d), "sa_in_w": (3 * d, d), "sa_in_b": (3 * d,), "sa_out_w": (d, d), "sa_out_b": (d,),
+            "norm1_w": (d,), "norm1_b": (d,), "ffn1_w": (ff, d), "ffn1_b": (ff,), "ffn2_w": (d, ff), "ffn2_b": (d,),
+            "norm2_w": (d,), "norm2_b": (d,),
+            "ca_in_w": (3 * d, d), "ca_in_b": (3 * d,), "ca_out_w": (d, d), "ca_out_b": (d,), "norm3_w": (d,),
+            "norm3_b": (d,),
+            "cam_w": (n_tok,), "enc1_w": (ff, d), "enc1_b": (ff,), "ln1_w": (ff,), "ln1_b": (ff,), "enc2_w": (d, ff),
+            "enc2_b": (d,), "ln2_w": (d,), "ln2_b": (d,), "act_w": (n_action, d), "act_b": (n_action,),
+            "desc_w": (n_desc, d), "desc_b": (n_desc,)}
+
+
+def camera_tail(tokens, params, bev=None, bev_scale=1.0):
+    """camera_transformer -> bev_fusion -> unified_predictor at inference in ONE launch (lss_camera_tail_fwd).
+
+    tokens  (B, N <= 8, 256) fp32 contiguous
+    params  {field of lss_camera_tail_desc_t: fp32 contiguous GPU tensor}, read in place, plus the floats "eps_cam",
+            "eps_fuse", "eps_pred" (default 1e-5) and optionally "ids" (B, N) int64 (default 0 .. N-1).  The 13 operands of
+            the camera transformer (`N.CameraTailDesc.CAMERA`) and the 6 of the fusion (`.FUSION`) are each given whole
+            or left out (the stage is then skipped); the predictor's 13 are required.
+    bev     with the fusion: the pooled BEV token (B, 256), or `bev_pool`'s partials (B, P, 256) with bev_scale = 1 / R
+    Returns (action (B, n_action), description (B, n_desc)), fp32."""
+    if not torch.is_tensor(tokens) or tokens.dim() != 3 or tokens.shape[2] != 256:
+        raise ValueError("tokens must be (B, N, 256)")
+    _f32c(tokens, "tokens")
+    B, n_tok = tokens.shape[0], tokens.shape[1]
+    D = N.CameraTailDesc
+    missing = [k for k in D.PREDICTOR if params.get(k) is None]
+    if missing:
+        raise ValueError("camera_tail: the predictor's operands are required, missing %s" % missing)
+    if params["act_w"].dim() != 2 or params["desc_w"].dim() != 2:
+        raise ValueError("act_w and desc_w must be matrices")
+    n_action, n_desc = params["act_w"].shape[0], params["desc_w"].shape[0]
+    if B < 1 or not camera_tail_ok(B, n_tok, n_action, n_desc):
+        raise ValueError("lss_camera_tail_ok refuses B=%d N=%d n_action=%d n_desc=%d" % (B, n_tok, n_action, n_desc))
+    stages = []
+    for group in (D.CAMERA, D.FUSION):
+        given = [k for k in group if params.get(k) is not None]
+        if given and len(given) != len(group):
+            raise ValueError("camera_tail: a stage is given whole or not at all, got only %s" % given)
+        stages.append(bool(given))
+    with_cam, with_fusion = stages
+    n_embed = params["cam_embed"].shape[0] if with_cam and params["cam_embed"].dim() == 2 else 0
+    shapes = _camera_tail_shapes(n_embed, n_tok, n_action, n_desc)
+    d = D()
+    names = D.PREDICTOR + (D.CAMERA if with_cam else ()) + (D.FUSION if with_fusion else ())
+    for k in names:
+        t = _f32c(params[k], k, shapes[k])
+        if t.device != tokens.device:
+            raise ValueError("%s lives on %s, the tokens on %s" % (k, t.device, tokens.device))
+        setattr(d, k, t.data_ptr())
+    ids = params.get("ids") if with_cam else None
+    if ids is not None:
+        if (ids.dtype != torch.int64 or not ids.is_cuda or not ids.is_contiguous()
+                or tuple(ids.shape) != (B, n_tok)):
+            raise ValueError("ids must be a contiguous (B, N) int64 GPU tensor")
+        d.ids = ids.data_ptr()
+    elif with_cam and n_embed < n_tok:
+        raise ValueError("cam_embed has %d rows for %d tokens" % (n_embed, n_tok))
+    if with_fusion:
+        if bev is None or bev.dim() not in (2, 3):
+            raise ValueError("the fusion needs bev (B, 256) or (B, P, 256)")
+        P = 1 if bev.dim() == 2 else bev.shape[1]
+        _f32c(bev, "bev", (B, 256) if bev.dim() == 2 else (B, P, 256))
+        if not 1 <= P <= 256 or bev.device != tokens.device:
+            raise ValueError("bev: 1..256 parts on the tokens' device")
+        d.bev, d.bev_parts, d.bev_scale = bev.data_ptr(), P, float(bev_scale)
+    action = torch.empty(B, n_action, dtype=torch.float32, device=tokens.device)
+    description = torch.empty(B, n_desc, dtype=torch.float32, device=tokens.device)
+    d.tokens, d.action, d.description = tokens.data_ptr(), action.data_ptr(), description.data_ptr()
+    d.eps_cam, d.eps_fuse, d.eps_pred = (float(params.get(k, 1e-5)) for k in ("eps_cam", "eps_fuse", "eps_pred"))
+    d.B, d.N, d.n_embed, d.n_action, d.n_desc = B, n_tok, n_embed, n_action, n_desc
+    with _timed("camera_tail"):
+        N.check(N.lib().lss_camera_tail_fwd(ctypes.byref(d), N.stream()), "lss_camera_tail_fwd")
+    return action, description
