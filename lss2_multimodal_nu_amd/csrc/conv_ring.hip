@@ -22,8 +22,9 @@
 //   wave  8    weight loader: streams the weight slabs by LDS-DMA
 //   waves 9-11 patch loaders: plain DMA of the input patch, or source-window DMA + four-corner blend (fused upsample)
 // K loop: chunk = 32 input channels, step = (chunk, tap): 20 MFMAs per consumer against one 8-KiB weight slab.
-// LDS (120-154 KiB):
-//   ring   NSL (7-8) slots x 8 KiB: the weight slab of one step in FRAGMENT ORDER (piece (cg, t, lane) at
+// LDS (136-154 KiB):
+//   ring   three slots x 24 KiB, a slot = the three slabs of a tap row (per-strip fused layout: seven slots of one
+//          8-KiB slab): the weight slab of one step in FRAGMENT ORDER (piece (cg, t, lane) at
 //          ((cg*4+t)*64+lane)*16: a consumer reads its A fragment lane-linearly = conflict-free); the packed weights
 //          in global memory have exactly this image, so a slab is 8 fully coalesced 1-KiB DMA pieces
 //   patch  2 buffers x 4 strips x (6 rows x 24 positions x 64 B): position-major, the four 16-B channel pieces of a
@@ -83,10 +84,10 @@ struct RingArgs {
 __device__ __attribute__((aligned(128))) unsigned char lss_ring_zero_page[128];  // source of out-of-image patch pieces
 __device__ int lss_ring_timeouts;  // flag waits that hit their bound (must stay 0; read by lss_conv2d_ring_timeouts)
 
-template <int MODE, bool HEAD, int NSL, bool T22>
+template <int MODE, bool HEAD, int NSL, bool T22, int SPS>
 struct RingLds {
   static constexpr int RING = 0;
-  static constexpr int PATCH = NSL * RK_SLAB;
+  static constexpr int PATCH = NSL * SPS * RK_SLAB;  // NSL slots of SPS slabs
   static constexpr int PBUF = T22 ? RK_TPIECE * 1024 : 4 * RK_STRIP_PATCH;  // one patch buffer (all strips)
   static constexpr int SRC = PATCH + 2 * PBUF;                        // two buffers
   static constexpr int HEADX = SRC + (MODE == 1 ? (T22 ? RK_TSRC : 4 * RK_SRC_STRIP) : 0);
@@ -170,13 +171,23 @@ struct RingTile {
 // round.)  A weight slab now feeds four strips instead of two: half the weight bytes streamed into LDS per MFMA.
 //
 // T22 (MODE 1 only): the shared 2 x 2 tile layout above; strip s is tile row s >> 1, tile column s & 1.
-template <int MODE, bool HEAD, int NSL, bool T22>
+//
+// SPS = slabs per weight slot.  1: a slot is the slab of one step, handed over at every step (NSL = 7-8 slots).  3: a
+// slot is one TAP ROW, the three slabs (nb, chunk, tap 3r .. 3r + 2) that already lie 24 contiguous KiB in the packed
+// image, and the ring is NSL = 3 slots = exactly one chunk: a consumer's slot is TAP / 3 and its generation chunk + 1,
+// both known per unrolled step, the tap's slab is an immediate of the fragment reads, and the FULL check, the FREE add
+// and the flag read happen once per three steps.  The per-strip fused layout has no LDS for 72 KiB of ring (165 632 B)
+// and keeps SPS = 1.
+template <int MODE, bool HEAD, int NSL, bool T22, int SPS>
 __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a) {
   static_assert(!T22 || MODE == 1, "shared tile: fused upsample only");
-  using L = RingLds<MODE, HEAD, NSL, T22>;
+  using L = RingLds<MODE, HEAD, NSL, T22, SPS>;
   constexpr int PW = T22 ? RK_TPW : RK_PW;  // patch row pitch (positions)
-  constexpr int LA = NSL - 2;  // weight slabs in flight at most: one slot is being consumed, one is published and waiting
+  constexpr int LA = NSL - 2;  // weight slots in flight at most: one slot is being consumed, one is published and waiting
+  constexpr int SLOTB = SPS * RK_SLAB, NPC = SPS * 8;  // bytes and 1-KiB DMA pieces of a slot
   static_assert(NSL >= 3 && NSL <= 8, "ring depth");
+  static_assert(SPS == 1 || (SPS == 3 && NSL == 3), "a three-slab slot is a tap row and the ring one chunk");
+  static_assert((LA + 1) * NPC < 64, "the pieces in flight must fit the 6-bit vmcnt");
   static_assert(L::TOTAL <= 160 * 1024, "LDS of one CU");
   __shared__ __attribute__((aligned(1024))) unsigned char smem[L::TOTAL];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -238,27 +249,35 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
     // =============================== weight loader ===============================
     __builtin_amdgcn_s_setprio(RK_PRIO_W);
     const unsigned char* wsrc = a.w + (size_t)T.nb * a.nch * 9 * RK_SLAB + lane * 16;
-    // Policy: issue a slab whenever its slot is free (at most LA + 1 in flight); while the next slot is NOT free, wait
-    // for the OLDEST slab in flight only (a counted vmcnt: the wave blocks for what is left of that slab's latency,
-    // not for the whole queue), publish it, look again.  History: build 1 published slab i - LA when it issued slab i -
-    // the consumers got slab s + 5 only after releasing slab s + 3, half a step before they needed it (603 TF on
-    // up1.conv3); build 2 drained the whole queue (vmcnt(0)) before blocking on FREE.
+    // Policy, in slot units (a slot = SPS slabs = NPC pieces): issue a slot whenever it is free (at most LA + 1 in
+    // flight); while the next slot is NOT free, wait for the OLDEST slot in flight only (a counted vmcnt: the wave
+    // blocks for what is left of that slot's latency, not for the whole queue), publish it, look again.  History:
+    // build 1 published slab i - LA when it issued slab i - the consumers got slab s + 5 only after releasing slab
+    // s + 3, half a step before they needed it (603 TF on up1.conv3); build 2 drained the whole queue (vmcnt(0))
+    // before blocking on FREE.  Three-slab slots: LA = 1, at most two slots = 48 pieces in flight, so the counted waits
+    // are vmcnt(24) and vmcnt(0).
     int slot = 0, gen = 1, pslot = 0, pgen = 1, inflight = 0;  // inflight = issued, not yet published
     auto publish_oldest = [&]() {
-      switch (inflight) {  // all but the inflight - 1 youngest slabs have landed
-        case 1: lss_wait_vmcnt<0>(); break;
-        case 2: lss_wait_vmcnt<8>(); break;
-        case 3: lss_wait_vmcnt<16>(); break;
-        case 4: lss_wait_vmcnt<24>(); break;
-        case 5: lss_wait_vmcnt<32>(); break;
-        case 6: lss_wait_vmcnt<40>(); break;
-        default: lss_wait_vmcnt<48>(); break;
+      if constexpr (SPS == 3) {  // all but the inflight - 1 youngest slots have landed
+        if (inflight == 1) lss_wait_vmcnt<0>();
+        else lss_wait_vmcnt<NPC>();
+      } else {
+        switch (inflight) {
+          case 1: lss_wait_vmcnt<0>(); break;
+          case 2: lss_wait_vmcnt<8>(); break;
+          case 3: lss_wait_vmcnt<16>(); break;
+          case 4: lss_wait_vmcnt<24>(); break;
+          case 5: lss_wait_vmcnt<32>(); break;
+          case 6: lss_wait_vmcnt<40>(); break;
+          default: lss_wait_vmcnt<48>(); break;
+        }
       }
       rk_set(flags + F_FULL_W + pslot, pgen, lane);
       if (++pslot == NSL) { pslot = 0; ++pgen; }
       --inflight;
     };
-    for (int i = 0; i < nsteps; ++i) {
+    const int nfill = nsteps / SPS;  // 9 steps per chunk: whole slots
+    for (int i = 0; i < nfill; ++i) {
       if (gen > 1) {
         int spins = 0;
         while (rk_peek(flags + F_FREE_W + slot) < RK_NCONS * (gen - 1)) {
@@ -275,10 +294,10 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
         }
         asm volatile("" ::: "memory");
       }
-      unsigned char* dst = smem + L::RING + slot * RK_SLAB;
+      unsigned char* dst = smem + L::RING + slot * SLOTB;
 #ifndef RK_DIAG_NOWDMA  // timing-only build: no weight traffic, the hand-off protocol alone
 #pragma unroll
-      for (int k = 0; k < 8; ++k) lss_glds16(wsrc + (size_t)i * RK_SLAB + k * 1024, dst + k * 1024);
+      for (int k = 0; k < NPC; ++k) lss_glds16(wsrc + (size_t)i * SLOTB + k * 1024, dst + k * 1024);
 #endif
       ++inflight;
       if (inflight > LA) publish_oldest();
@@ -498,7 +517,7 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
   // ================================== consumers ==================================
   __builtin_amdgcn_s_setprio(RK_PRIO_C);
   const int sidx = wave >> 1, cg = wave & 1;
-  const int n = lane & 15, kq = lane >> 4;
+  const int n0 = lane & 15, kq0 = lane >> 4;  // (the epilogue makes its own n, kq: see there)
   // this wave's strip (selects, not indexing: a runtime-indexed struct member would live in scratch)
   const int my_b = sidx == 0 ? T.b[0] : sidx == 1 ? T.b[1] : sidx == 2 ? T.b[2] : T.b[3];
   const int my_oy0 = sidx == 0 ? T.oy0[0] : sidx == 1 ? T.oy0[1] : sidx == 2 ? T.oy0[2] : T.oy0[3];
@@ -526,8 +545,29 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
   // - so block j of phase A needs `lgkmcnt(6 - j)` (the 4 - j younger pixel fragments and fw2, fw3 may still be in
   // flight) and phase B `lgkmcnt(3)`.  The waits take the fragments they cover as read-write operands, which is what
   // keeps the MFMAs behind them (cdna_hip_programming.md section 5.4 rule 18).
+  // Three-slab slots (SPS = 3): the flag read and the FREE_W add exist once per slot, so the content depends on
+  // r = TAP % 3 (the FREE_P add at tap 8 as before):
+  //     r = 0:  fw0' fw1'       add  fp0' .. fp4' | fw2 fw3 | phase A | fw0" fw1"       | phase B        fp0" ..
+  //     r = 1:  fw0' fw1'            fp0' .. fp4' | fw2 fw3 | phase A | fw0" fw1" flag" | phase B        fp0" ..
+  //     r = 2:  fw0' fw1' flag'      fp0' .. fp4' | fw2 fw3 | phase A | fw0" fw1"       | phase B  add   fp0" ..
+  // The flag word (FULL_W of the NEXT slot) is requested in the slot's second step and checked in its third, in front
+  // of the first reads of that slot; the add releases the slot behind the phase-B wait of its third step = behind its
+  // last read.  Everything that differs lies OLDER than fp0' in the queue, so phase A keeps `lgkmcnt(6 - j)`; phase B
+  // has two younger reads (r = 0, 2: `lgkmcnt(2)`) or three (r = 1: `lgkmcnt(3)`).  (The flag is read one STEP ahead of
+  // its check, not one slot: the slot it guards was released three steps before that read and is refilled meanwhile;
+  // a read three steps earlier would see the old generation every time and send the wave into the poll.)
   bf16x8 fw[4], fp[5];
 #define RK_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
+  // SPS = 3: the MFMAs are inline asm with the accumulator TIED (D = C).  The builtin leaves D free, and over the nine
+  // unrolled steps the allocator rotates the 20 accumulators through the fragment registers: ~140 register copies per
+  // chunk in the one-slab kernels, and in the first three-slab builds an accumulator spilled inside the loop.  The
+  // hazards the compiler would otherwise pad for: an accumulator is touched once per step (20 MFMAs apart), the
+  // fragments come from LDS behind counted waits, and the epilogue's first VALU read sits behind RK_MFMA_DRAIN.
+#define RK_MFMA(c, wf, pf)                                                                                   \
+  do {                                                                                                       \
+    if constexpr (SPS == 3) asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c) : "v"(wf), "v"(pf)); \
+    else c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf, pf, c, 0, 0, 0);                                    \
+  } while (0)
   // The two lane-dependent offsets - weight fragment (cg * 4096 + lane * 16 < 8192) and pixel fragment (< 8320) - live
   // packed in ONE register; an address is (field | or + wave-uniform part): 1-2 VALU where the first builds spent ~25
   // per step recomputing them from the lane id.  The few VALU / SALU instructions of a step are placed BETWEEN the
@@ -535,30 +575,48 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
   // where neither this wave nor - when the two consumer waves of a SIMD run in step - its partner issues MFMAs.
   const unsigned int lanepk =
       (unsigned int)(cg * 4096 + lane * 16) |
-      ((unsigned int)((((n >> 2) * PW + (n & 3)) * RK_POSB + (kq << 4)) ^ (((n >> 2) & 1) << 5)) << 16);
+      ((unsigned int)((((n0 >> 2) * PW + (n0 & 3)) * RK_POSB + (kq0 << 4)) ^ (((n0 >> 2) & 1) << 5)) << 16);
   const unsigned int flag_base = (unsigned int)(__UINTPTR_TYPE__)flags;
   // the strip's patch; T22: the strip's corner inside the tile's patch (4 rows / 20 columns on: multiples of 256 B,
   // row parity kept, so the swizzle and the bank pattern of every read are those of a strip's own patch)
   const int pconst = L::PATCH + (T22 ? ((sidx >> 1) * RK_SH * PW + (sidx & 1) * RK_SW) * RK_POSB : sidx * RK_STRIP_PATCH);
   // FREE counters: lane 0 adds 1 (exec narrowed inside the asm: no branch around it)
+  // SPS = 3: the word is known per unrolled step, so address and the 1 are made inside the asm from a scalar operand
+  // (as "v" operands they are loop-invariant constants that the compiler parks in registers for the whole loop, and
+  // the loop has none to spare); the flag read below does the same with its own destination as address register
   auto add1 = [&](int word) {
     unsigned long long save;
-    asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, 1\n\tds_add_u32 %1, %2\n\ts_mov_b64 exec, %0"
-                 : "=&s"(save)
-                 : "v"(flag_base + 4 * word), "v"(1)
-                 : "memory");
+    if constexpr (SPS == 1) {
+      asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, 1\n\tds_add_u32 %1, %2\n\ts_mov_b64 exec, %0"
+                   : "=&s"(save)
+                   : "v"(flag_base + 4 * word), "v"(1)
+                   : "memory");
+    } else {
+      unsigned int ta, tb;
+      asm volatile("s_mov_b64 %0, exec\n\ts_mov_b64 exec, 1\n\tv_mov_b32 %1, %3\n\tv_mov_b32 %2, 1\n\t"
+                   "ds_add_u32 %1, %2\n\ts_mov_b64 exec, %0"
+                   : "=&s"(save), "=&v"(ta), "=&v"(tb)
+                   : "s"(flag_base + 4 * word)
+                   : "memory");
+    }
   };
 
   RK_ST(const unsigned long long tc_loop = __builtin_amdgcn_s_memtime(); const unsigned long long tr_loop = __builtin_amdgcn_s_memrealtime();)
-  int slot = 0, gen = 1, buf = 0, pgen = 1;
+  int slot = 0, gen = 1, buf = 0, pgen = 1;  // (SPS = 3: the slot is TAP / 3, `slot` stays 0; gen = chunk + 1)
   rk_wait_ge(flags + F_FULL_P + 0, RK_NPATCH);
   rk_wait_ge(flags + F_FULL_W + 0, 1);
-  int fnext;  // FULL word of the next step's slot, read one step ahead
+  int fnext = 0;  // FULL word of the next slot, read one step ahead of its check
+  // SPS = 3: the ring is one chunk, so the slab of tap t lies at t * RK_SLAB behind ONE lane-dependent base and is an
+  // immediate of the fragment reads (16-bit field: up to tap 7, 7 * 8192 + 3072); tap 8 takes a second base, made by
+  // one v_add in tap 7's phase A and dead behind tap 8 (inline asm: as plain C++ it is loop-invariant, gets hoisted and
+  // costs a register for the whole loop - with three per-slot bases the first build spilled an accumulator)
+  const int wbase = (int)(lanepk & 0xffffu) + L::RING;
+  int w8 = 0;
   {
     const int wa = (int)(lanepk & 0xffffu) + L::RING, pa = (int)(lanepk >> 16) + pconst;
     RK_DSR(fw[0], wa, 0);
     RK_DSR(fw[1], wa, 1024);
-    asm volatile("ds_read_b32 %0, %1" : "=v"(fnext) : "v"(flag_base + 4 * (F_FULL_W + (1 % NSL))));
+    if constexpr (SPS == 1) asm volatile("ds_read_b32 %0, %1" : "=v"(fnext) : "v"(flag_base + 4 * (F_FULL_W + (1 % NSL))));
     RK_DSR(fp[0], pa, 0 * 4 * RK_POSB);
     RK_DSR(fp[1], pa, 1 * 4 * RK_POSB);
     RK_DSR(fp[2], pa, 2 * 4 * RK_POSB);
@@ -570,84 +628,121 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
     constexpr int TAP = decltype(TAPc)::value;
     constexpr int NT = (TAP + 1) % 9;
     constexpr int POFF = (NT / 3) * (PW * RK_POSB) + (NT % 3) * RK_POSB;  // tap offset of the next step's pixel fragments
-    {
+    constexpr bool SLOT_END = SPS == 1 || TAP % 3 == 2;  // the step that reads the last slab of its slot
+    constexpr bool FLAG_RD = SPS == 1 || TAP % 3 == 1;   // the step that requests the next slot's FULL word
+    if constexpr (SPS == 1) {
       const int wa = (int)(lanepk & 0xffffu) + (L::RING + slot * RK_SLAB);
       RK_DSR(fw[2], wa, 2048);
       RK_DSR(fw[3], wa, 3072);
+    } else if constexpr (TAP < 8) {
+      RK_DSR(fw[2], wbase, TAP * RK_SLAB + 2048);
+      RK_DSR(fw[3], wbase, TAP * RK_SLAB + 3072);
+    } else {
+      RK_DSR(fw[2], w8, 2048);
+      RK_DSR(fw[3], w8, 3072);
     }
     __builtin_amdgcn_sched_barrier(0);
     // phase A; the next step's bookkeeping and addresses ride between its MFMA pairs
     asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(fw[0]), "+v"(fw[1]), "+v"(fp[0]));
-    acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[0], fp[0], acc[0][0], 0, 0, 0);
-    acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[1], fp[0], acc[0][1], 0, 0, 0);
+    RK_MFMA(acc[0][0], fw[0], fp[0]);
+    RK_MFMA(acc[0][1], fw[1], fp[0]);
     __builtin_amdgcn_sched_barrier(0);
-    int nslot = slot + 1, ngen = gen;
-    if (nslot == NSL) { nslot = 0; ++ngen; }
+    int nslot = slot, ngen = gen;  // slot and generation of the next step's slab
+    if constexpr (SPS == 1) {
+      if (++nslot == NSL) { nslot = 0; ++ngen; }
+    } else {
+      if (TAP == 8) ++ngen;
+    }
     int nbuf = buf, npgen = pgen;
     if (TAP == 8) {
       nbuf = buf ^ 1;
       if (nbuf == 0) ++npgen;
     }
-    const int wan = (int)(lanepk & 0xffffu) + (L::RING + nslot * RK_SLAB);
+    int wan = 0;
+    if constexpr (SPS == 1) wan = (int)(lanepk & 0xffffu) + (L::RING + nslot * RK_SLAB);
+    else if constexpr (NT == 8) asm volatile("v_add_u32 %0, 0x10000, %1" : "=v"(w8) : "v"(wbase));  // 8 * RK_SLAB
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_waitcnt lgkmcnt(5)" : "+v"(fp[1]));
-    acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[0], fp[1], acc[1][0], 0, 0, 0);
-    acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[1], fp[1], acc[1][1], 0, 0, 0);
+    RK_MFMA(acc[1][0], fw[0], fp[1]);
+    RK_MFMA(acc[1][1], fw[1], fp[1]);
     __builtin_amdgcn_sched_barrier(0);
     const int pan = (int)((lanepk >> 16) ^ (NT / 3 == 1 ? 32u : 0u)) + (pconst + nbuf * L::PBUF);
-    const int n2 = nslot + 1 == NSL ? 0 : nslot + 1;
-    const unsigned int fa = flag_base + 4 * (F_FULL_W + n2);
+    unsigned int fa = 0;  // FULL word of the slot behind the next step's (SPS = 3: of the next slot)
+    if constexpr (SPS == 1) {
+      const int n2 = nslot + 1 == NSL ? 0 : nslot + 1;
+      fa = flag_base + 4 * (F_FULL_W + n2);
+    } else if constexpr (FLAG_RD) {
+      fa = flag_base + 4 * (F_FULL_W + (TAP / 3 + 1) % 3);
+    }
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(fp[2]));
-    acc[2][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[0], fp[2], acc[2][0], 0, 0, 0);
-    acc[2][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[1], fp[2], acc[2][1], 0, 0, 0);
+    RK_MFMA(acc[2][0], fw[0], fp[2]);
+    RK_MFMA(acc[2][1], fw[1], fp[2]);
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(fp[3]));
-    acc[3][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[0], fp[3], acc[3][0], 0, 0, 0);
-    acc[3][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[1], fp[3], acc[3][1], 0, 0, 0);
+    RK_MFMA(acc[3][0], fw[0], fp[3]);
+    RK_MFMA(acc[3][1], fw[1], fp[3]);
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(fp[4]));
-    acc[4][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[0], fp[4], acc[4][0], 0, 0, 0);
-    acc[4][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[1], fp[4], acc[4][1], 0, 0, 0);
+    RK_MFMA(acc[4][0], fw[0], fp[4]);
+    RK_MFMA(acc[4][1], fw[1], fp[4]);
     __builtin_amdgcn_sched_barrier(0);
     if (!last) {
-      // the next step's slab (and, at the last tap, the next chunk's patch) must have been published; the FULL word
-      // was read a step ago, ahead of fragments phase A has waited for
-      if (__builtin_amdgcn_readfirstlane(fnext) < ngen) st0 += 1 + rk_wait_ge(flags + F_FULL_W + nslot, ngen);
+      // the next step's slot, where that is a new one (and, at the last tap, the next chunk's patch) must have been
+      // published; the FULL word was read a step ago, ahead of fragments phase A has waited for
+      if constexpr (SLOT_END) {
+        if (__builtin_amdgcn_readfirstlane(fnext) < ngen)
+          st0 += 1 + rk_wait_ge(flags + F_FULL_W + (SPS == 1 ? nslot : NT / 3), ngen);
+      }
       if (TAP == 8) st1 += rk_wait_ge(flags + F_FULL_P + nbuf, RK_NPATCH * npgen);
       asm volatile("" ::: "memory");
-      RK_DSR(fw[0], wan, 0);
-      RK_DSR(fw[1], wan, 1024);
-      asm volatile("ds_read_b32 %0, %1" : "=v"(fnext) : "v"(fa));
-      __builtin_amdgcn_sched_barrier(0);
-      asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(fw[2]), "+v"(fw[3]));
+      if constexpr (SPS == 1) {
+        RK_DSR(fw[0], wan, 0);
+        RK_DSR(fw[1], wan, 1024);
+      } else if constexpr (NT < 8) {
+        RK_DSR(fw[0], wbase, NT * RK_SLAB + 0);
+        RK_DSR(fw[1], wbase, NT * RK_SLAB + 1024);
+      } else {
+        RK_DSR(fw[0], w8, 0);
+        RK_DSR(fw[1], w8, 1024);
+      }
+      if constexpr (FLAG_RD) {
+        if constexpr (SPS == 1) asm volatile("ds_read_b32 %0, %1" : "=v"(fnext) : "v"(fa));
+        else asm volatile("v_mov_b32 %0, %1\n\tds_read_b32 %0, %0" : "=&v"(fnext) : "s"(fa));
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt lgkmcnt(3)" : "+v"(fw[2]), "+v"(fw[3]));
+      } else {
+        __builtin_amdgcn_sched_barrier(0);
+        asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(fw[2]), "+v"(fw[3]));
+      }
     } else {
       asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(fw[2]), "+v"(fw[3]));
     }
     // phase B: behind block j's MFMAs the pixel fragment of block j is requested for the next step
-    acc[0][2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[2], fp[0], acc[0][2], 0, 0, 0);
-    acc[0][3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[3], fp[0], acc[0][3], 0, 0, 0);
+    RK_MFMA(acc[0][2], fw[2], fp[0]);
+    RK_MFMA(acc[0][3], fw[3], fp[0]);
     __builtin_amdgcn_sched_barrier(0);
-    add1(F_FREE_W + slot);  // the wave has waited for fragments 2, 3: every read of this slab is done
+    // the wave has waited for fragments 2, 3 of the slot's last slab: every read of this slot is done
+    if constexpr (SLOT_END) add1(F_FREE_W + (SPS == 1 ? slot : TAP / 3));
     if (!last) RK_DSR(fp[0], pan, POFF + 0 * 4 * RK_POSB);
     __builtin_amdgcn_sched_barrier(0);
-    acc[1][2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[2], fp[1], acc[1][2], 0, 0, 0);
-    acc[1][3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[3], fp[1], acc[1][3], 0, 0, 0);
+    RK_MFMA(acc[1][2], fw[2], fp[1]);
+    RK_MFMA(acc[1][3], fw[3], fp[1]);
     __builtin_amdgcn_sched_barrier(0);
     if (!last) RK_DSR(fp[1], pan, POFF + 1 * 4 * RK_POSB);
     __builtin_amdgcn_sched_barrier(0);
-    acc[2][2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[2], fp[2], acc[2][2], 0, 0, 0);
-    acc[2][3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[3], fp[2], acc[2][3], 0, 0, 0);
+    RK_MFMA(acc[2][2], fw[2], fp[2]);
+    RK_MFMA(acc[2][3], fw[3], fp[2]);
     __builtin_amdgcn_sched_barrier(0);
     if (!last) RK_DSR(fp[2], pan, POFF + 2 * 4 * RK_POSB);
     __builtin_amdgcn_sched_barrier(0);
-    acc[3][2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[2], fp[3], acc[3][2], 0, 0, 0);
-    acc[3][3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[3], fp[3], acc[3][3], 0, 0, 0);
+    RK_MFMA(acc[3][2], fw[2], fp[3]);
+    RK_MFMA(acc[3][3], fw[3], fp[3]);
     __builtin_amdgcn_sched_barrier(0);
     if (!last) RK_DSR(fp[3], pan, POFF + 3 * 4 * RK_POSB);
     __builtin_amdgcn_sched_barrier(0);
-    acc[4][2] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[2], fp[4], acc[4][2], 0, 0, 0);
-    acc[4][3] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fw[3], fp[4], acc[4][3], 0, 0, 0);
+    RK_MFMA(acc[4][2], fw[2], fp[4]);
+    RK_MFMA(acc[4][3], fw[3], fp[4]);
     __builtin_amdgcn_sched_barrier(0);
     if (!last) RK_DSR(fp[4], pan, POFF + 4 * 4 * RK_POSB);
     // behind the last block every pixel fragment of this chunk has arrived (phase A waited for them)
@@ -667,9 +762,23 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
     step(std::integral_constant<int, 8>{}, c + 1 == a.nch);
   }
 #undef RK_DSR
+#undef RK_MFMA
+  if constexpr (SPS == 3) {
+    // RK_MFMA_DRAIN: 2 x 16 wait states between the last asm MFMA and the first VALU read of an accumulator (the compiler
+    // cannot count them for an MFMA it does not see); every accumulator is an operand, so no read of one moves above it
+#define RK_A(j) "+v"(acc[j][0]), "+v"(acc[j][1]), "+v"(acc[j][2]), "+v"(acc[j][3])
+    asm volatile("s_nop 15\n\ts_nop 15" : RK_A(0), RK_A(1), RK_A(2), RK_A(3), RK_A(4));
+#undef RK_A
+  }
   RK_ST(if (a.stats != nullptr && lane == 0) { unsigned long long* o = a.stats + ((size_t)blockIdx.x * RK_NWAVES + wave) * 6; o[2] = __builtin_amdgcn_s_memrealtime() - t_entry; o[4] = __builtin_amdgcn_s_memtime() - tc_loop; o[5] = __builtin_amdgcn_s_memrealtime() - tr_loop; })  // end of the main loop: ticks, shader cycles and 100-MHz ticks of the loop
 
   // ---- epilogue: lane (q = kq, n) holds channels ch0 .. ch0 + 15 of pixel n of every block ----
+  // SPS = 3: the lane id is read again here (inline asm, so that it is a new value): n, kq and what the compiler derives
+  // from them are otherwise carried through the main loop, which has no register for them (the first builds spilled
+  // five such values in front of the loop and one accumulator inside it)
+  int lane_e = lane;
+  if constexpr (SPS == 3) asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_e));
+  const int n = lane_e & 15, kq = lane_e >> 4;
   const int ch0 = T.nb * 128 + cg * 64 + kq * 16;
   {
     float sc[16], sh[16];
@@ -756,7 +865,7 @@ __global__ __launch_bounds__(RK_NWAVES * 64, 3) void conv_ring_kernel(RingArgs a
 #pragma unroll
       for (int j = 0; j < 5; ++j) hx[(j * 16 + n) * 4 + kq] = part[j];
       lss_wait_lgkm0();
-      rk_set(flags + F_HEAD + sidx, 1, lane);
+      rk_set(flags + F_HEAD + sidx, 1, lane_e);
     } else {
       rk_wait_ge(flags + F_HEAD + sidx, 1);
       if (kq < a.head_n) {
@@ -888,14 +997,16 @@ int lss_conv_ring_launch(const void* x, const void* x2, const void* w_ring, cons
   const bool t22 = fused && a.Hin % RK_TH == 0 && a.Win % RK_TW == 0 &&
                    (int)(a.ry * (RK_TPH - 1) + 0.999f) + 2 <= RK_TSRC_H && (int)(a.rx * (RK_TPW - 1) + 0.999f) + 2 <= RK_TSRC_W;
   const dim3 g((a.nstrips + RK_NS - 1) / RK_NS * a.nblk), blk(RK_NWAVES * 64);
+  // ring depth and slabs per slot (the last two numbers): three tap-row slots where 72 KiB of ring fit, i.e. everywhere
+  // but the per-strip fused layout (seven one-slab slots)
   if (head_n > 0) {
-    if (t22) hipLaunchKernelGGL((conv_ring_kernel<1, true, 7, true>), g, blk, 0, st, a);
-    else if (fused) hipLaunchKernelGGL((conv_ring_kernel<1, true, 7, false>), g, blk, 0, st, a);
-    else hipLaunchKernelGGL((conv_ring_kernel<0, true, 8, false>), g, blk, 0, st, a);
+    if (t22) hipLaunchKernelGGL((conv_ring_kernel<1, true, 3, true, 3>), g, blk, 0, st, a);
+    else if (fused) hipLaunchKernelGGL((conv_ring_kernel<1, true, 7, false, 1>), g, blk, 0, st, a);
+    else hipLaunchKernelGGL((conv_ring_kernel<0, true, 3, false, 3>), g, blk, 0, st, a);
   } else {
-    if (t22) hipLaunchKernelGGL((conv_ring_kernel<1, false, 7, true>), g, blk, 0, st, a);
-    else if (fused) hipLaunchKernelGGL((conv_ring_kernel<1, false, 7, false>), g, blk, 0, st, a);
-    else hipLaunchKernelGGL((conv_ring_kernel<0, false, 8, false>), g, blk, 0, st, a);
+    if (t22) hipLaunchKernelGGL((conv_ring_kernel<1, false, 3, true, 3>), g, blk, 0, st, a);
+    else if (fused) hipLaunchKernelGGL((conv_ring_kernel<1, false, 7, false, 1>), g, blk, 0, st, a);
+    else hipLaunchKernelGGL((conv_ring_kernel<0, false, 3, false, 3>), g, blk, 0, st, a);
   }
   return lss_launch_status();
 }
