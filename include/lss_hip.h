@@ -991,6 +991,78 @@ int lss_bev_pool_parts(int B, long long R);
 int lss_bev_pool_fwd(const void* map, int dt, int B, long long R, int C, int parts, float* partials, void* stream);
 int lss_camera_tail_fwd(const lss_camera_tail_desc_t* desc, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * K15  the TXT half of BEV_TXT at inference behind the ASPP (csrc/txt_heads.hip).  The ASPP itself (SceneUnder(512))
+ *      runs on K13's lss_tapconv_fwd / lss_camera_pool_bias_fwd as they stand.
+ * replaces: src/modules.py:133-144 and src/model_BEV_TXT.py:285-287 (BevPost on the cropped BEV logits), and
+ *           src/model_BEV_TXT.py:293-332 (camera selection, the embedders, the concat with the BevPost map, the two
+ *           Linears, the three predictors, the final cat), in eval mode without autograd.
+ *
+ * lss_bev_post_fwd: crop -> 3x3 conv, stride (2, 1), padding 1, no bias -> folded BatchNorm -> ReLU -> MaxPool (5, 4).
+ *        y[b, o, i, j] = max over the 5 x 4 window of relu(scale[o] * conv(crop)[b, o, 5 i + di, 4 j + dj] + shift[o])
+ *   x      an fp32 map of Hm x Wm pixels read IN PLACE: element (b, c, h, w) lies at x[b sb + c sc + h sh + w sw]
+ *          (element strides, any layout); the crop is rows h0 .. h0 + Hc - 1 and columns w0 .. w0 + Wc - 1 of it and is
+ *          never copied.  The zero padding is around the CROP: a tap outside it reads zero, never the map beyond it.
+ *   w      (Co, Cb, 3, 3) fp32 OIHW, the module's own tensor; scale / shift (Co) fp32, the folded BatchNorm.
+ *   y      (B, Co, Ho, Wo) fp32 contiguous, Ho = (((Hc - 1) / 2) + 1) / 5, Wo = Wc / 4 (integer divisions: incomplete
+ *          pool windows are dropped, as torch does).
+ *   fp32 FMA chains in (channel, ky, kx) order, no atomics, nothing depends on B.
+ *   Argument checks, all before any HIP call: LSS_E_NULL (x, w, scale, shift, y), LSS_E_SHAPE (B outside 1..65535, Cb
+ *   outside 1..8, Co outside 1..16, a crop that is empty or leaves the Hm x Wm map, Ho or Wo zero), LSS_E_LAYOUT (a
+ *   negative stride), LSS_E_ALIGN (4 B).  Nothing is written when a check fails.
+ *
+ * lss_txt_heads_fwd: everything behind the scene map, two launches.
+ *   scene     (B ncams, H, W, 256) bf16 NHWC, contiguous: K13's projection output.
+ *   bev_post  (B, Cp, H, W) fp32 contiguous, Cp <= 8.
+ *   cams      n_slots <= 8 camera indices in 0 .. ncams - 1.  Slot 0 uses the FRONT set (embeder_f1, embeder_f2), every
+ *             other slot the SIDE set (embeder_lr1, embeder_lr2).  The production table is (1, 0, 3, 2, 5): the
+ *             reference's cat([desc_f, desc_l1, desc_l2, desc_r1, desc_r2]).
+ *   a set     embed_w: the [tap][32][256] bf16 image of lss_conv2d_pack_weights (9 taps); embed_scale / embed_shift
+ *             (32) fp32, the folded BatchNorm; lin_w (E, (32 + Cp) H W) and lin_b (E) fp32, the Linear's own tensors
+ *             read in place, E <= 64.
+ *   f1_w (n_desc_f, E), f1_b; f2_w (n_act, E), f2_b; lr_w (1, E), lr_b (1): the predictors' own fp32 tensors.
+ *   For slot s of sample b, with img = b ncams + cams[s]:
+ *        e[c, h, w] = relu(scale[c] * sum_{live taps, k} scene[img, h + ky, w + kx, k] * embed_w[t][c][k] + shift[c])
+ *        y_s[j]     = lin_b[j] + sum_{c, h, w} lin_w[j][c H W + h W + w] * cat([e, bev_post[b]])[c, h, w]
+ *        desc[b, 0:n_desc_f] = f1 y_0     act[b] = f2 y_0     desc[b, n_desc_f + s - 1] = lr y_s  (s >= 1)
+ *   act (B, n_act), desc (B, n_desc_f + n_slots - 1) fp32.
+ *   Rounding: scene and embed_w are bf16 as given, products are exact (v_mfma_f32_16x16x32_bf16), accumulation is fp32;
+ *   a tap that leaves the map zero-fills and never reads the neighbouring camera's rows; scale, shift and ReLU are
+ *   fp32 and e is NOT rounded to bf16; the Linear and the predictors are fp32 FMA.
+ *   Launch A: one workgroup per (16-pixel tile, slot, sample) multiplies its 16 x (32 + Cp) values into the matching
+ *   columns of lin_w and writes an E-wide fp32 partial to the workspace; rows of a partial last tile contribute
+ *   nothing.  Launch B: one workgroup per sample adds the tile partials in ascending tile order, adds the bias and
+ *   runs the predictors.  No float atomics, no workgroup waits for another, no tile shape or summation order depends
+ *   on B: bit-identical run to run, and a sample's result does not depend on its batch.
+ *   lss_txt_heads_ok: 1 for 1 <= B <= 65535, 1 <= ncams <= 64, 1 <= n_slots <= 8, 1 <= H, W <= 1024, H W <= 65536,
+ *   1 <= Cp <= 8, 1 <= E <= 64, 1 <= n_act, n_desc_f <= 16; else LSS_E_SHAPE.
+ *   lss_txt_heads_workspace_bytes: B n_slots ceil(H W / 16) E floats (0 for sizes lss_txt_heads_ok refuses).
+ *   Argument checks, all before any HIP call: LSS_E_NULL (desc, scene, bev_post, the front set, f1, f2, workspace, the
+ *   outputs; the side set and lr when n_slots > 1), LSS_E_SHAPE (lss_txt_heads_ok, a camera index outside
+ *   0 .. ncams - 1), LSS_E_ALIGN (16 B for scene and the weight images, 4 B for every fp32 operand),
+ *   LSS_E_WORKSPACE.  Nothing is written when a check fails. */
+typedef struct lss_txt_heads_set {
+  const void* embed_w;
+  const float *embed_scale, *embed_shift, *lin_w, *lin_b;
+} lss_txt_heads_set_t;
+typedef struct lss_txt_heads_desc {
+  const void* scene;
+  const float* bev_post;
+  lss_txt_heads_set_t front, side;
+  const float *f1_w, *f1_b, *f2_w, *f2_b, *lr_w, *lr_b;
+  void* workspace;
+  float *act, *desc;
+  uint64_t workspace_bytes;
+  int32_t cams[8];
+  int32_t B, ncams, n_slots, H, W, Cp, E, n_act, n_desc_f, reserved;
+} lss_txt_heads_desc_t;
+int lss_bev_post_fwd(const float* x, long long sb, long long sc, long long sh, long long sw, int Hm, int Wm, int h0,
+                     int w0, int B, int Cb, int Hc, int Wc, const float* w, const float* scale, const float* shift,
+                     int Co, float* y, void* stream);
+int lss_txt_heads_ok(int B, int ncams, int n_slots, int H, int W, int Cp, int E, int n_act, int n_desc_f);
+size_t lss_txt_heads_workspace_bytes(int B, int n_slots, int H, int W, int E);
+int lss_txt_heads_fwd(const lss_txt_heads_desc_t* desc, void* stream);
+
 /* Layout / dtype conversion helpers between the reference's NCHW fp32 tensors
  * and the conv path's NHWC tensors. */
 int lss_nchw_f32_to_nhwc(const float* src, void* dst, int B, int C, int H, int W, int dt,

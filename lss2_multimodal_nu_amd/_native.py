@@ -141,6 +141,10 @@ SIGNATURES = {
     "lss_bev_pool_parts": (_i, [_i, ctypes.c_longlong]),
     "lss_bev_pool_fwd": (_i, [_vp, _i, _i, ctypes.c_longlong, _i, _i, _vp, _vp]),
     "lss_camera_tail_fwd": (_i, [_vp, _vp]),
+    "lss_bev_post_fwd": (_i, [_vp] + [ctypes.c_longlong] * 4 + [_i] * 8 + [_vp, _vp, _vp, _i, _vp, _vp]),
+    "lss_txt_heads_ok": (_i, [_i] * 9),
+    "lss_txt_heads_workspace_bytes": (_sz, [_i] * 5),
+    "lss_txt_heads_fwd": (_i, [_vp, _vp]),
     "lss_nchw_f32_to_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lss_nhwc_to_nchw_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }
@@ -188,6 +192,21 @@ class CameraTailDesc(ctypes.Structure):
                 + ("action", "description")] + \
                [(n, ctypes.c_float) for n in ("eps_cam", "eps_fuse", "eps_pred", "bev_scale")] + \
                [(n, ctypes.c_int32) for n in ("B", "N", "n_embed", "n_action", "n_desc", "bev_parts")]
+
+
+class TxtHeadsSet(ctypes.Structure):
+    """lss_txt_heads_set_t of include/lss_hip.h."""
+    _fields_ = [(n, _vp) for n in ("embed_w", "embed_scale", "embed_shift", "lin_w", "lin_b")]
+
+
+class TxtHeadsDesc(ctypes.Structure):
+    """lss_txt_heads_desc_t of include/lss_hip.h."""
+    PREDICTORS = ("f1_w", "f1_b", "f2_w", "f2_b", "lr_w", "lr_b")
+    _fields_ = [("scene", _vp), ("bev_post", _vp), ("front", TxtHeadsSet), ("side", TxtHeadsSet)] + \
+               [(n, _vp) for n in PREDICTORS + ("workspace", "act", "desc")] + \
+               [("workspace_bytes", ctypes.c_uint64), ("cams", ctypes.c_int32 * 8)] + \
+               [(n, ctypes.c_int32) for n in ("B", "ncams", "n_slots", "H", "W", "Cp", "E", "n_act", "n_desc_f",
+                                              "reserved")]
 
 
 _lib = None

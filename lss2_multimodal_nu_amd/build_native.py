@@ -35,6 +35,7 @@ SOURCES = {
     "linear_mfma.hip": [],
     "camera_branch.hip": [],
     "camera_tail.hip": [],
+    "txt_heads.hip": [],
     "ffn_fused.hip": [],
     "conv_grad.hip": [],
     "conv_wgrad.hip": [],

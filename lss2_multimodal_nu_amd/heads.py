@@ -4,7 +4,10 @@ OUT OF THE HOT PATH (<1 % of the FLOPs, "stays stock
 PyTorch on ROCm").  They exist here only so that `BEV_TXT` is constructible with
 the reference's `state_dict` layout; nothing in csrc/ touches them there.
 (`SceneUnder(in_channels=256)` inside `VoVNetBEVTransformer` is another matter: at
-inference its parameters are read by K13, model_vovnet_transformer._CameraBranchPlan.)
+inference its parameters are read by K13, model_vovnet_transformer._CameraBranchPlan.
+And with LSS_TXT_HEADS_NATIVE=1 `BEV_TXT`'s inference forward reads all of these modules'
+parameters through model_BEV_TXT._TxtHeadsPlan - K13's tap-list conv and K15,
+csrc/txt_heads.hip; the switch is off by default.)
 """
 import torch
 from torch import nn

@@ -29,7 +29,8 @@ from . import ops
 from .data import CalibrationPack, calib_matrices
 from .heads import (BevPost, Embedder_f1, Embedder_f2, Embedder_lr1, Embedder_lr2, Predictor,
                     SceneUnder)
-from .modules import BevEncode, CamEncode, _PRECISIONS, _needs_autograd, default_precision
+from .modules import (BevEncode, CamEncode, _FoldedConv, _PRECISIONS, _bn_is, _conv_is, _needs_autograd, _to_nhwc,
+                      default_precision)
 from .tools import QuickCumsum, cumsum_trick, gen_dx_bx  # noqa: F401  (reference's import surface)
 from .tools import head_weighted_cross_entropy
 
@@ -398,10 +399,143 @@ class LSS(_LiftSplatMixin, nn.Module):
         return head_weighted_cross_entropy(y, self.bevencode.up2[4], binimgs, _bev_class_weights(y.device, class_weights))
 
 
+# which form `BEV_TXT._txt_heads` took: "native" = K13's tap-list conv + K15 (LSS_TXT_HEADS_NATIVE=1, eval, no autograd,
+# bf16, GPU, fp32 head parameters, no forward hooks), "composition" = the modules on library ops
+TXT_HEADS_CALLS = {"native": 0, "composition": 0}
+# LSS_TXT_HEADS_NATIVE unset: off.  tests/test_modules_gpu.py pins act / desc of the bf16 model to the fp32 heads at rtol
+# 2e-3, which a bf16 scene map cannot meet; see DESIGN.md 4b for the measurement
+_TXT_HEADS_NATIVE_DEFAULT = "0"
+
+
+def _linear_is(m, cin, cout=None):
+    return (type(m) is nn.Linear and m.in_features == cin and m.bias is not None
+            and (cout is None or m.out_features == cout))
+
+
+class _TxtHeadsPlan:
+    """What the native TXT half reads of sceneunder, the embedders, bevpost and the predictors: one `_FoldedConv` per
+    conv (packed bf16 weights, BatchNorm folded to (scale, shift); rebuilt when a source tensor changes) and the Linear /
+    predictor tensors, handed to K15 where they lie (an in-place edit or a `load_state_dict` is seen by the next call)."""
+
+    MID, EMBED = 256, 32
+    HEADS = ("sceneunder", "embeder_f1", "embeder_f2", "embeder_lr1", "embeder_lr2", "predictorf1", "predictorf2",
+             "predictorlr", "bevpost")
+
+    def __init__(self, model):
+        self.modules = self.modules_of(model)
+        aspp = model.sceneunder[0]
+        self.aspp = [_FoldedConv(c[0], c[1]) for c in list(aspp.convs)[:4]]
+        self.pool = _FoldedConv(aspp.convs[4][1], aspp.convs[4][2], pack=False)
+        self.project = _FoldedConv(aspp.project[0], aspp.project[1], pack=False)
+        self.embed = [_FoldedConv(e[0], e[1]) for e in (model.embeder_f1, model.embeder_lr1)]
+        self.post = _FoldedConv(model.bevpost.post[0], model.bevpost.post[1], pack=False)
+
+    @staticmethod
+    def modules_of(model):
+        """Every module the TXT half runs, or None when the heads do not have the reference's structure: an ASPP over
+        `Cin` channels with 256 mid channels and three atrous rates, 3x3 embedders 256 -> 32, Flatten + Linear, single
+        Linear predictors (the side one with one class), BevPost = conv 3x3 / (2, 1) / pad 1, BN, ReLU, MaxPool (5, 4)."""
+        M, EC = _TxtHeadsPlan.MID, _TxtHeadsPlan.EMBED
+        try:
+            su, post = model.sceneunder, model.bevpost.post
+            aspp = su[0]
+            convs, proj = list(aspp.convs), aspp.project
+            if len(su) != 1 or len(convs) != 5 or not isinstance(convs[4][0], nn.AdaptiveAvgPool2d):
+                return None
+            cin = convs[0][0].in_channels
+            ok = (_conv_is(convs[0][0], 1, cin, M, False) and all(_conv_is(c[0], 3, cin, M, False) for c in convs[1:4])
+                  and _conv_is(convs[4][1], 1, cin, M, False) and _conv_is(proj[0], 1, 5 * M, M, False)
+                  and convs[4][0].output_size in (1, (1, 1)) and len(proj) == 4 and type(proj[3]) is nn.Dropout)
+            pairs = [(c[0], c[1]) for c in convs[:4]] + [(convs[4][1], convs[4][2]), (proj[0], proj[1])]
+            relus = [c[2] for c in convs[:4]] + [convs[4][3], proj[2]]
+            if not ok or not all(_bn_is(bn, M) for _, bn in pairs):
+                return None
+            for e1 in (model.embeder_f1, model.embeder_lr1):
+                if not (len(e1) == 3 and _conv_is(e1[0], 3, M, EC, False) and e1[0].dilation == (1, 1) and _bn_is(e1[1], EC)):
+                    return None
+                relus.append(e1[2])
+            pc = post[0]
+            if not (len(post) == 4 and isinstance(pc, nn.Conv2d) and pc.kernel_size == (3, 3) and pc.stride == (2, 1)
+                    and pc.padding == (1, 1) and pc.dilation == (1, 1) and pc.groups == 1 and pc.bias is None
+                    and pc.padding_mode == "zeros" and _bn_is(post[1], pc.out_channels) and type(post[3]) is nn.MaxPool2d
+                    and post[3].kernel_size == (5, 4) and post[3].stride in ((5, 4), None) and post[3].padding in (0, (0, 0))
+                    and post[3].dilation in (1, (1, 1)) and not post[3].ceil_mode and not post[3].return_indices):
+                return None
+            relus.append(post[2])
+            if not all(type(r) is nn.ReLU for r in relus):
+                return None
+            feat = model.embeder_f2[1].in_features
+            E = model.embeder_f2[1].out_features
+            for e2 in (model.embeder_f2, model.embeder_lr2):
+                if not (len(e2) == 2 and type(e2[0]) is nn.Flatten and e2[0].start_dim == 1 and e2[0].end_dim == -1
+                        and _linear_is(e2[1], feat, E)):
+                    return None
+            for pr, classes in ((model.predictorf1, None), (model.predictorf2, None), (model.predictorlr, 1)):
+                if not (len(pr) == 1 and _linear_is(pr[0], E, classes)):
+                    return None
+            return [m for name in _TxtHeadsPlan.HEADS for m in getattr(model, name).modules()]
+        except (AttributeError, IndexError, TypeError):
+            return None
+
+    def current(self, model):
+        mods = self.modules_of(model)
+        return mods is not None and len(mods) == len(self.modules) and all(a is b for a, b in zip(mods, self.modules))
+
+    def quiet(self):
+        """Eval mode everywhere and no forward (pre-)hook, on these modules or globally: a hook must keep seeing real
+        module calls."""
+        from torch.nn.modules import module as _m
+        if _m._global_forward_hooks or _m._global_forward_pre_hooks:
+            return False
+        return not any(m.training or m._forward_hooks or m._forward_pre_hooks for m in self.modules)
+
+    def tensors(self, model):
+        """The parameters K15 reads in place: (front (lin_w, lin_b), side (lin_w, lin_b), predictors)."""
+        pred = {"f1_w": model.predictorf1[0].weight, "f1_b": model.predictorf1[0].bias,
+                "f2_w": model.predictorf2[0].weight, "f2_b": model.predictorf2[0].bias,
+                "lr_w": model.predictorlr[0].weight, "lr_b": model.predictorlr[0].bias}
+        f2, lr2 = model.embeder_f2[1], model.embeder_lr2[1]
+        return (f2.weight, f2.bias), (lr2.weight, lr2.bias), pred
+
+    def run(self, model, x, bev_crop, ncams):
+        """x (BN, Cin, H, W) fp32, bev_crop (B, Cb, Hc, Wc) fp32 in any layout -> (act, desc) in eight launches; the
+        1280-channel concatenation, the upsampled pooling branch and the camera selections never exist."""
+        dt = ops.DT_BF16
+        M = self.MID
+        xn = _to_nhwc(x, dt)                                                          # 1
+        BN, H, W, _ = xn.shape
+        mean = x.float().mean(dim=(2, 3))                                             # 2: one library reduction
+        cat = torch.empty(BN, H, W, 4 * M, dtype=torch.bfloat16, device=x.device)
+        branches = []
+        for i, f in enumerate(self.aspp):
+            w, sc, sh = f.get(dt)
+            branches.append((w, f.conv.kernel_size[0], f.conv.dilation[0], sc, sh, i * M))
+        ops.tapconv(xn, branches, y=cat)                                              # 3: the four conv branches
+        _, gsc, gsh = self.pool.get(dt)
+        _, jsc, jsh = self.project.get(dt)
+        wg = self.pool.image("f32", lambda w32: w32[:, :, 0, 0].contiguous())
+        wj = self.project.image("main", lambda w32: ops.pack_conv_weight(w32[:, :4 * M].contiguous(), dt))
+        wjp = self.project.image("pool", lambda w32: w32[:, 4 * M:, 0, 0].contiguous())
+        bias = ops.camera_pool_bias(mean, wg, gsc, gsh, wjp)                          # 4: pooled branch -> bias
+        scene = torch.empty(BN, H, W, M, dtype=torch.bfloat16, device=x.device)
+        ops.tapconv(cat, [(wj, 1, 1, jsc, jsh, 0)], y=scene, img_bias=bias)           # 5: the projection
+        _, psc, psh = self.post.get(dt)
+        post = ops.bev_post(bev_crop, (0, 0), bev_crop.shape[2:], model.bevpost.post[0].weight.detach(), psc, psh)  # 6
+        (fw, fb), (sw, sb), pred = self.tensors(model)
+        sets = []
+        for f, lw, lb in ((self.embed[0], fw, fb), (self.embed[1], sw, sb)):
+            w, sc, sh = f.get(dt)
+            sets.append((w, sc, sh, lw.detach(), lb.detach()))
+        return ops.txt_heads(scene, post, sets[0], sets[1], {k: v.detach() for k, v in pred.items()},
+                             ops.TXT_HEADS_CAMS, ncams)                               # 7, 8
+
+
 class BEV_TXT(_LiftSplatMixin, nn.Module):
     """BEV segmentation + driving action / description heads.  The BEV half is the
     HIP path above; the TXT half (ASPP scene features, per-camera embedders, linear
-    predictors) is stock PyTorch, as SURVEY.md section 2 scopes it."""
+    predictors) is stock PyTorch, as SURVEY.md section 2 scopes it - unless
+    LSS_TXT_HEADS_NATIVE=1 sends its inference form to K13's tap-list conv and K15
+    (`_TxtHeadsPlan`)."""
 
     def __init__(self, bsize, grid_conf, data_aug_conf, outC, encoder=None, precision=None):
         nn.Module.__init__(self)
@@ -442,8 +576,53 @@ class BEV_TXT(_LiftSplatMixin, nn.Module):
         return (loss_bev + F.binary_cross_entropy_with_logits(act_f, act_gt, weight=w1)
                 + F.binary_cross_entropy_with_logits(desc, desc_gt, weight=w2))
 
+    def _txt_heads_native_ok(self, x, bev_crop):
+        """Does `_txt_heads` take the native route?  LSS_TXT_HEADS_NATIVE=1 (read at call time), eval without autograd,
+        GPU fp32 tensors, bf16 precision, fp32 head parameters on the same GPU, no forward hooks, the reference's module
+        structure, shapes `lss_tapconv_ok` and `lss_txt_heads_ok` accept."""
+        if os.environ.get("LSS_TXT_HEADS_NATIVE", _TXT_HEADS_NATIVE_DEFAULT) != "1":
+            return False
+        if not all(torch.is_tensor(t) and t.is_cuda and t.dim() == 4 and t.dtype == torch.float32 for t in (x, bev_crop)):
+            return False
+        if x.device != bev_crop.device or _PRECISIONS[self.precision or default_precision()] != ops.DT_BF16:
+            return False
+        if torch.is_grad_enabled() and (x.requires_grad or bev_crop.requires_grad or any(
+                p.requires_grad for n in _TxtHeadsPlan.HEADS for p in getattr(self, n).parameters())):
+            return False
+        plan = self.__dict__.get("_txt_plan")
+        if plan is None or not plan.current(self):
+            if _TxtHeadsPlan.modules_of(self) is None:
+                return False
+            plan = self.__dict__["_txt_plan"] = _TxtHeadsPlan(self)
+        if not plan.quiet():
+            return False
+        for m in plan.modules:
+            for t in list(m.parameters(recurse=False)) + list(m.buffers(recurse=False)):
+                if t.device != x.device or (t.is_floating_point() and t.dtype != torch.float32) or not t.is_contiguous():
+                    return False
+        ncams = self.data_aug_conf["Ncams"]
+        BN, Cin, H, W = x.shape
+        B, Cb, Hc, Wc = bev_crop.shape
+        pc, lin = self.bevpost.post[0], self.embeder_f2[1]
+        Cp, E = pc.out_channels, lin.out_features
+        if (ncams <= max(ops.TXT_HEADS_CAMS) or BN != B * ncams or Cin != plan.aspp[0].conv.in_channels
+                or Cb != pc.in_channels or not 1 <= Cb <= 8 or not 1 <= Cp <= 8
+                or ((((Hc - 1) // 2) + 1) // 5, Wc // 4) != (H, W) or lin.in_features != (_TxtHeadsPlan.EMBED + Cp) * H * W):
+            return False
+        return (ops.tapconv_ok(BN, H, W, Cin, _TxtHeadsPlan.MID) and ops.tapconv_ok(BN, H, W, 4 * _TxtHeadsPlan.MID,
+                                                                                   _TxtHeadsPlan.MID)
+                and ops.txt_heads_ok(B, ncams, len(ops.TXT_HEADS_CAMS), H, W, Cp, E, self.predictorf2[0].out_features,
+                                     self.predictorf1[0].out_features))
+
     def _txt_heads(self, x, bev_crop):
-        """TXT half: the BEV crop around the ego vehicle joins every camera's features (ref :285-334)."""
+        """TXT half: the BEV crop around the ego vehicle joins every camera's features (ref :285-334).  With
+        LSS_TXT_HEADS_NATIVE=1 the inference form runs on K13's tap-list conv and K15 in eight launches
+        (`_txt_heads_native_ok`); every other call is the composition below."""
+        if self._txt_heads_native_ok(x, bev_crop):
+            TXT_HEADS_CALLS["native"] += 1
+            with ops.region("txt_heads"):
+                return self._txt_plan.run(self, x, bev_crop, self.data_aug_conf["Ncams"])
+        TXT_HEADS_CALLS["composition"] += 1
         bev_post = self.bevpost(bev_crop)
         scene = self.sceneunder(x)
         ncams = self.data_aug_conf["Ncams"]

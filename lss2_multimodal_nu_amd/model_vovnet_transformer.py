@@ -32,7 +32,7 @@ from torch.nn import functional as F
 from . import modules, ops
 from .heads import SceneUnder
 from .model_BEV_TXT import _LiftSplatMixin, _histogram_guard
-from .modules import _FoldedConv, _PRECISIONS, _needs_autograd, _to_nhwc, default_precision
+from .modules import _FoldedConv, _PRECISIONS, _bn_is, _conv_is, _needs_autograd, _to_nhwc, default_precision
 from .tools import QuickCumsum, gen_dx_bx  # noqa: F401  (reference's import surface)
 from .tools import head_1x1, head_weighted_cross_entropy, weighted_cross_entropy
 from .transformer_modules import LightweightBEVTransformer
@@ -481,22 +481,6 @@ class AdaptiveFeaturePyramid(nn.Module):
 
     def forward(self, x):
         return self.fusion(torch.cat([self.scale1(x), self.scale2(x)], dim=1))
-
-
-def _conv_is(conv, k, cin=None, cout=None, bias=None):
-    """Is `conv` a plain k x k / stride 1 conv with padding = dilation * (k // 2) (any dilation)?"""
-    if not isinstance(conv, nn.Conv2d) or conv.kernel_size != (k, k) or conv.stride != (1, 1) or conv.groups != 1:
-        return False
-    d = conv.dilation
-    if d[0] != d[1] or conv.padding != (d[0] * (k // 2), d[0] * (k // 2)) or conv.padding_mode != "zeros":
-        return False
-    if (cin is not None and conv.in_channels != cin) or (cout is not None and conv.out_channels != cout):
-        return False
-    return bias is None or (conv.bias is not None) == bias
-
-
-def _bn_is(bn, c):
-    return isinstance(bn, nn.BatchNorm2d) and bn.num_features == c and bn.affine and bn.running_mean is not None
 
 
 class _CameraBranchPlan:

@@ -691,6 +691,22 @@ class _FoldedConv:
                                x2=x2, up=up, dt=dt)
 
 
+def _conv_is(conv, k, cin=None, cout=None, bias=None):
+    """Is `conv` a plain k x k / stride 1 conv with padding = dilation * (k // 2) (any dilation)?"""
+    if not isinstance(conv, nn.Conv2d) or conv.kernel_size != (k, k) or conv.stride != (1, 1) or conv.groups != 1:
+        return False
+    d = conv.dilation
+    if d[0] != d[1] or conv.padding != (d[0] * (k // 2), d[0] * (k // 2)) or conv.padding_mode != "zeros":
+        return False
+    if (cin is not None and conv.in_channels != cin) or (cout is not None and conv.out_channels != cout):
+        return False
+    return bias is None or (conv.bias is not None) == bias
+
+
+def _bn_is(bn, c):
+    return isinstance(bn, nn.BatchNorm2d) and bn.num_features == c and bn.affine and bn.running_mean is not None
+
+
 def _to_nhwc(x, dt):
     """(B,C,H,W) fp32 (contiguous or channels_last) -> (B,H,W,C) activations in dt."""
     if x.dtype == torch.bfloat16 and dt == ops.DT_BF16 and x.is_contiguous(memory_format=torch.channels_last):

@@ -2098,3 +2098,113 @@ def camera_tail(tokens, params, bev=None, bev_scale=1.0):
     with _timed("camera_tail"):
         N.check(N.lib().lss_camera_tail_fwd(ctypes.byref(d), N.stream()), "lss_camera_tail_fwd")
     return action, description
+
+
+# --- K15: the TXT half of BEV_TXT at inference behind the ASPP (csrc/txt_heads.hip) ----------------------------------
+def bev_post(bev, origin, size, weight, scale, shift):
+    """BevPost on a crop of `bev`, read in place (lss_bev_post_fwd): 3x3 conv, stride (2, 1), padding 1 around the CROP
+    -> scale / shift -> ReLU -> MaxPool (5, 4).
+
+    bev     (B, Cb <= 8, Hm, Wm) fp32 GPU tensor in ANY layout (its strides go to the kernel; nothing is copied)
+    origin  (h0, w0) and size (Hc, Wc) of the crop
+    weight  (Co <= 16, Cb, 3, 3) fp32 contiguous; scale / shift (Co) fp32
+    Returns (B, Co, (((Hc - 1) // 2) + 1) // 5, Wc // 4) fp32."""
+    if not torch.is_tensor(bev) or bev.dim() != 4 or bev.dtype != torch.float32 or not bev.is_cuda:
+        raise ValueError("bev must be a (B, Cb, Hm, Wm) fp32 GPU tensor")
+    B, Cb, Hm, Wm = bev.shape
+    (h0, w0), (Hc, Wc) = (int(v) for v in origin), (int(v) for v in size)
+    if weight.dim() != 4 or tuple(weight.shape[1:]) != (Cb, 3, 3):
+        raise ValueError("weight must be (Co, %d, 3, 3), got %s" % (Cb, tuple(weight.shape)))
+    Co = weight.shape[0]
+    _f32c(weight, "weight")
+    _f32c(scale, "scale", (Co,))
+    _f32c(shift, "shift", (Co,))
+    if not (0 <= h0 and 0 <= w0 and 1 <= Hc and 1 <= Wc and h0 + Hc <= Hm and w0 + Wc <= Wm):
+        raise ValueError("the crop (%d, %d) + (%d, %d) leaves the %d x %d map" % (h0, w0, Hc, Wc, Hm, Wm))
+    Ho, Wo = (((Hc - 1) // 2) + 1) // 5, Wc // 4
+    if not (1 <= B <= 65535 and 1 <= Cb <= 8 and 1 <= Co <= 16 and Ho >= 1 and Wo >= 1):
+        raise ValueError("bev_post: B=%d Cb=%d Co=%d crop %dx%d outside the kernel's limits" % (B, Cb, Co, Hc, Wc))
+    y = torch.empty(B, Co, Ho, Wo, dtype=torch.float32, device=bev.device)
+    sb, sc, sh, sw = bev.stride()
+    with _timed("bev_post"):
+        N.check(N.lib().lss_bev_post_fwd(N.ptr(bev), sb, sc, sh, sw, Hm, Wm, h0, w0, B, Cb, Hc, Wc, N.ptr(weight),
+                                         N.ptr(scale), N.ptr(shift), Co, N.ptr(y), N.stream()), "lss_bev_post_fwd")
+    return y
+
+
+def txt_heads_ok(B, ncams, n_slots, H, W, Cp, E, n_act, n_desc_f):
+    """Does K15 take these sizes?  (lss_txt_heads_ok)"""
+    return N.lib().lss_txt_heads_ok(int(B), int(ncams), int(n_slots), int(H), int(W), int(Cp), int(E), int(n_act),
+                                    int(n_desc_f)) == 1
+
+
+TXT_HEADS_CAMS = (1, 0, 3, 2, 5)  # front, then the reference's side order l1, l2, r1, r2 (model_BEV_TXT.py:293-332)
+_txt_heads_ws = {}
+
+
+def txt_heads(scene, bev_post_map, front, side, predictors, cams=TXT_HEADS_CAMS, ncams=6):
+    """Everything behind the scene map in two launches (lss_txt_heads_fwd).
+
+    scene         (B * ncams, H, W, 256) bf16 contiguous
+    bev_post_map  (B, Cp <= 8, H, W) fp32 contiguous
+    front, side   (embed_w [9][32][256] bf16 image, embed_scale (32), embed_shift (32), lin_w (E, (32 + Cp) H W),
+                  lin_b (E)): slot 0 takes `front`, every other slot `side` (None when there is one slot)
+    predictors    {"f1_w": (n_desc_f, E), "f1_b", "f2_w": (n_act, E), "f2_b", "lr_w": (1, E), "lr_b"} fp32, read in place
+    cams          the camera of each slot
+    Returns (act (B, n_act), desc (B, n_desc_f + len(cams) - 1)) fp32."""
+    if (not torch.is_tensor(scene) or scene.dim() != 4 or scene.dtype != torch.bfloat16 or not scene.is_contiguous()
+            or not scene.is_cuda or scene.shape[3] != 256):
+        raise ValueError("scene must be a contiguous (B * ncams, H, W, 256) bf16 GPU tensor")
+    BN, H, W, _ = scene.shape
+    cams = tuple(int(c) for c in cams)
+    ncams, n_slots = int(ncams), len(cams)
+    if ncams < 1 or BN % ncams != 0 or not 1 <= n_slots <= 8 or any(not 0 <= c < ncams for c in cams):
+        raise ValueError("txt_heads: %d images, ncams=%d, slots %s" % (BN, ncams, cams))
+    B = BN // ncams
+    if bev_post_map.dim() != 4 or tuple(bev_post_map.shape[0:1] + bev_post_map.shape[2:]) != (B, H, W):
+        raise ValueError("bev_post must be (%d, Cp, %d, %d), got %s" % (B, H, W, tuple(bev_post_map.shape)))
+    _f32c(bev_post_map, "bev_post")
+    Cp = bev_post_map.shape[1]
+    if front[3].dim() != 2 or predictors["f1_w"].dim() != 2 or predictors["f2_w"].dim() != 2:
+        raise ValueError("lin_w, f1_w and f2_w must be matrices")
+    E, n_desc_f, n_act = front[3].shape[0], predictors["f1_w"].shape[0], predictors["f2_w"].shape[0]
+    if not txt_heads_ok(B, ncams, n_slots, H, W, Cp, E, n_act, n_desc_f):
+        raise ValueError("lss_txt_heads_ok refuses B=%d ncams=%d slots=%d H=%d W=%d Cp=%d E=%d n_act=%d n_desc_f=%d"
+                         % (B, ncams, n_slots, H, W, Cp, E, n_act, n_desc_f))
+    if n_slots > 1 and side is None:
+        raise ValueError("side slots need the side set")
+    d = N.TxtHeadsDesc()
+    for name, group, dst in (("front", front, d.front), ("side", side if n_slots > 1 else None, d.side)):
+        if group is None:
+            continue
+        ew, esc, esh, lw, lb = group
+        if (ew.dtype != torch.bfloat16 or not ew.is_contiguous() or not ew.is_cuda or tuple(ew.shape) != (9, 32, 256)):
+            raise ValueError("%s: embed_w must be a contiguous bf16 GPU [9][32][256] image, got %s %s"
+                             % (name, ew.dtype, tuple(ew.shape)))
+        _f32c(esc, name + " embed_scale", (32,))
+        _f32c(esh, name + " embed_shift", (32,))
+        _f32c(lw, name + " lin_w", (E, (32 + Cp) * H * W))
+        _f32c(lb, name + " lin_b", (E,))
+        dst.embed_w, dst.embed_scale, dst.embed_shift = ew.data_ptr(), esc.data_ptr(), esh.data_ptr()
+        dst.lin_w, dst.lin_b = lw.data_ptr(), lb.data_ptr()
+    shapes = {"f1_w": (n_desc_f, E), "f1_b": (n_desc_f,), "f2_w": (n_act, E), "f2_b": (n_act,), "lr_w": (1, E),
+              "lr_b": (1,)}
+    for k in N.TxtHeadsDesc.PREDICTORS:
+        if k.startswith("lr") and n_slots == 1:
+            continue
+        t = _f32c(predictors[k], k, shapes[k])
+        if t.device != scene.device:
+            raise ValueError("%s lives on %s, the scene map on %s" % (k, t.device, scene.device))
+        setattr(d, k, t.data_ptr())
+    nbytes = N.lib().lss_txt_heads_workspace_bytes(B, n_slots, H, W, E)
+    ws = _cached_ws(_txt_heads_ws, (str(scene.device), nbytes), nbytes, scene.device)
+    act = torch.empty(B, n_act, dtype=torch.float32, device=scene.device)
+    desc = torch.empty(B, n_desc_f + n_slots - 1, dtype=torch.float32, device=scene.device)
+    d.scene, d.bev_post, d.workspace, d.workspace_bytes = scene.data_ptr(), bev_post_map.data_ptr(), ws.data_ptr(), nbytes
+    d.act, d.desc = act.data_ptr(), desc.data_ptr()
+    for s, c in enumerate(cams):
+        d.cams[s] = c
+    d.B, d.ncams, d.n_slots, d.H, d.W, d.Cp, d.E, d.n_act, d.n_desc_f = B, ncams, n_slots, H, W, Cp, E, n_act, n_desc_f
+    with _timed("txt_heads"):
+        N.check(N.lib().lss_txt_heads_fwd(ctypes.byref(d), N.stream()), "lss_txt_heads_fwd")
+    return act, desc
