@@ -1063,6 +1063,45 @@ int lss_txt_heads_ok(int B, int ncams, int n_slots, int H, int W, int Cp, int E,
 size_t lss_txt_heads_workspace_bytes(int B, int n_slots, int H, int W, int E);
 int lss_txt_heads_fwd(const lss_txt_heads_desc_t* desc, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * K16  training of the vovnet camera branch: the backward halves K13's tap-list conv lacks (csrc/tapconv_wgrad.hip).
+ * replaces: the ConvolutionBackward nodes that `loss.backward()` (train_vovnet_transformer.py:210) runs for the dilated
+ *           3x3 and the 1x1 convs of src/model_vovnet_transformer.py:176-214 and src/modules.py:147-207.  The INPUT
+ *           gradient of such a conv is lss_tapconv_fwd on the [tap'][Cin][Cout] image of lss_conv2d_pack_weights_dgrad
+ *           (padding = dilation, the live tap pattern is symmetric); the forward is lss_tapconv_fwd.
+ *
+ * lss_tapconv_wgrad: weight gradient of a conv with ksize 1 | 3, stride 1, padding = dilation (0 for ksize 1),
+ *        dw[o][c][ky][kx] = sum_{img, h, w} dy[img, h, w, o] * x[img, h + ky d, w + kx d, c]     (ky, kx) in {-1, 0, 1}^2
+ *   x (BN, H, W, Cin), dy (BN, H, W, Cout) bf16 NHWC, contiguous; dw (Cout, Cin, ksize, ksize) fp32 OIHW, fully
+ *   overwritten.  A tap is LIVE by lss_tapconv_fwd's rule, |ky d| < H and |kx d| < W; a dead tap's gradient is written
+ *   as exactly 0.  A live tap reads zero where it leaves the map: the source pixel is formed from (row, column) inside
+ *   ONE image, so it never reads another row's wrap-around or another image.
+ *   Arithmetic: v_mfma_f32_16x16x32_bf16 with K = the pixel index; products are exact, accumulation is fp32.  The
+ *   pixel dimension is transposed on the way into the matrix core (ds_read_b64_tr_b16) from position-major LDS images
+ *   of ONE image's x and dy - no channel-major copy in global memory - and one LDS image of x serves all live taps
+ *   (the tap's shift is applied to the address a lane supplies).  Workgroup = a 64 x 64 tile of (o, c), all live taps,
+ *   a contiguous range of images added in image order; the partial tiles go to the fp32 workspace and a second kernel
+ *   adds them in range order.  No float atomics, a plain barrier kernel: bit-identical run to run.
+ *   lss_tapconv_wgrad_ok: 1 for 1 <= BN <= 65535, H, W >= 1, H W <= 224 (two 128-B-per-pixel LDS images of H W rounded
+ *   up to 32 pixels, plus one zero row, in 64 KiB: 8 x 22 = 176 fits), and lss_tapconv_ok's channel rules - Cin % 64
+ *   == 0, 64 <= Cin <= 4096, Cout % 64 == 0, 64 <= Cout <= 1024; else LSS_E_SHAPE.
+ *   lss_tapconv_wgrad_workspace_bytes: splits x live taps x Cout x Cin floats, splits = ceil(BN / ceil(BN / clamp(512 /
+ *   ((Cin / 64)(Cout / 64)), 1, BN))); 0 for arguments the launcher refuses.
+ *   Argument checks, all before any HIP call: LSS_E_NULL (x, dy, workspace, dw), LSS_E_SHAPE (lss_tapconv_wgrad_ok,
+ *   dilation outside 1..1024), LSS_E_LAYOUT (ksize not 1 or 3), LSS_E_ALIGN (16 B for x, dy, workspace; 4 B for dw),
+ *   LSS_E_WORKSPACE.  Nothing is written when a check fails.
+ *
+ * lss_tapconv_bias_grad: dbias[img, o] = sum over the image's H W pixels of dz[img, h, w, o] - the gradient of
+ *   lss_tapconv_fwd's img_bias.  dz (BN, H, W, Cout) bf16 NHWC, dbias (BN, Cout) fp32.  One fixed summation order (32
+ *   fp32 chains per channel in pixel order, added in chain order), no atomics.  LSS_E_NULL (dz, dbias), LSS_E_SHAPE (BN
+ *   outside 1..65535, H or W outside 1..1024, H W > 65536, Cout % 64 != 0 or outside 64..1024), LSS_E_ALIGN (16 B for
+ *   dz, 4 B for dbias).  Nothing is written when a check fails. */
+int lss_tapconv_wgrad_ok(int BN, int H, int W, int Cin, int Cout);
+size_t lss_tapconv_wgrad_workspace_bytes(int BN, int H, int W, int Cin, int Cout, int ksize, int dilation);
+int lss_tapconv_wgrad(const void* x, const void* dy, int BN, int H, int W, int Cin, int Cout, int ksize, int dilation,
+                      void* workspace, size_t workspace_bytes, float* dw, void* stream);
+int lss_tapconv_bias_grad(const void* dz, int BN, int H, int W, int Cout, float* dbias, void* stream);
+
 /* Layout / dtype conversion helpers between the reference's NCHW fp32 tensors
  * and the conv path's NHWC tensors. */
 int lss_nchw_f32_to_nhwc(const float* src, void* dst, int B, int C, int H, int W, int dt,

@@ -145,6 +145,10 @@ SIGNATURES = {
     "lss_txt_heads_ok": (_i, [_i] * 9),
     "lss_txt_heads_workspace_bytes": (_sz, [_i] * 5),
     "lss_txt_heads_fwd": (_i, [_vp, _vp]),
+    "lss_tapconv_wgrad_ok": (_i, [_i] * 5),
+    "lss_tapconv_wgrad_workspace_bytes": (_sz, [_i] * 7),
+    "lss_tapconv_wgrad": (_i, [_vp, _vp] + [_i] * 7 + [_vp, _sz, _vp, _vp]),
+    "lss_tapconv_bias_grad": (_i, [_vp] + [_i] * 4 + [_vp, _vp]),
     "lss_nchw_f32_to_nhwc": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "lss_nhwc_to_nchw_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }

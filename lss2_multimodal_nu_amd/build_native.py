@@ -34,6 +34,7 @@ SOURCES = {
     "transformer_pointwise.hip": ["-fno-slp-vectorize"],  # scalar row arithmetic, as the kernels were measured
     "linear_mfma.hip": [],
     "camera_branch.hip": [],
+    "tapconv_wgrad.hip": ["-fno-slp-vectorize"],  # no v_pk_*_f32 next to MFMAs, as conv_ring.hip
     "camera_tail.hip": [],
     "txt_heads.hip": [],
     "ffn_fused.hip": [],

@@ -62,6 +62,23 @@ _DEPTH_TAIL_NATIVE_DEFAULT = "1"
 CAMERA_BRANCH_CALLS = {"native": 0, "composition": 0}
 # LSS_CAMERA_BRANCH_NATIVE unset: see DESIGN.md 4b for the measurement that decides this
 _CAMERA_BRANCH_NATIVE_DEFAULT = "1"
+# which form a TRAINING call of `scene_tokens` took (a module in training mode, or gradients wanted): "native" = the
+# conv-BN autograd units on the HIP kernels (bf16 autocast, GPU, K16 for the dilated weight gradients), "composition" =
+# the library ops.  CAMERA_BRANCH_CALLS counts the composition as before and does not count the native training form.
+CAMERA_BRANCH_TRAIN_CALLS = {"native": 0, "composition": 0}
+# LSS_CAMERA_BRANCH_TRAIN_NATIVE unset: see DESIGN.md 4b for the measurement that decides this
+_CAMERA_BRANCH_TRAIN_NATIVE_DEFAULT = "1"
+
+
+class _MapLike:
+    """Stand-in for a GPU (B, C, H, W) map that does not exist yet: what the training units' guards read of a tensor."""
+    is_cuda = True
+
+    def __init__(self, *shape):
+        self.shape = tuple(shape)
+
+    def dim(self):
+        return len(self.shape)
 # which form the six-token tail of `VoVNetBEVTransformer.forward` took on the inference branch: "native" = K14 (bev_pool +
 # camera_tail: eval, no autograd, fp32 parameters, GPU, no forward hooks), "composition" = the pooled map through
 # camera_transformer, bev_fusion and unified_predictor on library ops
@@ -849,14 +866,101 @@ class VoVNetBEVTransformer(_LiftSplatMixin, nn.Module):
         return Cin == plan.pyr[0].conv.in_channels and all(
             ops.tapconv_ok(BN, H, W, ci, _CameraBranchPlan.MID) for ci in (Cin, 256, 512, 1024))
 
+    def _camera_branch_train_call(self, c3):
+        """Is this `scene_tokens` call a training call: a module in training mode, or gradients wanted?"""
+        fp, su = self.feature_pyramid, self.sceneunder
+        if fp.training or su.training:
+            return True
+        return torch.is_grad_enabled() and ((torch.is_tensor(c3) and c3.requires_grad) or any(
+            p.requires_grad for m in (fp, su) for p in m.parameters()))
+
+    def _camera_branch_train_native_ok(self, c3):
+        """Does a differentiable `scene_tokens` take the native conv-BN units?  Autograd needed, bf16 autocast, a GPU
+        map, `feature_pyramid` and `sceneunder` in training mode with the reference's structure and no forward or
+        backward hooks on them or their children (here and globally), and every unit's own guard;
+        LSS_CAMERA_BRANCH_TRAIN_NATIVE=0 keeps the library composition."""
+        if os.environ.get("LSS_CAMERA_BRANCH_TRAIN_NATIVE", _CAMERA_BRANCH_TRAIN_NATIVE_DEFAULT) == "0":
+            return False
+        if not (torch.is_tensor(c3) and c3.is_cuda and c3.dim() == 4 and c3.dtype in (torch.float32, torch.bfloat16)):
+            return False
+        fp, su = self.feature_pyramid, self.sceneunder
+        if not (fp.training and su.training and modules._native_training()):
+            return False
+        if not (_needs_autograd(fp, c3) or _needs_autograd(su)):
+            return False
+        mods = _CameraBranchPlan.convs_of(fp, su)
+        if mods is None:
+            return False
+        from torch.nn.modules import module as _m
+        if (_m._global_forward_hooks or _m._global_forward_pre_hooks or _m._global_backward_hooks
+                or _m._global_backward_pre_hooks):
+            return False
+        children = [c for top in (fp, su) for c in top.modules()]
+        if any(not c.training or c._forward_hooks or c._forward_pre_hooks or c._backward_hooks or c._backward_pre_hooks
+               for c in children):
+            return False
+        if any(m.weight.device != c3.device for m in mods):
+            return False
+        BN, Cin, H, W = c3.shape
+        M = _CameraBranchPlan.MID
+        aspp = su[0]
+        x, pyr, p, cat = (_MapLike(BN, c, H, W) for c in (Cin, 2 * M, M, 4 * M))
+        s1, s2, fu, convs, proj = fp.scale1, fp.scale2, fp.fusion, aspp.convs, aspp.project
+        pool_bn = convs[4][2]
+        return (modules._biased_conv3x3_unit_ok(s1[0], s1[1], True, Cin) and "_lss_sync" not in s1[1].__dict__
+                and s1[0].weight.dtype == torch.float32
+                and modules._tapconv_unit_ok(s2[0], s2[1], x)
+                and modules._conv1x1_unit_ok(fu[0], fu[1], pyr)
+                and modules._conv1x1_unit_ok(convs[0][0], convs[0][1], p)
+                and all(modules._tapconv_unit_ok(c[0], c[1], p) for c in convs[1:4])
+                and modules._tapconv_unit_ok(proj[0], proj[1], cat, cin=4 * M)
+                and "_lss_sync" not in pool_bn.__dict__ and convs[4][1].weight.dtype == torch.float32)
+
+    def _camera_branch_train_tokens(self, c3):
+        """The training form of `scene_tokens` on the native conv-BN units (the caller has checked
+        `_camera_branch_train_native_ok`): no library convolution in either direction.  c3 becomes bf16 NHWC once;
+        the d = 1 pyramid branch is the fused 3x3 unit, the d = 2 branch and the three atrous convs are tap-list
+        units, the fusion and the ASPP's 1x1 branch are 1x1 units.  The pooled branch is constant over the image:
+        it runs in fp32 on (BN, 256) rows through the modules' own parameters and BatchNorm and enters the
+        projection as a per-image bias, so the projection reads the 1024-channel concat of the conv branches only."""
+        fp, aspp = self.feature_pyramid, self.sceneunder[0]
+        M = _CameraBranchPlan.MID
+        BN = c3.shape[0]
+
+        def cat(maps):  # logical NCHW views of NHWC memory -> one NHWC buffer, again as a logical NCHW view
+            return torch.cat([t.permute(0, 2, 3, 1) for t in maps], dim=3).permute(0, 3, 1, 2)
+
+        x = modules._nhwc_bf16(c3).permute(0, 3, 1, 2)
+        s1 = modules._train_conv_bn_act(fp.scale1[0], fp.scale1[1], x, True)
+        s2 = modules._train_tapconv_bn_act(fp.scale2[0], fp.scale2[1], x)
+        p = modules._train_conv1x1_bn_act(fp.fusion[0], fp.fusion[1], cat([s1, s2]))
+        convs, proj = aspp.convs, aspp.project
+        branches = [modules._train_conv1x1_bn_act(convs[0][0], convs[0][1], p)]
+        branches += [modules._train_tapconv_bn_act(c[0], c[1], p) for c in convs[1:4]]
+        wj = proj[0].weight
+        with torch.autocast("cuda", enabled=False):
+            g = p.mean(dim=(2, 3), dtype=torch.float32)
+            g = F.linear(g, convs[4][1].weight.view(M, M))
+            g = F.relu(convs[4][2](g.view(BN, M, 1, 1))).view(BN, M)
+            img_bias = F.linear(g, wj[:, 4 * M:, 0, 0])
+        y = modules._train_tapconv_bn_act(proj[0], proj[1], cat(branches), weight=wj[:, :4 * M], img_bias=img_bias)
+        return proj[3](y).mean(dim=(2, 3), dtype=torch.float32)
+
     def scene_tokens(self, c3):
         """c3 (B*N, C, fH, fW) -> the per-camera scene tokens (B*N, 256) fp32: feature pyramid, ASPP, mean over the map
         (ref :612-620).  At inference in bf16 on the GPU this is K13 (six launches, the scene map is never written);
-        every other call - fp32 precision, CPU, training, foreign modules - is the library composition."""
+        a training call under bf16 autocast on the GPU runs on the native conv-BN units (`_camera_branch_train_tokens`);
+        every other call - fp32 precision, CPU, fp16 autocast, foreign modules - is the library composition."""
         if self._camera_branch_native_ok(c3):
             CAMERA_BRANCH_CALLS["native"] += 1
             with ops.region("camera_branch"):
                 return self._camera_plan.tokens(c3)
+        if self._camera_branch_train_call(c3):
+            if self._camera_branch_train_native_ok(c3):
+                CAMERA_BRANCH_TRAIN_CALLS["native"] += 1
+                with ops.region("camera_branch_train"):
+                    return self._camera_branch_train_tokens(c3)
+            CAMERA_BRANCH_TRAIN_CALLS["composition"] += 1
         CAMERA_BRANCH_CALLS["composition"] += 1
         scene = self.sceneunder(self.feature_pyramid(c3))
         return scene.mean(dim=(2, 3))

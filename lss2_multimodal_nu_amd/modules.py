@@ -23,7 +23,11 @@ HIP kernels, chosen by `_train_conv_bn_act` / `_train_conv
     then `_BNActFn`.
   - `conv1x1 -> BatchNorm(train) -> ReLU` (the vovnet encoder's `compress`): the token GEMM
     node of the transformer's linears, then `_BNActFn` (`_train_conv1x1_bn_act`).
-`_conv3x3_native_ok` is the one guard of the 3x3 kernels.  What the guards turn down
+  - `conv (k 1 | 3, padding = dilation) -> BatchNorm(train) -> ReLU` on small maps (the dilated convs of
+    the vovnet camera branch, at most 224 pixels per image): ONE node, `_TapConvBNActFn` (the tap-list
+    conv of camera_branch.hip forward and for the input gradient, tapconv_wgrad.hip for the weight and
+    per-image bias gradients), behind its own guard `_tapconv_unit_ok`.
+`_conv3x3_native_ok` is the one guard of the dilation-1 3x3 kernels.  What the guards turn down
 (channel counts that are no multiple of 64, dilated or grouped convs, a conv bias without a
 train-mode BatchNorm behind it) and all plain-fp32 training go through torch's GPU ops.
 """
@@ -540,6 +544,87 @@ def _train_conv1x1_bn_act(conv, bn, x, relu=True):
         zb = _zero_bias[key] = torch.zeros(Cout, dtype=torch.float32, device=x.device)
     z = _LinearFn.apply(xn, conv.weight.view(Cout, conv.in_channels), zb)      # (B, H, W, Cout) bf16
     y = _bn_apply(_BNActFn, bn, (z.permute(0, 3, 1, 2),), None, relu)
+    return y if conv.bias is None else _absorb_conv_bias(conv, bn, y)
+
+
+class _TapConvBNActFn(torch.autograd.Function):
+    """One autograd node for `act(BN_train(tapconv(x, w, ksize, d) + img_bias[img]))` on small maps: a conv with ksize 1
+    or 3, stride 1, padding = dilation (the dilated pyramid branch and the ASPP convs of the vovnet camera branch, the
+    ASPP projection with the pooled branch as its per-image bias).  Forward: K13's tap-list conv writes z in bf16, then
+    the batch-statistics BatchNorm.  Backward: BatchNorm backward gives dz; the same tap-list conv on the flipped /
+    transposed weight image gives dx, K16 gives dw and the per-image bias gradient.  Logical (B,C,H,W) tensors in and
+    out, bf16 NHWC inside; every tensor comes from torch and nothing waits for the GPU, so the node can be captured
+    (after one eager step has allocated the cached workspaces).  The weight is packed per call."""
+
+    @staticmethod
+    def forward(ctx, x, weight, img_bias, gamma, beta, running_mean, running_var, momentum, eps, relu, ksize, dil):
+        xn = _nhwc_bf16(x)
+        w = weight.detach().float().contiguous()
+        g32 = gamma.detach().float().contiguous()
+        ib = None if img_bias is None else img_bias.detach().float().contiguous()
+        wp = ops.pack_conv_weight(w, ops.DT_BF16)
+        z = torch.empty(xn.shape[:3] + (w.shape[0],), dtype=torch.bfloat16, device=xn.device)
+        ops.tapconv(xn, [(wp, ksize, dil, None, None, 0)], y=z, img_bias=ib, relu=False, tag="tapconv_train_fwd")
+        y, mean, invstd = ops.bn_train_fwd(z, g32, beta.detach().float().contiguous(), running_mean, running_var,
+                                           momentum, eps, relu)
+        ctx.save_for_backward(xn, z, y, w, g32, mean, invstd)
+        ctx.cfg = (relu, ksize, dil, x.dtype, weight.dtype, gamma.dtype, None if img_bias is None else img_bias.dtype)
+        ctx.mark_non_differentiable(*[t for t in (running_mean, running_var) if t is not None])
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, gy):
+        xn, z, y, w, g32, mean, invstd = ctx.saved_tensors
+        relu, ksize, dil, dtx, dtw, dtg, dtb = ctx.cfg
+        need = ctx.needs_input_grad
+        dz, _, dgamma, dbeta = ops.bn_train_bwd(_nhwc_bf16(gy), y, z, g32, mean, invstd, relu, False)
+        gx = gw = gb = None
+        if need[0]:
+            wd = ops.pack_conv_weight_dgrad(w, ops.DT_BF16)
+            dx = torch.empty_like(xn)
+            ops.tapconv(dz, [(wd, ksize, dil, None, None, 0)], y=dx, relu=False, tag="tapconv_dgrad")
+            gx = _nchw_as(dx, dtx)
+        if need[1]:
+            gw = ops.tapconv_wgrad(xn, dz, ksize, dil).to(dtw)
+        if need[2]:
+            gb = ops.tapconv_bias_grad(dz).to(dtb)
+        return (gx, gw, gb, dgamma.to(dtg) if need[3] else None, dbeta.to(dtg) if need[4] else None,
+                None, None, None, None, None, None, None)
+
+
+def _tapconv_unit_ok(conv, bn, x, cin=None):
+    """Does `conv -> BatchNorm(train) -> act` on x (B, C_in, H, W) take `_TapConvBNActFn`?  (cin: the unit reads only the
+    conv's first `cin` input channels - the ASPP projection without its pooled branch.)  GPU and bf16 autocast, a
+    train-mode BatchNorm `_bn_native_ok` accepts and whose statistics are not synchronised over ranks, a conv with k in
+    {1, 3}, stride 1, padding = dilation (0 for k = 1), square dilation, one group, fp32 weights, and shapes the
+    tap-list conv takes in both directions and K16 takes for the weight gradient."""
+    if not (x.is_cuda and x.dim() == 4 and _native_training()):
+        return False
+    if not _bn_native_ok(bn, True) or "_lss_sync" in bn.__dict__:
+        return False
+    k, d = conv.kernel_size[0], conv.dilation[0]
+    if conv.kernel_size not in ((1, 1), (3, 3)) or conv.stride != (1, 1) or conv.dilation != (d, d) or conv.groups != 1:
+        return False
+    if conv.padding != ((d, d) if k == 3 else (0, 0)) or conv.padding_mode != "zeros":
+        return False
+    if conv.weight.dtype != torch.float32 or bn.num_features != conv.out_channels:
+        return False
+    if x.shape[1] != (conv.in_channels if cin is None else cin) or x.shape[1] > conv.in_channels:
+        return False
+    BN, Cin, H, W = x.shape
+    Cout = conv.out_channels
+    return (ops.tapconv_ok(BN, H, W, Cin, Cout) and ops.tapconv_ok(BN, H, W, Cout, Cin)
+            and ops.tapconv_wgrad_ok(BN, H, W, Cin, Cout))
+
+
+def _train_tapconv_bn_act(conv, bn, x, relu=True, weight=None, img_bias=None):
+    """act(bn(conv(x) + img_bias[img])) as ONE native node; the caller has checked `_tapconv_unit_ok`.  `weight`
+    replaces conv.weight (a slice of its input channels, with x as wide as the slice); a conv bias directly in front
+    of the train-mode BatchNorm is absorbed (`_absorb_conv_bias`)."""
+    w = conv.weight if weight is None else weight
+    y = _TapConvBNActFn.apply(x, w, img_bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.momentum),
+                              float(bn.eps), bool(relu), conv.kernel_size[0], conv.dilation[0])
+    _count_batch(bn)
     return y if conv.bias is None else _absorb_conv_bias(conv, bn, y)
 
 

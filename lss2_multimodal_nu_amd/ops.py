@@ -1965,6 +1965,53 @@ def tapconv(x, branches, y=None, img_bias=None, means=False, relu=True, tag="tap
     return out
 
 
+# --- K16: the backward halves of the tap-list conv (csrc/tapconv_wgrad.hip) ------------------------------------------
+def tapconv_wgrad_ok(BN, H, W, Cin, Cout):
+    """Does the tap-list weight-gradient kernel take (BN, H, W, Cin) x (BN, H, W, Cout)?  (lss_tapconv_wgrad_ok:
+    lss_tapconv_ok's channel rules and H W <= 224)"""
+    return N.lib().lss_tapconv_wgrad_ok(int(BN), int(H), int(W), int(Cin), int(Cout)) == 1
+
+
+def _nhwc_bf16_gpu(t, name):
+    if t.dim() != 4 or t.dtype != torch.bfloat16 or not t.is_contiguous() or not t.is_cuda:
+        raise ValueError("%s must be a contiguous (BN, H, W, C) bf16 GPU tensor" % name)
+
+
+def tapconv_wgrad(x, dy, ksize, dilation):
+    """Weight gradient of a conv with ksize 1 | 3, stride 1, padding = dilation (lss_tapconv_wgrad): x (BN, H, W, Cin),
+    dy (BN, H, W, Cout) contiguous bf16 NHWC -> dw (Cout, Cin, ksize, ksize) fp32, dead taps exactly 0,
+    bit-reproducible.  The workspace is cached per shape and device."""
+    _nhwc_bf16_gpu(x, "x")
+    _nhwc_bf16_gpu(dy, "dy")
+    BN, H, W, Cin = x.shape
+    Cout = dy.shape[3]
+    if tuple(dy.shape[:3]) != (BN, H, W):
+        raise ValueError("dy %s does not match x %s" % (tuple(dy.shape), tuple(x.shape)))
+    if ksize not in (1, 3) or int(dilation) < 1:
+        raise ValueError("ksize must be 1 or 3 and dilation >= 1")
+    if not tapconv_wgrad_ok(BN, H, W, Cin, Cout):
+        raise ValueError("lss_tapconv_wgrad_ok refuses BN=%d H=%d W=%d Cin=%d Cout=%d" % (BN, H, W, Cin, Cout))
+    nbytes = N.lib().lss_tapconv_wgrad_workspace_bytes(BN, H, W, Cin, Cout, ksize, int(dilation))
+    ws = _cached_ws(_wgrad_ws, ("tapconv", BN, H, W, Cin, Cout, ksize, int(dilation), str(x.device)), nbytes, x.device)
+    dw = torch.empty(Cout, Cin, ksize, ksize, dtype=torch.float32, device=x.device)
+    with _timed("tapconv_wgrad"):
+        N.check(N.lib().lss_tapconv_wgrad(N.ptr(x), N.ptr(dy), BN, H, W, Cin, Cout, ksize, int(dilation), N.ptr(ws),
+                                          nbytes, N.ptr(dw), N.stream()), "lss_tapconv_wgrad")
+    return dw
+
+
+def tapconv_bias_grad(dz):
+    """The gradient of `tapconv`'s img_bias (lss_tapconv_bias_grad): dz (BN, H, W, Cout) contiguous bf16 NHWC ->
+    (BN, Cout) fp32 sums over each image's pixels, one fixed order."""
+    _nhwc_bf16_gpu(dz, "dz")
+    BN, H, W, Cout = dz.shape
+    out = torch.empty(BN, Cout, dtype=torch.float32, device=dz.device)
+    with _timed("tapconv_bias_grad"):
+        N.check(N.lib().lss_tapconv_bias_grad(N.ptr(dz), BN, H, W, Cout, N.ptr(out), N.stream()),
+                "lss_tapconv_bias_grad")
+    return out
+
+
 def camera_pool_bias(mean, wg, scale, shift, wj, want_g=False):
     """The ASPP pooling branch as a per-image bias of the projection (lss_camera_pool_bias_fwd):
     g = relu(scale * (wg . mean) + shift) (BN, Cg), bias = wj . g (BN, Cout), all fp32.  Returns bias, or (g, bias)."""
